@@ -19,9 +19,17 @@ the prepared query batch resident in HBM:
 convention; reverse-scan cells are NOT counted) divided by the time of the alignment stage inside the step (HIP events on
 the launch stream).  `queries_per_s` = queries / whole step time and `ms_per_step` (the whole step) stand beside it.
 
-Secondary sections of the same line: "align_only" (configs[1]: 1000 x 100 000 all-vs-all alignment), "nucleotide_align"
-(configs[4], alignment step).  CPU baselines = the real reference (oracle/_ref/libmmref.so) on the host cores, bounded
-samples; they double as full-size parity checks of the timed run's results.
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: the headline fields,
+the stage times of the timed steps and the set-up times.  `--full` adds everything else to the same line: the search-semantics
+step, the two-call path, backtraces, the block aligner, the end-to-end pass, the stock / patched `mmseqs` modules, rooflines,
+the N-rank parity against the unsplit run, and the secondary sections "align_only" (configs[1]: 1000 x 100 000 all-vs-all
+alignment), "nucleotide_align" (configs[4], alignment step) and the nucleotide / translated searches.  CPU baselines (also
+`--full` only) = the real reference (oracle/_ref/libmmref.so) on the host cores, bounded samples; they double as full-size
+parity checks of the timed run's results.
+
+`--dump-outputs DIR` writes what the last timed step computed (hit lists and alignment records of a fixed, seeded sample of
+the queries, see dump_outputs) as DIR/<field>.npy; the inputs are generated from fixed seeds, so two builds can be compared
+output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -502,6 +510,30 @@ def choose_query_groups(n_ranks, requested=0):
     return best
 
 
+DUMP_QUERIES = 2000        # --dump-outputs: queries of the fixed sample (~22 MB at --max-seqs 300)
+DUMP_SEED = 20260
+
+
+def dump_outputs(out_dir, hits, counts, sw):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step - the prefilter's hit lists (PF_HIT_DTYPE
+    [nq][stride] + counts) and the alignment records of every listed pair (SW_HIT_DTYPE [nq][stride]) - for a fixed, seeded
+    sample of the queries, one .npy per field.  Slots past a query's count are written as 0.  Target ids in float64, the
+    rest in float32 (all exact)."""
+    nq, stride = hits.shape
+    sel = np.sort(np.random.default_rng(DUMP_SEED).choice(nq, size=min(nq, DUMP_QUERIES), replace=False))
+    n = counts[sel].astype(np.int64)
+    used = np.arange(stride)[None, :] < n[:, None]
+    arrays = {"query_index": sel.astype(np.float64), "pf_count": n.astype(np.float32),
+              "pf_target_id": np.where(used, hits[sel]["id"], 0).astype(np.float64)}
+    for f in ("score", "diagonal"):
+        arrays["pf_" + f] = np.where(used, hits[sel][f], 0).astype(np.float32)
+    for f in ("score", "q_end", "t_end", "q_start", "t_start", "word"):
+        arrays["sw_" + f] = np.where(used, sw[sel][f], 0).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, device_index=0):
     """BASELINE.json configs[2] / configs[3]: the timed steps and everything derived from them."""
     from mmseqs2_amd import capi, evalue, workloads as wl
@@ -625,6 +657,7 @@ def search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, devi
     res_t = torch.zeros((nq, stride, 6), dtype=torch.int32, device=dev) if sharded else None
     stat = {"pf_ms": [], "align_ms": [], "cells": 0, "pairs": 0}
     keep = {}
+    last = {}           # handles of the last timed step, downloaded by collect_last() once the clock has stopped
 
     def step(record):
         pfb.run()
@@ -636,8 +669,9 @@ def search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, devi
                 stat["pf_ms"].append(pfb.stage_ms()[6])
                 stat["align_ms"].append(a_ms)
                 stat["cells"], stat["pairs"] = fb.cells, fb.pairs
-            if record == "keep":
-                keep["fused"] = fb.fetch().reshape(nq, stride)
+            if record == "last":
+                last["fb"] = fb
+                return
             fb.free()
             return
         if lib_comm:
@@ -656,16 +690,9 @@ def search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, devi
                 stat["pf_ms"].append(pfb.stage_ms()[6])
                 stat["align_ms"].append(a_ms)
                 stat["cells"], stat["pairs"] = b.cells, b.pairs
-            if record == "keep":
-                import ctypes
-                hip = ctypes.CDLL("libamdhip64.so")
-                mh, mc, mf = np.zeros((nq, stride, 3), np.int32), np.zeros(nq, np.int32), np.zeros(nq, np.int32)
-                for dst, src in ((mh, dh), (mc, dc), (mf, df)):
-                    assert hip.hipMemcpy(dst.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(src), dst.nbytes, 2) == 0      # device -> host
-                keep["merged"] = (mh, mc, mf)
-                full, nrec = b.fetch_owned()
-                keep["full"] = full.view(np.int32).reshape(nq, stride, 6)
-                keep["records_gathered"] = nrec
+            if record == "last":
+                last["owned"] = (b, dh, dc, df)      # the merged lists stay with pfb until its next run
+                return
             b.free()
             return
         mh_t, mc_t, mf_t = D.exchange_and_merge_device(gpu, pfb, nq, stride, group=pg)
@@ -682,17 +709,42 @@ def search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, devi
             stat["pf_ms"].append(pfb.stage_ms()[6])
             stat["align_ms"].append(a_ms)
             stat["cells"], stat["pairs"] = b.cells, b.pairs
-        if record == "keep":
-            keep["merged"] = (mh_t.cpu().numpy(), mc_t.cpu().numpy(), mf_t.cpu().numpy())
-            keep["full"] = full.cpu().numpy()
+        if record == "last":
+            last["tensors"] = (mh_t, mc_t, mf_t, full)
         b.free()
+
+    def collect_last(download):
+        """the results of the last timed step into `keep` (download=True) and its handles freed"""
+        if "fb" in last:
+            fb = last.pop("fb")
+            if download:
+                keep["fused"] = fb.fetch().reshape(nq, stride)
+            fb.free()
+        elif "owned" in last:
+            b, dh, dc, df = last.pop("owned")
+            if download:
+                import ctypes
+                hip = ctypes.CDLL("libamdhip64.so")
+                mh, mc, mf = np.zeros((nq, stride, 3), np.int32), np.zeros(nq, np.int32), np.zeros(nq, np.int32)
+                for dst, src in ((mh, dh), (mc, dc), (mf, df)):
+                    assert hip.hipMemcpy(dst.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(src), dst.nbytes, 2) == 0      # device -> host
+                keep["merged"] = (mh, mc, mf)
+                full, nrec = b.fetch_owned()
+                keep["full"] = full.view(np.int32).reshape(nq, stride, 6)
+                keep["records_gathered"] = nrec
+            b.free()
+        elif "tensors" in last:
+            mh_t, mc_t, mf_t, full = last.pop("tensors")
+            if download:
+                keep["merged"] = (mh_t.cpu().numpy(), mc_t.cpu().numpy(), mf_t.cpu().numpy())
+                keep["full"] = full.cpu().numpy()
 
     for _ in range(max(args.warmup, 1)):          # at least one untimed pass sizes the working buffers
         step(None)
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    for i in range(args.steps):
+        step("last" if i == args.steps - 1 else True)
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = allreduce(torch, dist, [elapsed], "max")[0]
@@ -700,13 +752,23 @@ def search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, devi
     pf_ms = allreduce(torch, dist, [float(np.mean(stat["pf_ms"]))], "max")[0]
     cells, pairs = allreduce(torch, dist, [stat["cells"], stat["pairs"]])
     mem_free, mem_total = gpu.device_memory()     # after the timed steps: targets + index + every working buffer at its high-water mark
-    step("keep")                                  # one more pass whose results are downloaded for the checks below
+    # the last timed step's results: for the checks below (--full) and for --dump-outputs
+    collect_last(args.full or bool(args.dump_outputs))
+    if args.dump_outputs and rank_all == 0:
+        if sharded:
+            mh, mc, _ = keep["merged"]
+            d_hits = mh.reshape(nq, stride * 3).view(capi.PF_HIT_DTYPE).reshape(nq, stride)
+            d_sw = np.ascontiguousarray(keep["full"]).reshape(-1).view(capi.SW_HIT_DTYPE).reshape(nq, stride)
+            dump_outputs(args.dump_outputs, d_hits, mc, d_sw)
+        else:
+            d_hits, d_counts, _, _ = pfb.fetch()      # pfb still holds the last timed step's lists
+            dump_outputs(args.dump_outputs, d_hits, d_counts, keep["fused"])
 
     # ---- the same batch with the semantics of `mmseqs search` (alignment mode 2, StripedSmithWaterman.cpp:857-882): start positions
     # of the hits of the uint8 pass from the reverse scan, those of the int16-range hits from the block aligner, the reverse scan only
     # for what it declines.  Timed beside the step above (whose definition `value` keeps): whole steps, wall clock, all on the device.
     search = {"align_ms": [], "block_s": [], "pf_ms": []}
-    if not sharded:
+    if not sharded and args.full:
         def step_search(record):
             pfb.run()
             fb = gpu.sw_prepare_from_pf(mat, 11, 1, None, pfb, mode=2, marshalled=msh)
@@ -748,7 +810,7 @@ def search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, devi
                                       "second context of the rank's device (mmgpu_pf_exchange_redo_unsplit)"} if gpu_full is not None else None)}
     if gpu_full is not None:
         gpu_full.close()
-    if rank_all != 0:
+    if rank_all != 0 or not args.full:
         pfb.free()
         return out
 
@@ -1321,7 +1383,16 @@ def main():
                     help="1 (mmseqs' default): the targets are tantan-masked for the prefilter on the device (mmgpu_pf_mask_targets), the alignment reads them unmasked")
     ap.add_argument("--no-modules", action="store_true", help="skip the stock-vs-patched `mmseqs prefilter` / `align` wall times")
     ap.add_argument("--module-timeout", type=float, default=240.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the search-semantics step, two-call path, backtraces, block aligner, end-to-end "
+                         "pass, stock / patched modules, CPU baselines with their parity checks, rooflines, the align-only and nucleotide "
+                         "sections and the N-rank parity against the unsplit run.  Without it: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's hit lists and alignment records (a fixed, seeded sample of "
+                         "%d queries) as DIR/<field>.npy" % DUMP_QUERIES)
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import mmseqs2_amd
@@ -1363,7 +1434,7 @@ def main():
 
     H = search_headline(args, gpu, torch, dist, rank, world, matrices, barrier, device_index)
     side = {}
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         if not args.no_align_only:
             try:
                 side["align_only"] = align_only_section(args, gpu, torch, matrices, rank)
@@ -1394,10 +1465,28 @@ def main():
         value = H["cells"] / (k_ms * 1e-3) / 1e9
         stage = H["stage"]
         default_wl = (args.pf_families, args.pf_members, args.pf_queries) == (20000, 50, 10000) and world == 1
-        # algorithmic HBM bytes of the alignment kernels: tlen + 28 bytes per pair + the query once
-        alg_bytes = H["alg_bytes"]
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-        lane_ops = H["cells"] / 2.0 * 10.0       # 10 VOP3P lane-ops per pair of cells, forward scan only
+        roofline = None
+        if args.full:       # from the lists downloaded after the timed steps and the separate counter passes
+            # algorithmic HBM bytes of the alignment kernels: tlen + 28 bytes per pair + the query once
+            alg_bytes = H["alg_bytes"]
+            achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+            lane_ops = H["cells"] / 2.0 * 10.0       # 10 VOP3P lane-ops per pair of cells, forward scan only
+            roofline = {"kernel": "sw_kernel<G,true> (four concurrent grids: tile shapes grouped by register need, forward + reverse scan; + sw_rev_multi_kernel)",
+                        "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 6),
+                        "traffic": pmc_traffic(("sw_kernel<", "sw_rev_multi_kernel"), PROFILE_ROUND + "_search") if default_wl else None,
+                        "traffic_source": "profiles/%s_search_pmc_{fetch,write}_size.txt: FETCH_SIZE + WRITE_SIZE (KB) per launch, separate --pmc passes; "
+                                          "null unless those passes were taken with the device sources of this run (csrc_digest)" % PROFILE_ROUND,
+                        "csrc_digest": csrc_digest(),
+                        "algorithmic_bytes_per_launch": round(alg_bytes), "kernel_ms": round(k_ms, 3),
+                        "note": "Gotoh SW is VALU-issue bound (0.003 B/cell, SURVEY.md section 8d): the binding roof is valu_roofline",
+                        "valu_roofline": {"achieved_lane_ops_per_s": round(lane_ops / (k_ms * 1e-3), 1),
+                                          "peak_lane_ops_per_s": VALU_LANE_OPS_PER_S,
+                                          "frac": round(lane_ops / (k_ms * 1e-3) / VALU_LANE_OPS_PER_S, 4),
+                                          "counts": "forward cells only; the reverse scan of the pairs passing -e 1e-3 runs inside the same kernels",
+                                          "reverse_scan_cells": H.get("reverse_cells"),
+                                          "frac_incl_reverse_scan": (round((H["cells"] + H["reverse_cells"]) / 2.0 * 10.0 / (k_ms * 1e-3) / VALU_LANE_OPS_PER_S, 4)
+                                                                     if H.get("reverse_cells") is not None else None)}}
         out = {
             "metric": "sw_gcells_per_s", "value": round(value, 1), "unit": "GCUPS",
             "queries_per_s": round(nq * args.steps / H["elapsed_s"], 1),
@@ -1419,29 +1508,18 @@ def main():
                        "collectives": H.get("collectives")},
             "ms_per_step_stages": {"prefilter_kernels": round(H["pf_ms"], 2), "align_kernels": round(k_ms, 2),
                                    "handover_exchange_and_host": round(ms_per_step - H["pf_ms"] - k_ms, 2)},
-            "roofline": {"kernel": "sw_kernel<G,true> (four concurrent grids: tile shapes grouped by register need, forward + reverse scan; + sw_rev_multi_kernel)",
-                         "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6),
-                         "traffic": pmc_traffic(("sw_kernel<", "sw_rev_multi_kernel"), PROFILE_ROUND + "_search") if default_wl else None,
-                         "traffic_source": "profiles/%s_search_pmc_{fetch,write}_size.txt: FETCH_SIZE + WRITE_SIZE (KB) per launch, separate --pmc passes; "
-                                           "null unless those passes were taken with the device sources of this run (csrc_digest)" % PROFILE_ROUND,
-                         "csrc_digest": csrc_digest(),
-                         "algorithmic_bytes_per_launch": round(alg_bytes), "kernel_ms": round(k_ms, 3),
-                         "note": "Gotoh SW is VALU-issue bound (0.003 B/cell, SURVEY.md section 8d): the binding roof is valu_roofline",
-                         "valu_roofline": {"achieved_lane_ops_per_s": round(lane_ops / (k_ms * 1e-3), 1),
-                                           "peak_lane_ops_per_s": VALU_LANE_OPS_PER_S,
-                                           "frac": round(lane_ops / (k_ms * 1e-3) / VALU_LANE_OPS_PER_S, 4),
-                                           "counts": "forward cells only; the reverse scan of the pairs passing -e 1e-3 runs inside the same kernels",
-                                           "reverse_scan_cells": H.get("reverse_cells"),
-                                           "frac_incl_reverse_scan": (round((H["cells"] + H["reverse_cells"]) / 2.0 * 10.0 / (k_ms * 1e-3) / VALU_LANE_OPS_PER_S, 4)
-                                                                      if H.get("reverse_cells") is not None else None)}},
+            "roofline": roofline,
         }
+        if roofline is None:
+            del out["roofline"]
         pf = {"queries_per_s": round(nq / (H["pf_ms"] * 1e-3), 1),
               "stage_ms": {"kmers_lists": round(stage[0], 2), "gather_split": round(stage[1], 2), "replay_score_keepmax": round(stage[2], 2),
                            "large_bins_score": round(stage[3], 2), "large_bins_keepmax_and_overflow_path": round(stage[4], 2),
                            "select": round(stage[5], 2), "total": round(stage[6], 2)},
               "hbm_in_use_gb_after_steps": H["hbm_in_use_gb"],
-              "ungapped_cells": int(H["pf_cells"]), "double_diagonal_candidates": int(H["pf_cands"]), "prefilter_hits": int(H.get("nhits", 0))}
+              "ungapped_cells": int(H["pf_cells"]), "double_diagonal_candidates": int(H["pf_cands"])}
+        if args.full:        # counted from the lists downloaded after the timed steps
+            pf["prefilter_hits"] = int(H.get("nhits", 0))
         if "ent" in H:
             ent = H["ent"]
             alg = 20.0 * ent        # ~20 B per index entry touched

@@ -10,9 +10,9 @@ cd $R
 for f in bench_kernel_trace_stats bench_sw_timeline search_pmc_fetch_size search_pmc_write_size search_pmc_sq_insts_valu search_pmc_sq_active_inst_valu search_pmc_sq_busy_cycles search_pmc_sq_wave_cycles; do
   cp gpurun_out/profiles_new/$f.txt profiles/r06_$f.txt
 done
-python bench.py > $O/bench_n1.json 2> $O/bench_err.txt; tail -c 600 $O/bench_n1.json; echo
+python bench.py --full > $O/bench_n1.json 2> $O/bench_err.txt; tail -c 600 $O/bench_n1.json; echo
 for N in 2 4; do
-  MMGPU_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus $N --headline-only --no-cpu-baseline > $O/bench_${N}ranks_one_gpu_gloo_full.json 2> $O/bench_${N}ranks_err.txt
+  MMGPU_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus $N --headline-only --no-cpu-baseline > $O/bench_${N}ranks_one_gpu_gloo_full.json 2> $O/bench_${N}ranks_err.txt
   python - <<PY
 import json
 try:

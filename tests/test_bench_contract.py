@@ -1,5 +1,5 @@
 """The bench line the driver parses: the committed line of this round (profiles/r06_bench_n1.json, produced by
-`python bench.py` on the GPU box) must carry the contract's keys, be quoted on BASELINE.json's metric configuration (10k
+`python bench.py --full` on an MI355X) must carry the contract's keys, be quoted on BASELINE.json's metric configuration (10k
 queries x 1M targets), and its CPU-baseline legs - which double as full-size parity checks against the real reference -
 must have found no difference."""
 import json

@@ -6,8 +6,10 @@ CPU: the server's device library is the CPU stand-in of the C-ABI (oracle/_build
 GPU: the server owns the real device."""
 import ctypes
 import os
+import shutil
 import signal
 import subprocess
+import tempfile
 import time
 
 import pytest
@@ -21,6 +23,15 @@ CLIENT = os.path.join(ROOT, "mmseqs2_amd", "lib", "libmmgpu_client.so")
 
 pytestmark = pytest.mark.skipif(not (os.path.exists(STOCK) and os.path.exists(MMGPU) and os.path.exists(SERVER) and os.path.exists(CLIENT)),
                                 reason="needs the mmseqs binaries (integration/build_mmseqs.sh) and mmseqs2_amd/lib/mmgpu_server")
+
+
+@pytest.fixture
+def sock_dir():
+    """a short directory for the Unix sockets: sun_path holds 107 bytes, and pytest's tmp_path (which grows with the user
+    name and the test name) can be longer than that"""
+    d = tempfile.mkdtemp(prefix="mmgs", dir="/tmp" if os.access("/tmp", os.W_OK) else None)
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 class Server:
@@ -57,7 +68,7 @@ class Server:
         return self.p.stderr.read()
 
 
-def _pipeline(w, emulate):
+def _pipeline(w, emulate, sock_dir):
     (qres, qoff), (tres, toff), _, _ = wl.config3_prefilter(n_families=60, members=20, n_queries=40, seed=5)
     wl.write_fasta(os.path.join(w, "q.fasta"), qres, qoff, "q")
     wl.write_fasta(os.path.join(w, "t.fasta"), tres, toff, "t")
@@ -65,7 +76,7 @@ def _pipeline(w, emulate):
     run(STOCK, ["createdb", "t.fasta", "t", "-v", "1"], w)
     run(STOCK, ["prefilter", "q", "t", "pref_s", "-s", "5.7", "--threads", THREADS, "-v", "2"], w)
     run(STOCK, ["align", "q", "t", "pref_s", "aln_s", "-a", "--threads", THREADS, "-v", "2"], w)
-    srv = Server(os.path.join(w, "mmgpu.sock"), emulate)
+    srv = Server(os.path.join(sock_dir, "mmgpu.sock"), emulate)
     try:
         env = {"LD_PRELOAD": CLIENT, "MMGPU_SERVER_SOCKET": srv.sock}
         for rnd in range(2):
@@ -86,24 +97,24 @@ def _pipeline(w, emulate):
     assert not os.path.exists(srv.sock)
 
 
-def test_server_mode_host_side_emulated(tmp_path):
+def test_server_mode_host_side_emulated(tmp_path, sock_dir):
     if not os.path.exists(EMU):
         pytest.skip("oracle/_build/emu/libmmgpu.so not built (make -C oracle emu)")
-    _pipeline(str(tmp_path), emulate=True)
+    _pipeline(str(tmp_path), emulate=True, sock_dir=sock_dir)
 
 
-def test_client_without_server_fails_loudly(tmp_path):
+def test_client_without_server_fails_loudly(tmp_path, sock_dir):
     """no server, no silent CPU computation: the binary exits with the client library's message"""
     w = str(tmp_path)
     (qres, qoff), (tres, toff), _, _ = wl.config3_prefilter(n_families=10, members=5, n_queries=5, seed=1)
     wl.write_fasta(os.path.join(w, "q.fasta"), qres, qoff, "q")
     run(STOCK, ["createdb", "q.fasta", "q", "-v", "1"], w)
-    env = dict(os.environ, LD_PRELOAD=CLIENT, MMGPU_SERVER_SOCKET=os.path.join(w, "nobody.sock"))
+    env = dict(os.environ, LD_PRELOAD=CLIENT, MMGPU_SERVER_SOCKET=os.path.join(sock_dir, "nobody.sock"))
     r = subprocess.run([MMGPU, "prefilter", "q", "q", "pref", "--threads", "2", "-v", "3"], cwd=w, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode != 0 and "cannot connect to mmgpu_server" in r.stdout, r.stdout[-1500:]
 
 
 @pytest.mark.gpu
-def test_server_mode_on_device(tmp_path):
-    _pipeline(str(tmp_path), emulate=False)
+def test_server_mode_on_device(tmp_path, sock_dir):
+    _pipeline(str(tmp_path), emulate=False, sock_dir=sock_dir)
