@@ -47,6 +47,31 @@ static void free_db(DeviceDb &db) {
 }
 
 namespace mmgpu {
+// the context's pinned staging arena (mmgpu_ctx::pinned) for the length of a call.  acquire() grows the arena to `need`
+// bytes and returns it, or null - another thread's call holds it, or pinned memory cannot be had - and the caller copies from / to
+// pageable memory instead.  The holder lets go when it dies: keep it until the stream has passed the last copy that uses the arena
+struct PinnedLease {
+    mmgpu_ctx *c = nullptr;
+    PinnedLease() = default;
+    PinnedLease(const PinnedLease &) = delete;
+    PinnedLease &operator=(const PinnedLease &) = delete;
+    ~PinnedLease() { if (c) c->pinned_busy.store(false, std::memory_order_release); }
+    void *acquire(mmgpu_ctx *ctx, size_t need);
+};
+
+void *PinnedLease::acquire(mmgpu_ctx *ctx, size_t need) {
+    if (c || ctx->pinned_busy.exchange(true, std::memory_order_acquire)) return nullptr;
+    c = ctx;
+    if (need > ctx->pinned_cap) {      // grown by a quarter more than asked for: the next batch is about as large
+        if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+        ctx->pinned = nullptr;
+        ctx->pinned_cap = 0;
+        if (hipHostMalloc(&ctx->pinned, need + need / 4, hipHostMallocDefault) == hipSuccess) ctx->pinned_cap = need + need / 4;
+        else (void)hipGetLastError();   // pageable copies then
+    }
+    return ctx->pinned_cap >= need ? ctx->pinned : nullptr;
+}
+
 // what mmgpu_load_targets drops before it loads: the resident targets, their masked view, the index over them, the shard description
 void db_release(mmgpu_ctx *c) {
     pf_index_free(c);
@@ -552,39 +577,97 @@ struct DeviceLists {
     uint32_t stride = 0;
 };
 
-static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, int mode,
-                           const DeviceLists *pf, mmgpu_sw_batch_t **out) {
-    if (!c || !par || !out || (!qs && nq)) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: NULL argument");
-    const mmgpu_pf_hit *pf_hits = nullptr;
-    const uint32_t *pf_counts = nullptr;
-    uint32_t pf_stride = 0;
+namespace {
+
+// a batch under preparation: freed (with its buffers) unless the preparation hands it to the caller
+struct SwBatchFree {
+    mmgpu_ctx *c;
+    void operator()(mmgpu_sw_batch_t *b) const { mmgpu_sw_free(c, b); }
+};
+
+double prep_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// One call of sw_prepare_impl: its arguments, the batch, and the host arrays its steps hand to one another.  The steps run in the
+// order they are declared in.  Two of them depend on where the lists are: a list on the device (`pf`: the fused hand-over, the
+// lists of mmgpu_sw_prepare_from_lists, the owned pairs of a sharded run) gets fixed jobs over its slots while the queries are
+// copied and is ordered by sw_from_pf_kernel at the end (order_device_lists); a list of the caller is sorted and cut on the host
+// (cut_list_jobs, join_list_jobs) and uploaded as it stands.
+struct SwPrepare {
+    mmgpu_ctx *c;
+    const mmgpu_sw_params *par;
+    const mmgpu_sw_query *qs;
+    uint32_t nq;
+    int mode;
+    const DeviceLists *pf;        // null: the lists are the caller's (mmgpu_sw_query::target_ids)
+    mmgpu_sw_batch_t *b = nullptr;
+
+    std::vector<uint8_t> qres;
+    std::vector<int8_t> qcb, mat;
+    std::vector<uint32_t> qoff;
+    std::vector<int32_t> qbias, qminstart;
+    std::vector<int8_t> qprof;                       // profile queries: [alphabet][qlen] blocks, concatenated
+    std::vector<uint32_t> qprof_off;
+    std::vector<uint32_t> hit_target, hit_out;       // caller's lists only
+    std::vector<SwJob> jobs;
+    std::vector<SwJob> rev_jobs;          // multi-tile queries, mode START: the reverse scan runs per query (sw_rev_multi_kernel)
+    std::vector<uint64_t> rev_cells, job_cells;
+    std::vector<SwJob> sorted;            // the jobs as uploaded (asynchronously: lives until the stream is drained)
+    struct Deferred { uint32_t query, hit_cursor, out_cursor, shape, round; bool multi; };   // caller-supplied lists, scheduled by cut_list_jobs
+    std::vector<Deferred> deferred;
+    struct PerQuery { std::vector<SwJob> jobs; std::vector<uint64_t> cells; uint64_t sum_cells = 0; uint32_t max_tlen = 0; uint32_t rev_mid_len = 0; bool bad = false; };
+    std::vector<PerQuery> per_query;      // [deferred.size()]
+    uint64_t total_hits = 0;
+    uint32_t pf_stride = 0, n_multi = 0, max_tlen = 0;
+    uint32_t hit_cursor = 0, out_cursor = 0;
+    int minp = 0;
+    bool any_multi = false;
+    PinnedLease pinned;                   // the context's staging arena, from enqueue_uploads until the call ends (stream drained)
+    double mark = prep_now();
+
+    void lap(const char *what);
+    int check_params();
+    void new_batch();
+    int size_buffers();
+    int copy_query(uint32_t i, int *qminp);
+    void add_slot_jobs(uint32_t i, uint32_t shape, uint32_t round, bool multi);
+    void add_rev_jobs(uint32_t query, uint32_t first, uint32_t n, uint32_t shape, uint64_t cells_per_hit);
+    int copy_queries();
+    void cut_list_jobs_of(size_t from, size_t to);
+    void cut_list_jobs();
+    int join_list_jobs();
+    void order_jobs();
+    int enqueue_uploads();
+    hipError_t alloc_scratch(uint32_t longest);
+    int finish_host_lists();
+    int order_device_lists();
+};
+
+// where the host side of a batch's preparation goes
+void SwPrepare::lap(const char *what) {
+    static const bool prep_trace = getenv("MMGPU_TRACE") != nullptr;
+    if (!prep_trace) return;
+    const double t = prep_now();
+    fprintf(stderr, "[mmgpu sw_prepare] %s %.3f s\n", what, t - mark);
+    mark = t;
+}
+
+int SwPrepare::check_params() {
     if (pf) {
-        pf_hits = pf->hits;
-        pf_counts = pf->counts;
         pf_stride = pf->stride;
         if (pf_stride > (uint32_t)SW_PF_MAX_LIST) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare_from_pf: lists longer than 16384");
     }
     if (!c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_sw_prepare: no targets loaded");
-    static const bool prep_trace = getenv("MMGPU_TRACE") != nullptr;      // where the host side of a batch's preparation goes
-    auto prep_now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double prep_mark = prep_now();
-    auto prep_lap = [&](const char *what) {
-        if (!prep_trace) return;
-        const double t = prep_now();
-        fprintf(stderr, "[mmgpu sw_prepare] %s %.3f s\n", what, t - prep_mark);
-        prep_mark = t;
-    };
     if (par->alphabet != c->db.alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: alphabet differs from the loaded targets");
     if (mode != MMGPU_SW_SCORE_END && mode != MMGPU_SW_START && mode != MMGPU_SW_START_NOT_WORD) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: unknown mode");
     if (par->gap_open < par->gap_extend || par->gap_extend < 0 || par->gap_open > 32767)
         return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: need 0 <= gap_extend <= gap_open");
     // The cell-by-cell recurrence equals the reference's striped lazy-F result only if opening a gap right after
-    // a gap in the other direction never beats a substitution (StripedSmithWaterman.cpp:205).
-    int minp = 0;
+    // a gap in the other direction never beats a substitution (StripedSmithWaterman.cpp:205): checked per query in copy_query
     for (int i = 0; i < par->alphabet * par->alphabet; i++) minp = std::min<int>(minp, par->mat[i]);
-    HIP_TRY(hipSetDevice(c->device));
+    return MMGPU_OK;
+}
 
-    mmgpu_sw_batch_t *b = new mmgpu_sw_batch_t();
+void SwPrepare::new_batch() {
     b->mode = mode;
     b->alphabet = par->alphabet;
     b->gap_open = par->gap_open;
@@ -592,94 +675,116 @@ static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu
     b->n_queries = nq;
     for (DevBuf *d : {&b->d_qres, &b->d_qcb, &b->d_qoff, &b->d_qbias, &b->d_qminstart, &b->d_hit_target, &b->d_hit_out, &b->d_out,
                       &b->d_mat, &b->d_stats, &b->d_bt_scratch, &b->d_bt_jobs, &b->d_bt_info, &b->d_bt_str, &b->d_bt_cursor, &b->d_scratch_busy,
-                      &b->d_pf_counts, &b->d_slot_target, &b->d_qprof, &b->d_qprof_off, &b->d_qout_off, &b->d_out_target})
+                      &b->d_pf_counts, &b->d_slot_target, &b->d_qprof, &b->d_qprof_off, &b->d_qout_off, &b->d_out_target, &b->d_jobs, &b->d_scratch})
         d->bind(c->cache);
+}
 
-    std::vector<uint8_t> qres;
-    std::vector<int8_t> qcb;
-    std::vector<uint32_t> qoff(nq + 1, 0);
-    std::vector<int32_t> qbias(std::max<uint32_t>(nq, 1), 0), qminstart(std::max<uint32_t>(nq, 1), 0);
-    std::vector<int8_t> qprof;                       // profile queries: [alphabet][qlen] blocks, concatenated
-    std::vector<uint32_t> qprof_off(std::max<uint32_t>(nq, 1), 0xFFFFFFFFu);
-    uint64_t total_hits = 0;
+int SwPrepare::size_buffers() {
+    qoff.assign(nq + 1, 0);
+    qbias.assign(std::max<uint32_t>(nq, 1), 0);
+    qminstart.assign(std::max<uint32_t>(nq, 1), 0);
+    qprof_off.assign(std::max<uint32_t>(nq, 1), 0xFFFFFFFFu);
     for (uint32_t i = 0; i < nq; i++) {
         // a query without targets may come without residues (Alignment::run never maps the query of an empty list, :322)
         const bool empty_ok = !pf && qs[i].n_targets == 0 && qs[i].qlen == 0;
-        if (!empty_ok && (qs[i].qlen == 0 || qs[i].qlen > 65535 || !qs[i].q)) { delete b; return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: bad query"); }
+        if (!empty_ok && (qs[i].qlen == 0 || qs[i].qlen > 65535 || !qs[i].q)) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: bad query");
         qoff[i + 1] = qoff[i] + qs[i].qlen;
         total_hits += pf ? pf_stride : qs[i].n_targets;
     }
-    if (total_hits > 0xFFFFFFF0ull) { delete b; return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: more than 2^32 pairs in one batch"); }
+    if (total_hits > 0xFFFFFFF0ull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: more than 2^32 pairs in one batch");
     qres.resize(qoff[nq]);
     qcb.assign(qoff[nq], 0);
-    std::vector<uint32_t> hit_target(pf ? 0 : (size_t)total_hits), hit_out(pf ? 0 : (size_t)total_hits);
-    b->d_jobs.bind(c->cache);
-    b->d_scratch.bind(c->cache);
-    std::vector<SwJob> jobs;
-    std::vector<SwJob> rev_jobs;          // multi-tile queries, mode START: the reverse scan runs per query (sw_rev_multi_kernel)
-    std::vector<uint64_t> rev_cells;
-    std::vector<uint64_t> job_cells;
-    uint32_t n_multi = 0;
-    struct Deferred { uint32_t query, hit_cursor, out_cursor, shape, round; bool multi; };   // caller-supplied lists, scheduled below
-    std::vector<Deferred> deferred;
-    uint32_t hit_cursor = 0, out_cursor = 0;
+    if (!pf) {
+        hit_target.resize((size_t)total_hits);
+        hit_out.resize((size_t)total_hits);
+    }
     b->h_qout_off.assign(nq + 1, 0);
     if (mode >= MMGPU_SW_START && !pf) b->h_out_target.resize((size_t)total_hits);
-    uint32_t max_tlen = 0;
-    bool any_multi = false;
-    // Reverse-scan jobs of a multi-tile query: consecutive slots of its list, as many as hold about six forward jobs'
-    // worth of cells (one pair in six reaches the start-score threshold on hit lists), whole workgroup rounds, at most
-    // SW_REV_JOB_MAX; the kernel packs the live pairs of a job before it deals them to its waves.
-    auto add_rev_jobs = [&](uint32_t query, uint32_t first, uint32_t n, uint32_t shape, uint64_t cells_per_hit) {
-        uint64_t per = 6 * JOB_CELLS / std::max<uint64_t>(cells_per_hit, 1);
-        per = std::min<uint64_t>(std::max<uint64_t>(per / JOB_ROUND * JOB_ROUND, JOB_ROUND), (uint64_t)SW_REV_JOB_MAX);
-        for (uint32_t k = 0; k < n; k += (uint32_t)per) {
-            SwJob j;
-            j.query = query;
-            j.hit_begin = first + k;
-            j.hit_end = first + std::min<uint32_t>(k + (uint32_t)per, n);
-            j.shape = shape;
-            rev_jobs.push_back(j);
-            rev_cells.push_back(cells_per_hit * (j.hit_end - j.hit_begin) * 65536u + (n - k));
-        }
-    };
+    return MMGPU_OK;
+}
+
+// residues, composition bias / profile rows, bias and start-score threshold of query i; *qminp = its lowest substitution score
+int SwPrepare::copy_query(uint32_t i, int *qminp) {
+    const mmgpu_sw_query &Q = qs[i];
+    memcpy(qres.data() + qoff[i], Q.q, Q.qlen);
+    int mincb = 0;
+    *qminp = minp;
+    for (uint32_t k = 0; k < Q.qlen; k++) {
+        if (Q.q[k] >= par->alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: query residue code >= alphabet");
+        if (Q.comp_bias && !Q.profile) { qcb[qoff[i] + k] = Q.comp_bias[k]; mincb = std::min<int>(mincb, Q.comp_bias[k]); }
+    }
+    if (Q.profile) {
+        // ssw_init with a profile query (StripedSmithWaterman.cpp:1386-1406): the first PROFILE_AA_SIZE letter rows are the
+        // profile, the X row scores 0, no composition bias; bias = |min| over the profile rows
+        if (Q.profile_letters == 0 || (int)Q.profile_letters > par->alphabet)
+            return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: profile_letters must be in [1, alphabet]");
+        if (qprof.size() + (size_t)par->alphabet * Q.qlen > 0xFFFFFFF0ull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: more than 4 GB of query profiles in one batch");
+        qprof_off[i] = (uint32_t)qprof.size();
+        qprof.resize(qprof.size() + (size_t)par->alphabet * Q.qlen, 0);
+        const uint32_t rows = std::min<uint32_t>(Q.profile_letters, (uint32_t)par->alphabet - 1);   // :1389-1390 zeroes the last letter (X)
+        memcpy(qprof.data() + qprof_off[i], Q.profile, (size_t)rows * Q.qlen);
+        *qminp = 0;
+        for (size_t k = 0; k < (size_t)Q.profile_letters * Q.qlen; k++) *qminp = std::min<int>(*qminp, Q.profile[k]);
+        b->any_profile = true;
+        b->h_query_is_profile.resize(nq, 0);
+        b->h_query_is_profile[i] = 1;
+    }
+    if (!(*qminp + mincb + par->gap_extend > -par->gap_open))
+        return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: gap penalties too small for this matrix (adjacent insertion+deletion could win)");
+    qbias[i] = std::abs(*qminp) + std::abs(mincb);   // ssw_init :1397-1406
+    qminstart[i] = Q.min_start_score;
+    return MMGPU_OK;
+}
+
+// Reverse-scan jobs of a multi-tile query: consecutive slots of its list, as many as hold about six forward jobs'
+// worth of cells (one pair in six reaches the start-score threshold on hit lists), whole workgroup rounds, at most
+// SW_REV_JOB_MAX; the kernel packs the live pairs of a job before it deals them to its waves.
+void SwPrepare::add_rev_jobs(uint32_t query, uint32_t first, uint32_t n, uint32_t shape, uint64_t cells_per_hit) {
+    uint64_t per = 6 * JOB_CELLS / std::max<uint64_t>(cells_per_hit, 1);
+    per = std::min<uint64_t>(std::max<uint64_t>(per / JOB_ROUND * JOB_ROUND, JOB_ROUND), (uint64_t)SW_REV_JOB_MAX);
+    for (uint32_t k = 0; k < n; k += (uint32_t)per) {
+        SwJob j;
+        j.query = query;
+        j.hit_begin = first + k;
+        j.hit_end = first + std::min<uint32_t>(k + (uint32_t)per, n);
+        j.shape = shape;
+        rev_jobs.push_back(j);
+        rev_cells.push_back(cells_per_hit * (j.hit_end - j.hit_begin) * 65536u + (n - k));
+    }
+}
+
+// a list on the device: fixed jobs over the query's slots, the kernel clips them to the list length (SwLaunch::q_hit_count); order
+// and statistics come from sw_from_pf_kernel.  Hits per job: as many rounds as fit JOB_CELLS at the length the hits will probably
+// have (prefilter hits are mostly about as long as the query; the database mean otherwise)
+void SwPrepare::add_slot_jobs(uint32_t i, uint32_t shape, uint32_t round, bool multi) {
+    const mmgpu_sw_query &Q = qs[i];
+    const uint64_t est_cells = (uint64_t)Q.qlen * ((Q.qlen + c->mean_len) / 2 + 1) * round;
+    const uint32_t per_job = job_slots(round, JOB_CELLS / est_cells);
+    for (uint32_t k = 0; k < pf_stride; k += per_job) {
+        SwJob j;
+        j.query = i;
+        j.hit_begin = hit_cursor + k;
+        j.hit_end = hit_cursor + std::min<uint32_t>(k + per_job, pf_stride);
+        j.shape = shape | (multi ? n_multi++ << 8 : 0u);
+        jobs.push_back(j);
+        // stand-in for the cell count the host cannot see: query length x slots; the lists are sorted by
+        // target length on the device, so among equals a query's earlier jobs hold the longer targets
+        job_cells.push_back((uint64_t)Q.qlen * (j.hit_end - j.hit_begin) * 65536u + (pf_stride - k));
+    }
+    if (multi && mode >= MMGPU_SW_START)
+        add_rev_jobs(i, hit_cursor, pf_stride, shape, (uint64_t)Q.qlen * ((Q.qlen + c->mean_len) / 2 + 1));
+    max_tlen = c->db.max_len;
+}
+
+int SwPrepare::copy_queries() {
     for (uint32_t i = 0; i < nq; i++) {
         const mmgpu_sw_query &Q = qs[i];
         if (Q.qlen == 0) {      // empty list, no residues: no jobs, no result slots
             b->h_qout_off[i + 1] = out_cursor;
             continue;
         }
-        memcpy(qres.data() + qoff[i], Q.q, Q.qlen);
-        int mincb = 0;
-        int qminp = minp;
-        for (uint32_t k = 0; k < Q.qlen; k++) {
-            if (Q.q[k] >= par->alphabet) { delete b; return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: query residue code >= alphabet"); }
-            if (Q.comp_bias && !Q.profile) { qcb[qoff[i] + k] = Q.comp_bias[k]; mincb = std::min<int>(mincb, Q.comp_bias[k]); }
-        }
-        if (Q.profile) {
-            // ssw_init with a profile query (StripedSmithWaterman.cpp:1386-1406): the first PROFILE_AA_SIZE letter rows are the
-            // profile, the X row scores 0, no composition bias; bias = |min| over the profile rows
-            if (Q.profile_letters == 0 || (int)Q.profile_letters > par->alphabet) {
-                delete b;
-                return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: profile_letters must be in [1, alphabet]");
-            }
-            if (qprof.size() + (size_t)par->alphabet * Q.qlen > 0xFFFFFFF0ull) { delete b; return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: more than 4 GB of query profiles in one batch"); }
-            qprof_off[i] = (uint32_t)qprof.size();
-            qprof.resize(qprof.size() + (size_t)par->alphabet * Q.qlen, 0);
-            const uint32_t rows = std::min<uint32_t>(Q.profile_letters, (uint32_t)par->alphabet - 1);   // :1389-1390 zeroes the last letter (X)
-            memcpy(qprof.data() + qprof_off[i], Q.profile, (size_t)rows * Q.qlen);
-            qminp = 0;
-            for (size_t k = 0; k < (size_t)Q.profile_letters * Q.qlen; k++) qminp = std::min<int>(qminp, Q.profile[k]);
-            b->any_profile = true;
-            b->h_query_is_profile.resize(nq, 0);
-            b->h_query_is_profile[i] = 1;
-        }
-        if (!(qminp + mincb + par->gap_extend > -par->gap_open)) {
-            delete b;
-            return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: gap penalties too small for this matrix (adjacent insertion+deletion could win)");
-        }
-        qbias[i] = std::abs(qminp) + std::abs(mincb);   // ssw_init :1397-1406
-        qminstart[i] = Q.min_start_score;
+        int qminp;
+        if (int e = copy_query(i, &qminp)) return e;
         int rpl; bool multi;
         pick_class(Q.qlen, &rpl, &multi);
         any_multi |= multi;
@@ -689,263 +794,269 @@ static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu
         // jobs are cut at multiples of one workgroup round (4 waves x 8 targets); for queries of several tiles a
         // single wave's 8 targets already run for milliseconds, so those are cut per wave to shorten the tail
         const uint32_t round = (multi && Q.qlen >= LONG_QUERY) ? JOB_ROUND / 4 : JOB_ROUND;
-        if (pf) {
-            // the list is on the device: fixed jobs over the query's slots, the kernel clips them to the list length
-            // (SwLaunch::q_hit_count); order and statistics come from sw_from_pf_kernel.  Hits per job: as many rounds as fit JOB_CELLS at the length the hits will probably have (prefilter hits are
-            // mostly about as long as the query; the database mean otherwise)
-            const uint64_t est_cells = (uint64_t)Q.qlen * ((Q.qlen + c->mean_len) / 2 + 1) * round;
-            const uint32_t per_job = job_slots(round, JOB_CELLS / est_cells);
-            for (uint32_t k = 0; k < pf_stride; k += per_job) {
-                SwJob j;
-                j.query = i;
-                j.hit_begin = hit_cursor + k;
-                j.hit_end = hit_cursor + std::min<uint32_t>(k + per_job, pf_stride);
-                j.shape = shape | (multi ? n_multi++ << 8 : 0u);
-                jobs.push_back(j);
-                // stand-in for the cell count the host cannot see: query length x slots; the lists are sorted by
-                // target length on the device, so among equals a query's earlier jobs hold the longer targets
-                job_cells.push_back((uint64_t)Q.qlen * (j.hit_end - j.hit_begin) * 65536u + (pf_stride - k));
-            }
-            if (multi && mode >= MMGPU_SW_START)
-                add_rev_jobs(i, hit_cursor, pf_stride, shape, (uint64_t)Q.qlen * ((Q.qlen + c->mean_len) / 2 + 1));
-            max_tlen = c->db.max_len;
-            hit_cursor += pf_stride;
-            out_cursor += pf_stride;
-            b->h_qout_off[i + 1] = out_cursor;
-            continue;
-        }
-        // caller-supplied list: the sort by target length and the job cuts are done for all queries in parallel below
-        deferred.push_back(Deferred{i, hit_cursor, out_cursor, shape, round, multi});
-        hit_cursor += Q.n_targets;
-        out_cursor += Q.n_targets;
+        const uint32_t n_slots = pf ? pf_stride : Q.n_targets;
+        if (pf) add_slot_jobs(i, shape, round, multi);
+        // caller-supplied list: the sort by target length and the job cuts are done for all queries in parallel (cut_list_jobs)
+        else deferred.push_back(Deferred{i, hit_cursor, out_cursor, shape, round, multi});
+        hit_cursor += n_slots;
+        out_cursor += n_slots;
         b->h_qout_off[i + 1] = out_cursor;
     }
-    prep_lap("queries copied, buffers sized");
-    if (!deferred.empty()) {
-        // Per query: sort the prefilter list by target length (longest first) so the 8 targets a wave runs together end
-        // together, cut it into jobs.  3 M pairs of a 10 000-query block cost 0.2 s on one thread (the sort's comparisons
-        // read the length table at random) - the queries are independent, so threads take contiguous ranges of them; the jobs
-        // are concatenated in query order afterwards, so the result does not depend on the number of threads.
-        struct PerQuery { std::vector<SwJob> jobs; std::vector<uint64_t> cells; uint64_t sum_cells = 0; uint32_t max_tlen = 0; uint32_t rev_mid_len = 0; bool bad = false; };
-        std::vector<PerQuery> pq(deferred.size());
-        auto work = [&](size_t from, size_t to) {
-            std::vector<uint32_t> ord;
-            for (size_t d = from; d < to; d++) {
-                const Deferred &D = deferred[d];
-                const mmgpu_sw_query &Q = qs[D.query];
-                PerQuery &P = pq[d];
-                const bool same_list = d > from && Q.target_ids == qs[deferred[d - 1].query].target_ids && Q.n_targets == qs[deferred[d - 1].query].n_targets;
-                if (!same_list) {   // all-vs-all callers hand the same list to every query: sort it once (per thread)
-                    ord.resize(Q.n_targets);
-                    std::iota(ord.begin(), ord.end(), 0u);
-                    for (uint32_t k = 0; k < Q.n_targets; k++)
-                        if (Q.target_ids[k] >= c->db.n) { P.bad = true; break; }
-                    if (P.bad) continue;
-                    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t bb) {
-                        return c->h_len[Q.target_ids[a]] > c->h_len[Q.target_ids[bb]];
-                    });
-                }
-                for (uint32_t k = 0; k < Q.n_targets; k++) {
-                    const uint32_t t = Q.target_ids[ord[k]];
-                    hit_target[D.hit_cursor + k] = t;
-                    hit_out[D.hit_cursor + k] = D.out_cursor + ord[k];
-                    P.sum_cells += (uint64_t)Q.qlen * c->h_len[t];
-                    P.max_tlen = std::max(P.max_tlen, c->h_len[t]);
-                }
-                // Jobs: consecutive hits of the (length-sorted) list, cut at multiples of one workgroup round (32 targets)
-                // once a job holds JOB_CELLS forward cells, at the latest after JOB_HITS hits - a 5000-residue query against
-                // 300 long targets must not become one 7e9-cell workgroup.
-                for (uint32_t k = 0; k < Q.n_targets;) {
-                    uint64_t jc = 0;
-                    uint32_t e = k;
-                    while (e < Q.n_targets && e - k < JOB_HITS) {
-                        const uint32_t stop = std::min<uint32_t>(e + D.round, Q.n_targets);
-                        for (; e < stop; e++) jc += (uint64_t)Q.qlen * c->h_len[hit_target[D.hit_cursor + e]];
-                        // cut at 8, 16 (long queries) or whole workgroup rounds: no wave idles while another runs a second round
-                        const uint32_t held = e - k;
-                        if (jc >= JOB_CELLS && (held <= 16 || held % JOB_ROUND == 0)) break;
-                    }
-                    SwJob j;
-                    j.query = D.query;
-                    j.hit_begin = D.hit_cursor + k;
-                    j.hit_end = D.hit_cursor + e;
-                    j.shape = D.shape;      // (multi-tile jobs get their scratch slot number when the lists are joined)
-                    P.jobs.push_back(j);
-                    P.cells.push_back(jc);
-                    k = e;
-                }
-                if (Q.n_targets) P.rev_mid_len = c->h_len[hit_target[D.hit_cursor + Q.n_targets / 2]];
-                if (mode >= MMGPU_SW_START)
-                    for (uint32_t k = 0; k < Q.n_targets; k++) b->h_out_target[D.out_cursor + k] = Q.target_ids[k];
-            }
-        };
-        static const unsigned host_threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-        const size_t n_thr = std::max<size_t>(1, std::min<size_t>(host_threads, total_hits / 65536 + 1));
-        if (n_thr <= 1) {
-            work(0, deferred.size());
-        } else {
-            // ranges of about equal numbers of pairs
-            std::vector<std::thread> pool;
-            size_t from = 0;
-            uint64_t acc = 0;
-            const uint64_t share = total_hits / n_thr + 1;
-            for (size_t d = 0; d < deferred.size(); d++) {
-                acc += qs[deferred[d].query].n_targets;
-                if (acc >= share || d + 1 == deferred.size()) {
-                    pool.emplace_back(work, from, d + 1);
-                    from = d + 1;
-                    acc = 0;
-                }
-            }
-            for (std::thread &t : pool) t.join();
+    return MMGPU_OK;
+}
+
+// the caller's lists of deferred[from, to): sorted by target length (longest first) so the 8 targets a wave runs together end
+// together, and cut into jobs
+void SwPrepare::cut_list_jobs_of(size_t from, size_t to) {
+    std::vector<uint32_t> ord;
+    for (size_t d = from; d < to; d++) {
+        const Deferred &D = deferred[d];
+        const mmgpu_sw_query &Q = qs[D.query];
+        PerQuery &P = per_query[d];
+        const bool same_list = d > from && Q.target_ids == qs[deferred[d - 1].query].target_ids && Q.n_targets == qs[deferred[d - 1].query].n_targets;
+        if (!same_list) {   // all-vs-all callers hand the same list to every query: sort it once (per thread)
+            ord.resize(Q.n_targets);
+            std::iota(ord.begin(), ord.end(), 0u);
+            for (uint32_t k = 0; k < Q.n_targets; k++)
+                if (Q.target_ids[k] >= c->db.n) { P.bad = true; break; }
+            if (P.bad) continue;
+            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t bb) {
+                return c->h_len[Q.target_ids[a]] > c->h_len[Q.target_ids[bb]];
+            });
         }
-        prep_lap("lists sorted by target length, jobs cut (threads)");
-        for (size_t d = 0; d < deferred.size(); d++) {
-            const Deferred &D = deferred[d];
-            PerQuery &P = pq[d];
-            if (P.bad) { delete b; return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: target id out of range"); }
-            b->cells += P.sum_cells;
-            max_tlen = std::max(max_tlen, P.max_tlen);
-            for (size_t z = 0; z < P.jobs.size(); z++) {
-                SwJob j = P.jobs[z];
-                if (D.multi) j.shape |= n_multi++ << 8;
-                jobs.push_back(j);
-                job_cells.push_back(P.cells[z]);
+        for (uint32_t k = 0; k < Q.n_targets; k++) {
+            const uint32_t t = Q.target_ids[ord[k]];
+            hit_target[D.hit_cursor + k] = t;
+            hit_out[D.hit_cursor + k] = D.out_cursor + ord[k];
+            P.sum_cells += (uint64_t)Q.qlen * c->h_len[t];
+            P.max_tlen = std::max(P.max_tlen, c->h_len[t]);
+        }
+        // Jobs: consecutive hits of the (length-sorted) list, cut at multiples of one workgroup round (32 targets)
+        // once a job holds JOB_CELLS forward cells, at the latest after JOB_HITS hits - a 5000-residue query against
+        // 300 long targets must not become one 7e9-cell workgroup.
+        for (uint32_t k = 0; k < Q.n_targets;) {
+            uint64_t jc = 0;
+            uint32_t e = k;
+            while (e < Q.n_targets && e - k < JOB_HITS) {
+                const uint32_t stop = std::min<uint32_t>(e + D.round, Q.n_targets);
+                for (; e < stop; e++) jc += (uint64_t)Q.qlen * c->h_len[hit_target[D.hit_cursor + e]];
+                // cut at 8, 16 (long queries) or whole workgroup rounds: no wave idles while another runs a second round
+                const uint32_t held = e - k;
+                if (jc >= JOB_CELLS && (held <= 16 || held % JOB_ROUND == 0)) break;
             }
-            const uint32_t n_t = qs[D.query].n_targets;
-            if (D.multi && mode >= MMGPU_SW_START && n_t)
-                add_rev_jobs(D.query, D.hit_cursor, n_t, D.shape, (uint64_t)qs[D.query].qlen * (P.rev_mid_len + 1));
+            SwJob j;
+            j.query = D.query;
+            j.hit_begin = D.hit_cursor + k;
+            j.hit_end = D.hit_cursor + e;
+            j.shape = D.shape;      // (multi-tile jobs get their scratch slot number when the lists are joined)
+            P.jobs.push_back(j);
+            P.cells.push_back(jc);
+            k = e;
+        }
+        if (Q.n_targets) P.rev_mid_len = c->h_len[hit_target[D.hit_cursor + Q.n_targets / 2]];
+        if (mode >= MMGPU_SW_START)
+            for (uint32_t k = 0; k < Q.n_targets; k++) b->h_out_target[D.out_cursor + k] = Q.target_ids[k];
+    }
+}
+
+// 3 M pairs of a 10 000-query block cost 0.2 s on one thread (the sort's comparisons read the length table at random) - the queries
+// are independent, so threads take contiguous ranges of them; the jobs are concatenated in query order afterwards
+// (join_list_jobs), so the result does not depend on the number of threads.
+void SwPrepare::cut_list_jobs() {
+    per_query.resize(deferred.size());
+    static const unsigned host_threads = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    const size_t n_thr = std::max<size_t>(1, std::min<size_t>(host_threads, total_hits / 65536 + 1));
+    if (n_thr <= 1) {
+        cut_list_jobs_of(0, deferred.size());
+        return;
+    }
+    // ranges of about equal numbers of pairs
+    std::vector<std::thread> pool;
+    size_t from = 0;
+    uint64_t acc = 0;
+    const uint64_t share = total_hits / n_thr + 1;
+    for (size_t d = 0; d < deferred.size(); d++) {
+        acc += qs[deferred[d].query].n_targets;
+        if (acc >= share || d + 1 == deferred.size()) {
+            pool.emplace_back(&SwPrepare::cut_list_jobs_of, this, from, d + 1);
+            from = d + 1;
+            acc = 0;
         }
     }
-    prep_lap("jobs joined");
+    for (std::thread &t : pool) t.join();
+}
+
+int SwPrepare::join_list_jobs() {
+    for (size_t d = 0; d < deferred.size(); d++) {
+        const Deferred &D = deferred[d];
+        PerQuery &P = per_query[d];
+        if (P.bad) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: target id out of range");
+        b->cells += P.sum_cells;
+        max_tlen = std::max(max_tlen, P.max_tlen);
+        for (size_t z = 0; z < P.jobs.size(); z++) {
+            SwJob j = P.jobs[z];
+            if (D.multi) j.shape |= n_multi++ << 8;
+            jobs.push_back(j);
+            job_cells.push_back(P.cells[z]);
+        }
+        const uint32_t n_t = qs[D.query].n_targets;
+        if (D.multi && mode >= MMGPU_SW_START && n_t)
+            add_rev_jobs(D.query, D.hit_cursor, n_t, D.shape, (uint64_t)qs[D.query].qlen * (P.rev_mid_len + 1));
+    }
+    return MMGPU_OK;
+}
+
+// `sorted` = the forward jobs by kernel group, longest job first inside a group (the dispatcher hands out workgroups in blockIdx
+// order, so the tail is the shortest jobs), then the reverse-scan jobs, longest first
+void SwPrepare::order_jobs() {
+    sorted.resize(jobs.size());
+    std::vector<uint32_t> ord(jobs.size());
+    std::iota(ord.begin(), ord.end(), 0u);
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t bb) {
+        const int ga = sw_shape_group(jobs[a].shape & 0xFFu), gb = sw_shape_group(jobs[bb].shape & 0xFFu);
+        return ga != gb ? ga < gb : job_cells[a] > job_cells[bb];
+    });
+    for (size_t z = 0; z < ord.size(); z++) {
+        sorted[z] = jobs[ord[z]];
+        b->group_begin[sw_shape_group(sorted[z].shape & 0xFFu) + 1]++;
+    }
+    for (int g = 0; g < SW_GROUPS; g++) b->group_begin[g + 1] += b->group_begin[g];
+    b->n_jobs = (uint32_t)sorted.size();
+    b->n_multi_jobs = n_multi;
+    std::vector<uint32_t> ro(rev_jobs.size());
+    std::iota(ro.begin(), ro.end(), 0u);
+    std::stable_sort(ro.begin(), ro.end(), [&](uint32_t a, uint32_t bb) { return rev_cells[a] > rev_cells[bb]; });
+    for (uint32_t z : ro) sorted.push_back(rev_jobs[z]);
+    b->n_rev_jobs = (uint32_t)rev_jobs.size();
+}
+
+int SwPrepare::enqueue_uploads() {
     b->pairs = total_hits;
     b->h_qoff = qoff;
     b->from_pf = pf != nullptr;
     b->pf_stride = pf_stride;
     b->slot_stride = pf_stride;
-
     hipStream_t s = c->stream;
-    std::vector<int8_t> mat(par->mat, par->mat + par->alphabet * par->alphabet);
-#define B_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { delete b; return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
-    // the fused hand-over (pf): the stream still holds the prefilter batch - the uploads go through pinned staging so that this
+    mat.assign(par->mat, par->mat + par->alphabet * par->alphabet);
+    // lists on the device (pf): the stream still holds the prefilter batch - the uploads go through pinned staging so that this
     // thread is not parked behind it (mmgpu_ctx::pinned); sized here, once, for everything uploaded below
     void *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0;
     if (pf) {
-        size_t need = upload_pinned_need(qres.size()) + upload_pinned_need(qcb.size()) + upload_pinned_need(qoff.size() * 4) +
-                      upload_pinned_need(qbias.size() * 4) + upload_pinned_need(qminstart.size() * 4) + upload_pinned_need(mat.size()) +
-                      upload_pinned_need((jobs.size() + rev_jobs.size()) * sizeof(SwJob)) + upload_pinned_need(qprof.size()) +
-                      upload_pinned_need(qprof_off.size() * 4);
-        if (need > c->pinned_cap) {      // (nothing of an earlier batch is in flight from it: every prepare ends with the stream drained)
-            if (c->pinned) (void)hipHostFree(c->pinned);
-            c->pinned = nullptr;
-            c->pinned_cap = 0;
-            if (hipHostMalloc(&c->pinned, need + need / 4, hipHostMallocDefault) == hipSuccess) c->pinned_cap = need + need / 4;
-            else (void)hipGetLastError();   // pageable copies then
-        }
-        pin = c->pinned;
-        pin_cap = c->pinned_cap;
+        pin_cap = upload_pinned_need(qres.size()) + upload_pinned_need(qcb.size()) + upload_pinned_need(qoff.size() * 4) +
+                  upload_pinned_need(qbias.size() * 4) + upload_pinned_need(qminstart.size() * 4) + upload_pinned_need(mat.size()) +
+                  upload_pinned_need((jobs.size() + rev_jobs.size()) * sizeof(SwJob)) + upload_pinned_need(qprof.size()) +
+                  upload_pinned_need(qprof_off.size() * 4);
+        pin = pinned.acquire(c, pin_cap);      // (nothing of an earlier batch is in flight from it: every prepare ends with the stream drained)
     }
-#define UPLOAD(buf, vec) upload_pinned(buf, vec, s, pin, pin_cap, pin_used)
-    B_TRY(UPLOAD(b->d_qres, qres));
-    B_TRY(UPLOAD(b->d_qcb, qcb));
-    B_TRY(UPLOAD(b->d_qoff, qoff));
-    B_TRY(UPLOAD(b->d_qbias, qbias));
-    B_TRY(UPLOAD(b->d_qminstart, qminstart));
+    auto up = [&](DevBuf &buf, const auto &vec) { return upload_pinned(buf, vec, s, pin, pin_cap, pin_used); };
+    HIP_TRY(up(b->d_qres, qres));
+    HIP_TRY(up(b->d_qcb, qcb));
+    HIP_TRY(up(b->d_qoff, qoff));
+    HIP_TRY(up(b->d_qbias, qbias));
+    HIP_TRY(up(b->d_qminstart, qminstart));
     if (b->any_profile) {
-        B_TRY(UPLOAD(b->d_qprof, qprof));
-        B_TRY(UPLOAD(b->d_qprof_off, qprof_off));
+        HIP_TRY(up(b->d_qprof, qprof));
+        HIP_TRY(up(b->d_qprof_off, qprof_off));
     }
     if (pf) {
-        B_TRY(b->d_hit_target.alloc(std::max<size_t>((size_t)total_hits, 1) * 4));
-        B_TRY(b->d_hit_out.alloc(std::max<size_t>((size_t)total_hits, 1) * 4));
-        B_TRY(b->d_stats.alloc(SW_FROM_PF_STAT_SLOTS * 24));      // (cells, pairs, longest target) x slots: sw_from_pf_kernel
-        B_TRY(hipMemsetAsync(b->d_stats.p, 0, SW_FROM_PF_STAT_SLOTS * 24, s));
-        B_TRY(b->d_pf_counts.alloc(std::max<size_t>(nq, 1) * 4));
-        B_TRY(b->d_slot_target.alloc(std::max<size_t>((size_t)total_hits, 1) * 4));
+        HIP_TRY(b->d_hit_target.alloc(std::max<size_t>((size_t)total_hits, 1) * 4));
+        HIP_TRY(b->d_hit_out.alloc(std::max<size_t>((size_t)total_hits, 1) * 4));
+        HIP_TRY(b->d_stats.alloc(SW_FROM_PF_STAT_SLOTS * 24));      // (cells, pairs, longest target) x slots: sw_from_pf_kernel
+        HIP_TRY(hipMemsetAsync(b->d_stats.p, 0, SW_FROM_PF_STAT_SLOTS * 24, s));
+        HIP_TRY(b->d_pf_counts.alloc(std::max<size_t>(nq, 1) * 4));
+        HIP_TRY(b->d_slot_target.alloc(std::max<size_t>((size_t)total_hits, 1) * 4));
     } else {
-        B_TRY(upload(b->d_hit_target, hit_target, s));
-        B_TRY(upload(b->d_hit_out, hit_out, s));
+        HIP_TRY(upload(b->d_hit_target, hit_target, s));
+        HIP_TRY(upload(b->d_hit_out, hit_out, s));
     }
-    B_TRY(UPLOAD(b->d_mat, mat));
-    B_TRY(b->d_out.alloc(std::max<size_t>((size_t)total_hits, 1) * sizeof(mmgpu_sw_hit)));
-    std::vector<SwJob> sorted(jobs.size());   // uploaded asynchronously: must live until the stream is drained below
-    {
-        // longest job first: the dispatcher hands out workgroups in blockIdx order, so the tail is the shortest jobs
-        std::vector<uint32_t> ord(jobs.size());
-        std::iota(ord.begin(), ord.end(), 0u);
-        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t bb) {
-            const int ga = sw_shape_group(jobs[a].shape & 0xFFu), gb = sw_shape_group(jobs[bb].shape & 0xFFu);
-            return ga != gb ? ga < gb : job_cells[a] > job_cells[bb];
-        });
-        for (size_t z = 0; z < ord.size(); z++) {
-            sorted[z] = jobs[ord[z]];
-            b->group_begin[sw_shape_group(sorted[z].shape & 0xFFu) + 1]++;
-        }
-        for (int g = 0; g < SW_GROUPS; g++) b->group_begin[g + 1] += b->group_begin[g];
-        b->n_jobs = (uint32_t)sorted.size();
-        b->n_multi_jobs = n_multi;
-        {
-            std::vector<uint32_t> ro(rev_jobs.size());
-            std::iota(ro.begin(), ro.end(), 0u);
-            std::stable_sort(ro.begin(), ro.end(), [&](uint32_t a, uint32_t bb) { return rev_cells[a] > rev_cells[bb]; });
-            for (uint32_t z : ro) sorted.push_back(rev_jobs[z]);
-            b->n_rev_jobs = (uint32_t)rev_jobs.size();
-        }
-        B_TRY(UPLOAD(b->d_jobs, sorted));
+    HIP_TRY(up(b->d_mat, mat));
+    HIP_TRY(b->d_out.alloc(std::max<size_t>((size_t)total_hits, 1) * sizeof(mmgpu_sw_hit)));
+    order_jobs();
+    HIP_TRY(up(b->d_jobs, sorted));
+    return MMGPU_OK;
+}
+
+// column scratch of the multi-tile jobs: a pool with one slot per workgroup that can be resident at once (not one
+// per job: a batch of long queries against one very long target would ask for 100+ GB), sized by the longest
+// target any list holds
+hipError_t SwPrepare::alloc_scratch(uint32_t longest) {
+    b->scratch_cols = longest + 16;
+    b->scratch_slots = std::min<uint32_t>(std::max<uint32_t>(std::max<uint32_t>(n_multi, (uint32_t)rev_jobs.size()), 1),
+                                          sw_multi_resident_blocks(b->group_lds[SW_GROUPS - 1], mode >= MMGPU_SW_START, c->compute_units));
+    hipError_t e = b->d_scratch.alloc((size_t)b->scratch_slots * 4 * 4 * 2 * (size_t)b->scratch_cols * sizeof(uint2));
+    if (e != hipSuccess) return e;
+    e = b->d_scratch_busy.alloc((size_t)b->scratch_slots * 4);
+    if (e != hipSuccess) return e;
+    return hipMemsetAsync(b->d_scratch_busy.p, 0, (size_t)b->scratch_slots * 4, c->stream);
+}
+
+int SwPrepare::finish_host_lists() {
+    if (any_multi) HIP_TRY(alloc_scratch(max_tlen));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the host vectors of this call die with it
+    return MMGPU_OK;
+}
+
+// sw_from_pf_kernel orders every list by target length and counts cells, pairs and the longest target, which sizes the scratch
+int SwPrepare::order_device_lists() {
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemsetAsync(b->d_out.p, 0, std::max<size_t>((size_t)total_hits, 1) * sizeof(mmgpu_sw_hit), s));
+    SwFromPfArgs F;
+    F.pf_hits = pf->hits;
+    F.pf_stride = pf_stride;
+    F.hit_count = pf->counts;
+    F.stride = pf_stride;
+    F.q_off = b->d_qoff.as<uint32_t>();
+    F.t_len = c->db.len;
+    F.hit_target = b->d_hit_target.as<uint32_t>();
+    F.hit_out = b->d_hit_out.as<uint32_t>();
+    F.cells = b->d_stats.as<unsigned long long>();
+    F.pairs = b->d_stats.as<unsigned long long>() + 1;
+    F.count_copy = b->d_pf_counts.as<uint32_t>();
+    F.slot_target = b->d_slot_target.as<uint32_t>();
+    HIP_TRY(launch_sw_from_pf(F, nq, s));
+    HIP_TRY(hipStreamSynchronize(s));   // the host vectors of this call die with it
+    unsigned long long st[3] = {0, 0, 0}, slots[SW_FROM_PF_STAT_SLOTS * 3];
+    HIP_TRY(hipMemcpy(slots, b->d_stats.p, sizeof(slots), hipMemcpyDeviceToHost));
+    for (int z = 0; z < SW_FROM_PF_STAT_SLOTS; z++) {
+        st[0] += slots[z * 3];
+        st[1] += slots[z * 3 + 1];
+        st[2] = std::max(st[2], slots[z * 3 + 2]);
     }
-#undef UPLOAD
-    prep_lap("uploads enqueued, jobs ordered");
-    // column scratch of the multi-tile jobs: a pool with one slot per workgroup that can be resident at once (not one
-    // per job: a batch of long queries against one very long target would ask for 100+ GB), sized by the longest
-    // target any list holds
-    auto alloc_scratch = [&](uint32_t longest) -> hipError_t {
-        b->scratch_cols = longest + 16;
-        b->scratch_slots = std::min<uint32_t>(std::max<uint32_t>(std::max<uint32_t>(n_multi, (uint32_t)rev_jobs.size()), 1),
-                                              sw_multi_resident_blocks(b->group_lds[SW_GROUPS - 1], mode >= MMGPU_SW_START, c->compute_units));
-        hipError_t e = b->d_scratch.alloc((size_t)b->scratch_slots * 4 * 4 * 2 * (size_t)b->scratch_cols * sizeof(uint2));
-        if (e != hipSuccess) return e;
-        e = b->d_scratch_busy.alloc((size_t)b->scratch_slots * 4);
-        if (e != hipSuccess) return e;
-        return hipMemsetAsync(b->d_scratch_busy.p, 0, (size_t)b->scratch_slots * 4, s);
-    };
-    if (any_multi && !pf) B_TRY(alloc_scratch(max_tlen));
-    if (pf) {
-        B_TRY(hipMemsetAsync(b->d_out.p, 0, std::max<size_t>((size_t)total_hits, 1) * sizeof(mmgpu_sw_hit), s));
-        SwFromPfArgs F;
-        F.pf_hits = pf_hits;
-        F.pf_stride = pf_stride;
-        F.hit_count = pf_counts;
-        F.stride = pf_stride;
-        F.q_off = b->d_qoff.as<uint32_t>();
-        F.t_len = c->db.len;
-        F.hit_target = b->d_hit_target.as<uint32_t>();
-        F.hit_out = b->d_hit_out.as<uint32_t>();
-        F.cells = b->d_stats.as<unsigned long long>();
-        F.pairs = b->d_stats.as<unsigned long long>() + 1;
-        F.count_copy = b->d_pf_counts.as<uint32_t>();
-        F.slot_target = b->d_slot_target.as<uint32_t>();
-        B_TRY(launch_sw_from_pf(F, nq, s));
+    b->cells = st[0];
+    b->valid_pairs = st[1];
+    if (any_multi) {
+        HIP_TRY(alloc_scratch((uint32_t)st[2]));
+        HIP_TRY(hipStreamSynchronize(s));
     }
-    B_TRY(hipStreamSynchronize(s));   // the host vectors above die with this scope
-    if (pf) {
-        unsigned long long st[3] = {0, 0, 0}, slots[SW_FROM_PF_STAT_SLOTS * 3];
-        B_TRY(hipMemcpy(slots, b->d_stats.p, sizeof(slots), hipMemcpyDeviceToHost));
-        for (int z = 0; z < SW_FROM_PF_STAT_SLOTS; z++) {
-            st[0] += slots[z * 3];
-            st[1] += slots[z * 3 + 1];
-            st[2] = std::max(st[2], slots[z * 3 + 2]);
-        }
-        b->cells = st[0];
-        b->valid_pairs = st[1];
-        if (any_multi) {
-            B_TRY(alloc_scratch((uint32_t)st[2]));
-            B_TRY(hipStreamSynchronize(s));
-        }
+    return MMGPU_OK;
+}
+
+}  // namespace
+
+static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, int mode,
+                           const DeviceLists *pf, mmgpu_sw_batch_t **out) {
+    if (!c || !par || !out || (!qs && nq)) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: NULL argument");
+    SwPrepare S{c, par, qs, nq, mode, pf};
+    if (int e = S.check_params()) return e;
+    HIP_TRY(hipSetDevice(c->device));
+    std::unique_ptr<mmgpu_sw_batch_t, SwBatchFree> b(new mmgpu_sw_batch_t(), SwBatchFree{c});
+    S.b = b.get();
+    S.new_batch();
+    if (int e = S.size_buffers()) return e;
+    if (int e = S.copy_queries()) return e;
+    S.lap("queries copied, buffers sized");
+    if (!S.deferred.empty()) {
+        S.cut_list_jobs();
+        S.lap("lists sorted by target length, jobs cut (threads)");
+        if (int e = S.join_list_jobs()) return e;
     }
-#undef B_TRY
-    prep_lap("scratch + stream drained");
-    *out = b;
+    S.lap("jobs joined");
+    if (int e = S.enqueue_uploads()) return e;
+    S.lap("uploads enqueued, jobs ordered");
+    if (int e = pf ? S.order_device_lists() : S.finish_host_lists()) return e;
+    S.lap("scratch + stream drained");
+    *out = b.release();
     return MMGPU_OK;
 }
 
@@ -1350,6 +1461,7 @@ static int block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pa
     DevBuf d_out, d_sel_jobs, d_sel_pairs, d_sel_cnt, d_flags;
     for (DevBuf *d : {&d_out, &d_sel_jobs, &d_sel_pairs, &d_sel_cnt, &d_flags}) d->bind(c->cache);
     std::vector<mmgpu_sw_block> out_auto;
+    PinnedLease pinned;      // the context's staging arena, held to the end of the call (`out` may point into it)
     if (au) {
         // ---- the device picks the pairs (block_select.hip): int16-range hits that pass the query's start-score threshold ----
         if (!b->d_qout_off.p) {
@@ -1390,23 +1502,18 @@ static int block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pa
         HIP_TRY(launch_block_select(A, s));
         jobs.resize(n);
         // the selected jobs come back once and all n answers after every launch (block4_collect): through pinned memory where the
-        // context's staging area can be had (mmgpu_ctx::pinned; nothing else uses it between a batch's preparation and its free) -
+        // context's staging arena can be had for the length of this call (mmgpu_ctx::pinned; a thread preparing the next batch of
+        // the context meanwhile then uploads from pageable memory, as this call copies to it when that thread holds the arena) -
         // the copies of pageable memory were ~5 ms of a 45 ms call
         const size_t out_bytes = (size_t)n * sizeof(mmgpu_sw_block), jobs_bytes = (size_t)n * sizeof(BlockJob);
         const size_t pin_need = upload_pinned_need(out_bytes) + upload_pinned_need(jobs_bytes);
-        if (pin_need > c->pinned_cap) {
-            if (c->pinned) (void)hipHostFree(c->pinned);
-            c->pinned = nullptr;
-            c->pinned_cap = 0;
-            if (hipHostMalloc(&c->pinned, pin_need + pin_need / 4, hipHostMallocDefault) == hipSuccess) c->pinned_cap = pin_need + pin_need / 4;
-            else (void)hipGetLastError();
-        }
-        if (c->pinned_cap >= pin_need) {
-            BlockJob *pj = reinterpret_cast<BlockJob *>(static_cast<char *>(c->pinned) + upload_pinned_need(out_bytes));
+        void *pin = pinned.acquire(c, pin_need);
+        if (pin) {
+            BlockJob *pj = reinterpret_cast<BlockJob *>(static_cast<char *>(pin) + upload_pinned_need(out_bytes));
             HIP_TRY(hipMemcpyAsync(pj, d_sel_jobs.p, jobs_bytes, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             memcpy(jobs.data(), pj, jobs_bytes);
-            out = static_cast<mmgpu_sw_block *>(c->pinned);
+            out = static_cast<mmgpu_sw_block *>(pin);
         } else {
             HIP_TRY(hipMemcpyAsync(jobs.data(), d_sel_jobs.p, jobs_bytes, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -1791,6 +1898,7 @@ static int block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pa
     lap("backtrace strings download");
     return MMGPU_OK;
 }
+
 
 // One call = what `mmseqs search` needs of the block aligner in alignment mode 2 without backtraces: the device picks every int16-range
 // hit that passes its query's start-score threshold, runs the block aligner for start positions only, writes them into the batch's

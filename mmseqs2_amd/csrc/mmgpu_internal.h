@@ -830,9 +830,13 @@ struct mmgpu_ctx {
     hipEvent_t fork = nullptr, join[4] = {};
     // pinned staging for the uploads of mmgpu_sw_prepare_from_pf: a copy from pageable memory blocks the calling thread until the
     // stream has reached it - i.e. until the prefilter batch before it has finished - and everything the host still had to do for
-    // the alignment batch (ordering ~1e5 jobs) then ran with the device idle
+    // the alignment batch (ordering ~1e5 jobs) then ran with the device idle.  mmgpu_sw_block_starts receives its jobs and answers
+    // through it.  Threading rule: one call at a time owns the arena, from PinnedLease::acquire (mmgpu_api.hip) - the only place that
+    // grows, i.e. frees and reallocates, it - until the holder dies; a call that finds it taken (pinned_busy: a thread prepares the
+    // next batch while another runs the block aligner on this one) uses pageable memory
     void *pinned = nullptr;
-    size_t pinned_cap = 0, pinned_used = 0;
+    size_t pinned_cap = 0;
+    std::atomic<bool> pinned_busy{false};
 };
 
 // device memory for a context's long-lived buffers (targets, masked view): when the runtime is out of memory the blocks the

@@ -43,6 +43,24 @@ struct PfIndex {
     const void *w_owner = nullptr;   // batch whose last run the working buffers hold (debug fetch)
 };
 
+// The environment's test hooks of the prefilter, read in this one place, once per call that uses them (they are not part of
+// mmgpu_pf_params: that is the ABI and the server's wire format)
+struct PfEnv {
+    bool has_max_db_matches = false, has_sort_cap = false, has_stage_gb = false;
+    uint64_t max_db_matches = 0;   // MMGPU_PF_MAX_DB_MATCHES (at least 64): a small database reaches the overflow path / a shard its share
+    uint64_t sort_cap = 0;         // MMGPU_PF_SORT_CAP: a small database reaches the select kernel's candidate cap
+    double stage_gb = 0;           // MMGPU_PF_STAGE_GB: budget of the candidate + survivor arrays of a stage chunk
+    bool cofs_off = false;         // MMGPU_PF_COFS=0: the similar-k-mer kernels look lists up in the full offset table (A/B runs)
+};
+inline PfEnv pf_env() {
+    PfEnv E;
+    if (const char *e = getenv("MMGPU_PF_MAX_DB_MATCHES")) { E.has_max_db_matches = true; E.max_db_matches = std::max<uint64_t>(64, strtoull(e, nullptr, 10)); }
+    if (const char *e = getenv("MMGPU_PF_SORT_CAP")) { E.has_sort_cap = true; E.sort_cap = strtoull(e, nullptr, 10); }
+    if (const char *e = getenv("MMGPU_PF_STAGE_GB")) { E.has_stage_gb = true; E.stage_gb = atof(e); }
+    if (const char *e = getenv("MMGPU_PF_COFS")) E.cofs_off = e[0] == '0';
+    return E;
+}
+
 // Sparse indexes (a shard of a multi-GPU run holds 1/N of the entries over the same k-mer space; small databases): most similar
 // k-mers of a query have no list.  The bit table is consulted by pf_kmers_kernel when fewer than 60 % of the k-mers have one
 // similar-k-mer searches with k = 6 only (the table of k = 7 has 1.3e9 k-mers).
@@ -69,8 +87,7 @@ static hipError_t pf_index_bitmap(mmgpu_ctx *c, PfIndex *P) {
 // look-up per window does not pay for it).  MMGPU_PF_COFS=0 keeps the look-ups on the full table (A/B runs).
 static hipError_t pf_index_cofs(mmgpu_ctx *c, PfIndex *P) {
     P->use_cofs = false;
-    const char *e = getenv("MMGPU_PF_COFS");
-    if (!P->has_tables || P->n_entries >= (1ull << 31) || P->table > (1ull << 31) || (e && e[0] == '0')) return hipSuccess;
+    if (!P->has_tables || P->n_entries >= (1ull << 31) || P->table > (1ull << 31) || pf_env().cofs_off) return hipSuccess;
     hipError_t rc = P->d_cofs.alloc(pf_cofs_bytes(P->table));
     if (rc == hipSuccess) rc = launch_pf_cofs(P->d_offsets.as<uint32_t>(), P->table, P->d_cofs.p, c->stream);
     if (rc == hipSuccess) P->use_cofs = true;
@@ -586,6 +603,14 @@ static uint32_t reference_bins(uint64_t dbsize) {
     return 2048;
 }
 
+// a batch under preparation: freed (with its buffers and events) unless the preparation hands it to the caller
+namespace {
+struct PfBatchFree {
+    mmgpu_ctx *c;
+    void operator()(mmgpu_pf_batch_t *b) const { mmgpu_pf_free(c, b); }
+};
+}  // namespace
+
 extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const mmgpu_pf_query *qs, uint32_t nq,
                                 mmgpu_pf_batch_t **out) {
     if (!c || !par || !out || (!qs && nq)) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: NULL argument");
@@ -617,7 +642,8 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
 
     if (c->pf && c->pf->kbase != c->pf->kalph && !par->exact_kmer)
         return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: an index over the full alphabet (profile targets) serves exact k-mer matching only");
-    mmgpu_pf_batch_t *b = new mmgpu_pf_batch_t();
+    std::unique_ptr<mmgpu_pf_batch_t, PfBatchFree> owner(new mmgpu_pf_batch_t(), PfBatchFree{c});
+    mmgpu_pf_batch_t *b = owner.get();
     // the batch's buffers come from / go back to the context's block cache: a process prepares batch after batch (and, like the
     // drop-in's prefilter hook, the next one while this one runs), a fresh hipMalloc costs 25 - 40 ms per GB on some hosts
     for (DevBuf *d : {&b->d_qres, &b->d_qthr, &b->d_qcorr, &b->d_qoff, &b->d_qident, &b->d_qself, &b->d_qkind, &b->d_qisprof, &b->d_pscore,
@@ -636,7 +662,7 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
     b->ref_bins = par->ref_bins ? par->ref_bins : reference_bins(db_size);
     b->exchange = exchange;
     b->max_db_matches = std::max<uint64_t>(1000000, db_size) * 2;   // QueryMatcher.cpp:44-45 (dbSize of the WHOLE database)
-    if (const char *e = getenv("MMGPU_PF_MAX_DB_MATCHES")) b->max_db_matches = std::max<uint64_t>(64, strtoull(e, nullptr, 10));      // tests: a small database reaches the overflow path / a shard its share
+    if (pf_env().has_max_db_matches) b->max_db_matches = pf_env().max_db_matches;      // tests: a small database reaches the overflow path / a shard its share
     // a shard gathers its share of a query's index entries: the unsplit run's overflow path (QueryMatcher.cpp:310-346) is taken
     // when the shares add up to max_db_matches.  If NO shard reaches max_db_matches / n_shards the sum stays below the limit:
     // a shard that reaches its share flags the query (bit 31 of its exchanged count -> MMGPU_PF_X_INEXACT_ORDER in the merge,
@@ -645,10 +671,10 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
     b->q_off.assign(nq + 1, 0);
     uint64_t tot = 0;
     for (uint32_t i = 0; i < nq; i++) {
-        if (!qs[i].q || qs[i].qlen == 0) { delete b; return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: bad query"); }
-        if (qs[i].qlen > 65535) { delete b; return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: query longer than 65535 (Parameters.h:271)"); }
+        if (!qs[i].q || qs[i].qlen == 0) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: bad query");
+        if (qs[i].qlen > 65535) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: query longer than 65535 (Parameters.h:271)");
         tot += qs[i].qlen;
-        if (tot > 0x7FFFFFFFull) { delete b; return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: more than 2^31 query residues per batch"); }
+        if (tot > 0x7FFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: more than 2^31 query residues per batch");
         b->q_off[i + 1] = (uint32_t)tot;
     }
     b->n_pos = (uint32_t)tot;
@@ -673,11 +699,9 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
     bool any_prof = false;
     for (uint32_t i = 0; i < nq; i++) {
         if (!qs[i].profile_score && !qs[i].profile_index && !qs[i].profile) continue;
-        if (!qs[i].profile_score || !qs[i].profile_index || !qs[i].profile || qs[i].profile_row < (uint32_t)PF_PROF_LETTERS) {
-            delete b;
+        if (!qs[i].profile_score || !qs[i].profile_index || !qs[i].profile || qs[i].profile_row < (uint32_t)PF_PROF_LETTERS)
             return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: a profile query needs profile_score, profile_index (row >= 20) and profile");
-        }
-        if (P.kalph != PF_PROF_LETTERS) { delete b; return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: profile queries need the 20-letter k-mer alphabet"); }
+        if (P.kalph != PF_PROF_LETTERS) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: profile queries need the 20-letter k-mer alphabet");
         any_prof = true;
     }
     std::vector<uint8_t> qkind, qisprof, pletter;
@@ -750,78 +774,93 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
             qself[i] = mx;
         }
     });
-    if (bad) { delete b; return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: query residue code >= alphabet"); }
+    if (bad) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: query residue code >= alphabet");
     hipStream_t s = c->stream;
-#define B_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { delete b; return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
-    B_TRY(upload(b->d_qres, qres, s));
-    B_TRY(upload(b->d_qthr, qthr, s));
-    B_TRY(upload(b->d_qcorr, qcorr, s));
-    B_TRY(upload(b->d_qoff, b->q_off, s));
-    B_TRY(upload(b->d_qident, qident, s));
-    B_TRY(upload(b->d_qself, qself, s));
+    HIP_TRY(upload(b->d_qres, qres, s));
+    HIP_TRY(upload(b->d_qthr, qthr, s));
+    HIP_TRY(upload(b->d_qcorr, qcorr, s));
+    HIP_TRY(upload(b->d_qoff, b->q_off, s));
+    HIP_TRY(upload(b->d_qident, qident, s));
+    HIP_TRY(upload(b->d_qself, qself, s));
     if (any_prof) {
-        B_TRY(upload(b->d_qkind, qkind, s));
-        B_TRY(upload(b->d_qisprof, qisprof, s));
-        B_TRY(upload(b->d_pscore, pscore, s));
-        B_TRY(upload(b->d_pletter, pletter, s));
-        B_TRY(upload(b->d_qrows, qrows, s));
+        HIP_TRY(upload(b->d_qkind, qkind, s));
+        HIP_TRY(upload(b->d_qisprof, qisprof, s));
+        HIP_TRY(upload(b->d_pscore, pscore, s));
+        HIP_TRY(upload(b->d_pletter, pletter, s));
+        HIP_TRY(upload(b->d_qrows, qrows, s));
     }
     const size_t np = std::max<size_t>(tot, 1), nqq = std::max<uint32_t>(nq, 1);
-    B_TRY(b->d_nsim.alloc(np * 4));
-    B_TRY(b->d_list_base.alloc((np + 1) * 4));
-    B_TRY(b->d_pos_entries.alloc(np * 4));
-    B_TRY(b->d_peb.alloc((np + 1) * 4));
-    B_TRY(b->d_qtot.alloc(nqq * 8));
-    B_TRY(b->d_qbase.alloc(nqq * 8));
-    B_TRY(b->d_qentries.alloc(nqq * 4));
-    B_TRY(b->d_qtile_base.alloc(nqq * 4));
-    B_TRY(b->d_qntiles.alloc(nqq * 4));
-    B_TRY(b->d_bucket_count.alloc((size_t)nqq * bins * 4));
-    B_TRY(b->d_bucket_off.alloc(((size_t)nqq + 1) * 4));
-    B_TRY(b->d_cand_base.alloc(((size_t)nqq * bins + 1) * 4));
-    B_TRY(b->d_cand_count.alloc((size_t)nqq * bins * 4));
-    B_TRY(b->d_cand_small.alloc((size_t)nqq * bins * PF_CAND0 * sizeof(PfCand)));
-    B_TRY(b->d_cells.alloc((size_t)nqq * 8));
-    B_TRY(b->d_surv_count.alloc(nqq * 4));
-    B_TRY(b->d_hits.alloc((size_t)nqq * max_hits * (exchange ? sizeof(mmgpu_pf_xhit) : sizeof(mmgpu_pf_hit))));
-    B_TRY(b->d_hit_count.alloc(nqq * 4));
-    B_TRY(b->d_diag_thr.alloc(nqq * 4));
-    B_TRY(b->d_qflags.alloc(nqq * 4));
-    if (par->nucleotide || par->kmer_score) B_TRY(b->d_qncand.alloc(nqq * 4));
+    HIP_TRY(b->d_nsim.alloc(np * 4));
+    HIP_TRY(b->d_list_base.alloc((np + 1) * 4));
+    HIP_TRY(b->d_pos_entries.alloc(np * 4));
+    HIP_TRY(b->d_peb.alloc((np + 1) * 4));
+    HIP_TRY(b->d_qtot.alloc(nqq * 8));
+    HIP_TRY(b->d_qbase.alloc(nqq * 8));
+    HIP_TRY(b->d_qentries.alloc(nqq * 4));
+    HIP_TRY(b->d_qtile_base.alloc(nqq * 4));
+    HIP_TRY(b->d_qntiles.alloc(nqq * 4));
+    HIP_TRY(b->d_bucket_count.alloc((size_t)nqq * bins * 4));
+    HIP_TRY(b->d_bucket_off.alloc(((size_t)nqq + 1) * 4));
+    HIP_TRY(b->d_cand_base.alloc(((size_t)nqq * bins + 1) * 4));
+    HIP_TRY(b->d_cand_count.alloc((size_t)nqq * bins * 4));
+    HIP_TRY(b->d_cand_small.alloc((size_t)nqq * bins * PF_CAND0 * sizeof(PfCand)));
+    HIP_TRY(b->d_cells.alloc((size_t)nqq * 8));
+    HIP_TRY(b->d_surv_count.alloc(nqq * 4));
+    HIP_TRY(b->d_hits.alloc((size_t)nqq * max_hits * (exchange ? sizeof(mmgpu_pf_xhit) : sizeof(mmgpu_pf_hit))));
+    HIP_TRY(b->d_hit_count.alloc(nqq * 4));
+    HIP_TRY(b->d_diag_thr.alloc(nqq * 4));
+    HIP_TRY(b->d_qflags.alloc(nqq * 4));
+    if (par->nucleotide || par->kmer_score) HIP_TRY(b->d_qncand.alloc(nqq * 4));
     if (par->nucleotide) {
-        B_TRY(b->d_sat.alloc((size_t)nqq * PF_SAT_CAP * sizeof(PfCand)));
-        B_TRY(b->d_qnsat.alloc(nqq * 4));
+        HIP_TRY(b->d_sat.alloc((size_t)nqq * PF_SAT_CAP * sizeof(PfCand)));
+        HIP_TRY(b->d_qnsat.alloc(nqq * 4));
     }
     if (max_hits > (uint32_t)PF_MAX_HITS) {
         b->big_stride = 1;
         while (b->big_stride < max_hits) b->big_stride <<= 1;
-        B_TRY(b->d_big_keys.alloc((size_t)nqq * b->big_stride * 8));
-        B_TRY(b->d_big_diags.alloc((size_t)nqq * b->big_stride * 2));
+        HIP_TRY(b->d_big_keys.alloc((size_t)nqq * b->big_stride * 8));
+        HIP_TRY(b->d_big_diags.alloc((size_t)nqq * b->big_stride * 2));
     }
-    for (auto &e : b->ev) B_TRY(hipEventCreate(&e));
-    B_TRY(hipStreamSynchronize(s));
-#undef B_TRY
-    *out = b;
+    for (auto &e : b->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = owner.release();
     return MMGPU_OK;
 }
 
-extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
-    if (!c || !b) return fail(MMGPU_ERR_ARG, "mmgpu_pf_run: NULL argument");
-    if (!c->pf) return fail(MMGPU_ERR_STATE, "mmgpu_pf_run: no index loaded");
-    HIP_TRY(hipSetDevice(c->device));
-    PfIndex &P = *c->pf;
-    P.w_owner = b;
-    hipStream_t s = c->stream;
-    const uint32_t nq = b->nq;
-    b->status.assign(nq, MMGPU_PF_OK);
-    for (uint32_t i = 0; i < nq; i++)
-        if (b->long_query[i]) b->status[i] = MMGPU_PF_LONG_SEQ;
-    b->q_lists.assign(nq, 0);
-    b->q_entries.assign(nq, 0);
-    if (nq == 0) { b->ran = true; return MMGPU_OK; }
-    HIP_TRY(hipEventRecord(b->ev[0], s));
+// ---------------------------------------------------------------------------------------------------------
+// mmgpu_pf_run.  The argument records of the kernels are pure functions of index + batch (+ context); the run sets their
+// per-chunk fields only.
+namespace {
 
-    // ---- stage 0: similar k-mers and their index lists, in the reference's order ----
+// One call of mmgpu_pf_run: what its stages hand to one another.  The host arrays a stage uploads from pageable memory are
+// members where a later stage's synchronisation is the one that protects them, locals where the stage synchronises itself.
+struct PfRun {
+    mmgpu_ctx *c;
+    mmgpu_pf_batch_t *b;
+    PfIndex &P;
+    hipStream_t s;
+    uint32_t nq;
+    PfEnv env = pf_env();
+    std::vector<uint32_t> ovf_q;          // queries on the reference's overflow path that the device emulates
+    std::vector<uint32_t> h_nseg;         // [nq] their number of flushes
+    std::vector<uint32_t> qent, qtb, qnt; // [nq] entries, first tile, tiles (the per-tile lists are written on the device: pf_tiles_kernel)
+    std::vector<uint64_t> qebase;         // [nq] entries of the queries before
+    uint32_t n_tiles = 0, n_chunks = 0;
+    std::vector<uint32_t> chunk_first;    // [n_chunks + 1] stage chunks: runs of consecutive queries
+    uint64_t chunk_max_entries = 0;
+    std::vector<uint32_t> ovf_chunk_lo;   // [n_chunks + 1] the overflow queries of a chunk in ovf_q
+
+    int similar_kmers();
+    int overflow_segments();
+    int tiles();
+    int plan_chunks();
+    int gather_split();
+    int work_list(PfDedupArgs &D);
+    int overflow_flush_buffers(PfOvfArgs &O);
+    int score_chunk(uint32_t ch, PfDedupArgs &D, PfOvfArgs &O);
+};
+
+PfKmerArgs make_kmer_args(const PfIndex &P, const mmgpu_pf_batch_t *b) {
     PfKmerArgs K;
     memset(&K, 0, sizeof(K));
     K.q_res = b->d_qres.as<uint8_t>();
@@ -852,6 +891,12 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     K.cum2_w = P.cum2_w;
     K.score2_min = P.score2_min;
     K.nsim = b->d_nsim.as<uint32_t>();
+    return K;
+}
+
+// ---- stage 0: similar k-mers and their index lists, in the reference's order ----
+int PfRun::similar_kmers() {
+    PfKmerArgs K = make_kmer_args(P, b);
     // work order of the positions (pf_order.hip): built with the batch's first run
     if (!b->order_ready && !K.exact) {
         HIP_TRY(b->d_pos_order.alloc((size_t)b->n_pos * 4));
@@ -882,64 +927,68 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     HIP_TRY(launch_pf_scan(b->d_pos_entries.as<uint32_t>(), b->d_qoff.as<uint32_t>(), nq, nullptr, b->d_peb.as<uint32_t>(), b->d_qtot.as<uint64_t>(), s));
     HIP_TRY(hipMemcpyAsync(b->q_entries.data(), b->d_qtot.p, nq * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));   // qbase (pageable) has been consumed, q_entries is valid
-    HIP_TRY(hipEventRecord(b->ev[1], s));
+    return MMGPU_OK;
+}
 
-    // ---- queries on the reference's overflow path (QueryMatcher.cpp:310-346): segment boundaries ----
-    std::vector<uint32_t> ovf_q;
+PfSegArgs make_seg_args(const PfIndex &P, const mmgpu_pf_batch_t *b, uint32_t n_ovf) {
+    PfSegArgs G;
+    G.ovf_queries = b->d_ovf_queries.as<uint32_t>();
+    G.n_ovf = n_ovf;
+    G.q_off = b->d_qoff.as<uint32_t>();
+    G.list_base = b->d_list_base.as<uint32_t>();
+    G.pos_entry_base = b->d_peb.as<uint32_t>();
+    G.lists = P.w_lists.as<PfList>();
+    G.cap = b->max_db_matches;
+    G.seg_start = b->d_seg_start.as<uint32_t>();
+    G.q_nseg = b->d_qnseg.as<uint32_t>();
+    G.q_final = b->d_qfinal.as<uint32_t>();
+    G.q_entries = b->d_qentries.as<uint32_t>();
+    return G;
+}
+
+// ---- queries on the reference's overflow path (QueryMatcher.cpp:310-346): segment boundaries ----
+int PfRun::overflow_segments() {
     for (uint32_t i = 0; i < nq; i++)
         if (b->q_entries[i] >= b->max_db_matches) ovf_q.push_back(i);
-    std::vector<uint32_t> h_nseg(nq, 0);
-    uint32_t max_seg = 0;
-    if (!ovf_q.empty()) {
-        HIP_TRY(b->d_ovf_queries.reserve(ovf_q.size() * 4));
-        HIP_TRY(b->d_qnseg.reserve((size_t)nq * 4));
-        HIP_TRY(b->d_qfinal.reserve((size_t)nq * 4));
-        HIP_TRY(b->d_seg_start.reserve((size_t)nq * (PF_MAX_SEG + 2) * 4));
-        HIP_TRY(hipMemcpyAsync(b->d_ovf_queries.p, ovf_q.data(), ovf_q.size() * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(b->d_qnseg.p, 0, (size_t)nq * 4, s));
-        HIP_TRY(hipMemsetAsync(b->d_qfinal.p, 0, (size_t)nq * 4, s));
-        std::vector<uint32_t> e32(nq);
-        for (uint32_t i = 0; i < nq; i++) e32[i] = (uint32_t)std::min<uint64_t>(b->q_entries[i], 0xFFFFFFFFull);
-        HIP_TRY(hipMemcpyAsync(b->d_qentries.p, e32.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
-        PfSegArgs G;
-        G.ovf_queries = b->d_ovf_queries.as<uint32_t>();
-        G.n_ovf = (uint32_t)ovf_q.size();
-        G.q_off = b->d_qoff.as<uint32_t>();
-        G.list_base = b->d_list_base.as<uint32_t>();
-        G.pos_entry_base = b->d_peb.as<uint32_t>();
-        G.lists = P.w_lists.as<PfList>();
-        G.cap = b->max_db_matches;
-        G.seg_start = b->d_seg_start.as<uint32_t>();
-        G.q_nseg = b->d_qnseg.as<uint32_t>();
-        G.q_final = b->d_qfinal.as<uint32_t>();
-        G.q_entries = b->d_qentries.as<uint32_t>();
-        HIP_TRY(launch_pf_segments(G, s));
-        HIP_TRY(hipMemcpyAsync(h_nseg.data(), b->d_qnseg.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        bool rewrite = false;
-        std::vector<uint32_t> keep;
-        for (uint32_t i : ovf_q) {
-            // (--diag-score 0 merges the segments by score, QueryMatcher.cpp:514-533: not on the device either)
-            if (h_nseg[i] == 0 || h_nseg[i] > (uint32_t)PF_MAX_SEG || b->q_entries[i] >= 0xF0000000ull || b->par.kmer_score) {
-                h_nseg[i] = 0;      // more flushes than the device emulates: the host runs the reference for this query
-                b->status[i] = MMGPU_PF_OVERFLOW;
-                rewrite = true;
-            } else {
-                keep.push_back(i);
-                max_seg = std::max(max_seg, h_nseg[i]);
-            }
-        }
-        ovf_q.swap(keep);
-        if (rewrite) {
-            HIP_TRY(hipMemcpyAsync(b->d_qnseg.p, h_nseg.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
-            if (!ovf_q.empty()) HIP_TRY(hipMemcpyAsync(b->d_ovf_queries.p, ovf_q.data(), ovf_q.size() * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
+    h_nseg.assign(nq, 0);
+    if (ovf_q.empty()) return MMGPU_OK;
+    HIP_TRY(b->d_ovf_queries.reserve(ovf_q.size() * 4));
+    HIP_TRY(b->d_qnseg.reserve((size_t)nq * 4));
+    HIP_TRY(b->d_qfinal.reserve((size_t)nq * 4));
+    HIP_TRY(b->d_seg_start.reserve((size_t)nq * (PF_MAX_SEG + 2) * 4));
+    HIP_TRY(hipMemcpyAsync(b->d_ovf_queries.p, ovf_q.data(), ovf_q.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(b->d_qnseg.p, 0, (size_t)nq * 4, s));
+    HIP_TRY(hipMemsetAsync(b->d_qfinal.p, 0, (size_t)nq * 4, s));
+    std::vector<uint32_t> e32(nq);
+    for (uint32_t i = 0; i < nq; i++) e32[i] = (uint32_t)std::min<uint64_t>(b->q_entries[i], 0xFFFFFFFFull);
+    HIP_TRY(hipMemcpyAsync(b->d_qentries.p, e32.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_pf_segments(make_seg_args(P, b, (uint32_t)ovf_q.size()), s));
+    HIP_TRY(hipMemcpyAsync(h_nseg.data(), b->d_qnseg.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));      // e32 (pageable) has been consumed, h_nseg is valid
+    bool rewrite = false;
+    std::vector<uint32_t> keep;
+    for (uint32_t i : ovf_q) {
+        // (--diag-score 0 merges the segments by score, QueryMatcher.cpp:514-533: not on the device either)
+        if (h_nseg[i] == 0 || h_nseg[i] > (uint32_t)PF_MAX_SEG || b->q_entries[i] >= 0xF0000000ull || b->par.kmer_score) {
+            h_nseg[i] = 0;      // more flushes than the device emulates: the host runs the reference for this query
+            b->status[i] = MMGPU_PF_OVERFLOW;
+            rewrite = true;
+        } else {
+            keep.push_back(i);
         }
     }
+    ovf_q.swap(keep);
+    if (rewrite) {
+        HIP_TRY(hipMemcpyAsync(b->d_qnseg.p, h_nseg.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        if (!ovf_q.empty()) HIP_TRY(hipMemcpyAsync(b->d_ovf_queries.p, ovf_q.data(), ovf_q.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return MMGPU_OK;
+}
 
-    // ---- tiles ----
-    std::vector<uint32_t> qent(nq), qtb(nq), qnt(nq);      // (the per-tile lists are written on the device: pf_tiles_kernel)
-    std::vector<uint64_t> qebase(nq);
+// ---- tiles ----
+int PfRun::tiles() {
+    qent.resize(nq); qtb.resize(nq); qnt.resize(nq); qebase.resize(nq);
     uint64_t total_entries = 0, tiles_so_far = 0;
     for (uint32_t i = 0; i < nq; i++) {
         uint64_t e = b->q_entries[i];
@@ -954,10 +1003,10 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     if (tiles_so_far >= 0xFFFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_run: >= 2^32 tiles in one batch; use smaller batches");
     // (total_entries may pass 2^32: the 32-bit bases derived from it - cand_base, cand_origin - only ever meet as differences
     // inside one stage chunk, whose entries are bounded below)
-    const uint32_t n_tiles = (uint32_t)tiles_so_far;
+    n_tiles = (uint32_t)tiles_so_far;
     b->last_tiles = n_tiles;
     b->last_entries = total_entries;
-    const uint32_t B = b->bins;
+    // (qent, qtb, qnt, qebase are pageable: gather_split's synchronisation is the one that follows these copies)
     HIP_TRY(hipMemcpyAsync(b->d_qentries.p, qent.data(), nq * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b->d_qtile_base.p, qtb.data(), nq * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b->d_qntiles.p, qnt.data(), nq * 4, hipMemcpyHostToDevice, s));
@@ -967,36 +1016,36 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     if (n_tiles) HIP_TRY(launch_pf_tiles(b->d_qtile_base.as<uint32_t>(), b->d_qntiles.as<uint32_t>(), nq, P.w_tile_q.as<uint32_t>(), P.w_tile_idx.as<uint32_t>(), s));
     HIP_TRY(P.w_split.reserve(std::max<size_t>(n_tiles, 1) * PF_T * sizeof(uint32_t)));
     HIP_TRY(P.w_split_hi.reserve(std::max<size_t>(n_tiles, 1) * PF_T));
-    HIP_TRY(P.w_bin_off.reserve(std::max<size_t>(n_tiles, 1) * (B + 1) * sizeof(uint16_t)));
-    // Stages 2 and 3 run over CHUNKS of consecutive queries: the candidate / survivor arrays are entry-sized (every entry
-    // of a bin can be a candidate), 32 B per entry, of which ~1 % is touched - 115 GB for a 10 000-query batch against
-    // 1 M targets.  A chunk is the longest run of queries whose entries fit MMGPU_PF_STAGE_GB (default 16 GB for both
-    // arrays); the arrays are re-used from chunk to chunk (same stream, so the order is the program order).
-    std::vector<uint32_t> chunk_first;
-    uint64_t chunk_max_entries = 0;
+    HIP_TRY(P.w_bin_off.reserve(std::max<size_t>(n_tiles, 1) * (b->bins + 1) * sizeof(uint16_t)));
+    return MMGPU_OK;
+}
+
+// Stages 2 and 3 run over CHUNKS of consecutive queries: the candidate / survivor arrays are entry-sized (every entry
+// of a bin can be a candidate), 32 B per entry, of which ~1 % is touched - 115 GB for a 10 000-query batch against
+// 1 M targets.  A chunk is the longest run of queries whose entries fit MMGPU_PF_STAGE_GB (default 16 GB for both
+// arrays); the arrays are re-used from chunk to chunk (same stream, so the order is the program order).
+int PfRun::plan_chunks() {
+    // (one chunk per ~40 GB on a 288 GB device: every chunk ends with the tail of its replay grid and four small launches -
+    // 7 chunks of 16 GB cost the 10 000-query batch 1 ms more than 3 of 40, profiles/r05_exp_pf_stage_chunks.txt)
+    double gb = 16.0;
     {
-        // (one chunk per ~40 GB on a 288 GB device: every chunk ends with the tail of its replay grid and four small launches -
-        // 7 chunks of 16 GB cost the 10 000-query batch 1 ms more than 3 of 40, profiles/r05_exp_pf_stage_chunks.txt)
-        double gb = 16.0;
-        {
-            size_t mem_free = 0, mem_total = 0;
-            if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_total >= (192ull << 30) && mem_free >= (120ull << 30)) gb = 40.0;
-        }
-        if (const char *e = getenv("MMGPU_PF_STAGE_GB")) gb = atof(e);
-        // (a chunk's entries stay below 2^32 whatever the budget: the candidate bases are 32-bit differences inside a chunk)
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>((uint64_t)(gb * 1073741824.0 / (2.0 * sizeof(PfCand))), 1), 0xF0000000ull);
-        uint64_t run = 0;
-        for (uint32_t i = 0; i < nq; i++) {
-            if (i == 0 || run + qent[i] > cap) {
-                chunk_first.push_back(i);
-                run = 0;
-            }
-            run += qent[i];
-            chunk_max_entries = std::max(chunk_max_entries, run);
-        }
-        chunk_first.push_back(nq);
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_total >= (192ull << 30) && mem_free >= (120ull << 30)) gb = 40.0;
     }
-    const uint32_t n_chunks = (uint32_t)chunk_first.size() - 1;
+    if (env.has_stage_gb) gb = env.stage_gb;
+    // (a chunk's entries stay below 2^32 whatever the budget: the candidate bases are 32-bit differences inside a chunk)
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>((uint64_t)(gb * 1073741824.0 / (2.0 * sizeof(PfCand))), 1), 0xF0000000ull);
+    uint64_t run = 0;
+    for (uint32_t i = 0; i < nq; i++) {
+        if (i == 0 || run + qent[i] > cap) {
+            chunk_first.push_back(i);
+            run = 0;
+        }
+        run += qent[i];
+        chunk_max_entries = std::max(chunk_max_entries, run);
+    }
+    chunk_first.push_back(nq);
+    n_chunks = (uint32_t)chunk_first.size() - 1;
     b->last_chunks = n_chunks;
     while (b->chunk_ev.size() < (size_t)4 * n_chunks) {
         hipEvent_t e = nullptr;
@@ -1005,14 +1054,17 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     }
     HIP_TRY(P.w_cand.reserve(std::max<uint64_t>(chunk_max_entries, 1) * sizeof(PfCand)));
     HIP_TRY(P.w_surv.reserve(std::max<uint64_t>(chunk_max_entries, 1) * sizeof(PfCand)));
+    const uint32_t B = b->bins;
     HIP_TRY(hipMemsetAsync(b->d_bucket_count.p, 0, (size_t)nq * B * 4, s));
     HIP_TRY(hipMemsetAsync(b->d_surv_count.p, 0, (size_t)nq * 4, s));
     HIP_TRY(hipMemsetAsync(b->d_cells.p, 0, (size_t)nq * 8, s));
     HIP_TRY(hipMemsetAsync(b->d_qflags.p, 0, (size_t)nq * 4, s));
     if (b->par.nucleotide || b->par.kmer_score) HIP_TRY(hipMemsetAsync(b->d_qncand.p, 0, (size_t)nq * 4, s));
     if (b->par.nucleotide) HIP_TRY(hipMemsetAsync(b->d_qnsat.p, 0, (size_t)nq * 4, s));
+    return MMGPU_OK;
+}
 
-    // ---- stage 1: gather + stable split ----
+PfSplitArgs make_split_args(const PfIndex &P, const mmgpu_pf_batch_t *b) {
     PfSplitArgs SA;
     SA.tile_q = P.w_tile_q.as<uint32_t>();
     SA.tile_idx = P.w_tile_idx.as<uint32_t>();
@@ -1022,27 +1074,33 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     SA.list_base = b->d_list_base.as<uint32_t>();
     SA.lists = P.w_lists.as<PfList>();
     SA.idx_entries = P.d_entries.as<uint64_t>();
-    SA.bins = B;
+    SA.bins = b->bins;
     SA.split = P.w_split.as<uint32_t>();
     SA.split_hi = P.w_split_hi.as<uint8_t>();
     SA.bin_off = P.w_bin_off.as<uint16_t>();
     SA.bucket_count = b->d_bucket_count.as<uint32_t>();
-    HIP_TRY(launch_pf_split(SA, n_tiles, s));
-    // cand_base[q * B + bin] = entries of earlier queries + entries of earlier bins of this query
-    {
-        std::vector<uint32_t> boff(nq + 1);
-        for (uint32_t i = 0; i <= nq; i++) boff[i] = i * B;
-        HIP_TRY(hipMemcpyAsync(b->d_bucket_off.p, boff.data(), (size_t)(nq + 1) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(launch_pf_scan(b->d_bucket_count.as<uint32_t>(), b->d_bucket_off.as<uint32_t>(), nq, b->d_qbase.as<uint64_t>(),
-                               b->d_cand_base.as<uint32_t>(), nullptr, s));
-        HIP_TRY(hipStreamSynchronize(s));   // host vectors above are pageable
-    }
-    HIP_TRY(hipEventRecord(b->ev[2], s));
+    return SA;
+}
 
-    // ---- stage 2: replay, ungapped score, best element per target ----
+// ---- stage 1: gather + stable split ----
+int PfRun::gather_split() {
+    const uint32_t B = b->bins;
+    HIP_TRY(launch_pf_split(make_split_args(P, b), n_tiles, s));
+    // cand_base[q * B + bin] = entries of earlier queries + entries of earlier bins of this query
+    std::vector<uint32_t> boff(nq + 1);
+    for (uint32_t i = 0; i <= nq; i++) boff[i] = i * B;
+    HIP_TRY(hipMemcpyAsync(b->d_bucket_off.p, boff.data(), (size_t)(nq + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_pf_scan(b->d_bucket_count.as<uint32_t>(), b->d_bucket_off.as<uint32_t>(), nq, b->d_qbase.as<uint64_t>(),
+                           b->d_cand_base.as<uint32_t>(), nullptr, s));
+    HIP_TRY(hipStreamSynchronize(s));   // boff and the vectors of tiles() are pageable
+    return MMGPU_OK;
+}
+
+// stage 2 (per chunk: q_first, n_queries, cand_origin, big_count; big_list where the run has a work list)
+PfDedupArgs make_dedup_args(const mmgpu_ctx *c, const PfIndex &P, const mmgpu_pf_batch_t *b, bool overflow_queries) {
     PfDedupArgs D;
-    D.n_queries = nq;
-    D.bins = B;
+    D.n_queries = b->nq;
+    D.bins = b->bins;
     D.q_tile_base = b->d_qtile_base.as<uint32_t>();
     D.q_ntiles = b->d_qntiles.as<uint32_t>();
     D.split = P.w_split.as<uint32_t>();
@@ -1071,49 +1129,59 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     D.min_diag_score = b->par.min_diag_score;
     D.cand_count = b->d_cand_count.as<uint32_t>();
     D.cand_small = b->d_cand_small.as<PfCand>();
-    D.q_nseg = ovf_q.empty() ? nullptr : b->d_qnseg.as<uint32_t>();
-    D.seg_start = ovf_q.empty() ? nullptr : b->d_seg_start.as<uint32_t>();
+    D.q_nseg = overflow_queries ? b->d_qnseg.as<uint32_t>() : nullptr;
+    D.seg_start = overflow_queries ? b->d_seg_start.as<uint32_t>() : nullptr;
     D.cell_counter = b->d_cells.as<uint64_t>();
     D.q_flags = b->d_qflags.as<uint32_t>();
     D.ref_bins = b->ref_bins;
     D.big_list = D.big_count = nullptr;
-    {   // the work list of the larger buckets: one list (re-used from chunk to chunk, same stream) and one counter per chunk
-        uint64_t chunk_buckets = 0;
-        for (uint32_t ch = 0; ch < n_chunks; ch++) chunk_buckets = std::max<uint64_t>(chunk_buckets, (uint64_t)(chunk_first[ch + 1] - chunk_first[ch]) * B);
-        if (!b->par.kmer_score && chunk_buckets > 0 && chunk_buckets < 0xFFFFFFFFull) {
-            HIP_TRY(b->d_work_list.reserve(chunk_buckets * 4));
-            HIP_TRY(b->d_work_count.reserve((size_t)n_chunks * 4));
-            HIP_TRY(hipMemsetAsync(b->d_work_count.p, 0, (size_t)n_chunks * 4, s));
-            D.big_list = b->d_work_list.as<uint32_t>();
-        }
-    }
-    // the flushes of the overflow path: per-query bases relative to the first overflow query of the same chunk
-    std::vector<uint32_t> ovf_chunk_lo(n_chunks + 1, 0);
-    PfOvfArgs O;
-    if (!ovf_q.empty()) {
-        std::vector<uint64_t> obase(ovf_q.size());
-        uint64_t oe_max = 0;
-        size_t z = 0;
-        for (uint32_t ch = 0; ch < n_chunks; ch++) {
-            ovf_chunk_lo[ch] = (uint32_t)z;
-            uint64_t oe = 0;
-            for (; z < ovf_q.size() && ovf_q[z] < chunk_first[ch + 1]; z++) { obase[z] = oe; oe += qent[ovf_q[z]]; }
-            oe_max = std::max(oe_max, oe);
-        }
-        ovf_chunk_lo[n_chunks] = (uint32_t)ovf_q.size();
-        HIP_TRY(b->d_ovf_base.reserve(obase.size() * 8));
-        HIP_TRY(b->d_ovf_a.reserve(std::max<uint64_t>(oe_max, 1) * sizeof(PfOvfElem)));
-        HIP_TRY(b->d_ovf_b.reserve(std::max<uint64_t>(oe_max, 1) * sizeof(PfOvfElem)));
-        HIP_TRY(b->d_ovf_ocount.reserve(ovf_q.size() * (size_t)B * 4));
-        HIP_TRY(b->d_ovf_totals.reserve(ovf_q.size() * (size_t)(PF_MAX_SEG + 2) * 4));
-        HIP_TRY(hipMemcpyAsync(b->d_ovf_base.p, obase.data(), obase.size() * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(b->d_ovf_ocount.p, 0, ovf_q.size() * (size_t)B * 4, s));
-        HIP_TRY(hipMemsetAsync(b->d_ovf_totals.p, 0, ovf_q.size() * (size_t)(PF_MAX_SEG + 2) * 4, s));
-        HIP_TRY(hipStreamSynchronize(s));   // obase is pageable
-        O.q_final = b->d_qfinal.as<uint32_t>();
-    }
+    return D;
+}
 
-    // ---- stage 3: top max_hits per query ----
+// the work list of the larger buckets: one list (re-used from chunk to chunk, same stream) and one counter per chunk
+int PfRun::work_list(PfDedupArgs &D) {
+    const uint32_t B = b->bins;
+    uint64_t chunk_buckets = 0;
+    for (uint32_t ch = 0; ch < n_chunks; ch++) chunk_buckets = std::max<uint64_t>(chunk_buckets, (uint64_t)(chunk_first[ch + 1] - chunk_first[ch]) * B);
+    if (!b->par.kmer_score && chunk_buckets > 0 && chunk_buckets < 0xFFFFFFFFull) {
+        HIP_TRY(b->d_work_list.reserve(chunk_buckets * 4));
+        HIP_TRY(b->d_work_count.reserve((size_t)n_chunks * 4));
+        HIP_TRY(hipMemsetAsync(b->d_work_count.p, 0, (size_t)n_chunks * 4, s));
+        D.big_list = b->d_work_list.as<uint32_t>();
+    }
+    return MMGPU_OK;
+}
+
+// the flushes of the overflow path: per-query bases relative to the first overflow query of the same chunk
+int PfRun::overflow_flush_buffers(PfOvfArgs &O) {
+    const uint32_t B = b->bins;
+    ovf_chunk_lo.assign(n_chunks + 1, 0);
+    if (ovf_q.empty()) return MMGPU_OK;
+    std::vector<uint64_t> obase(ovf_q.size());
+    uint64_t oe_max = 0;
+    size_t z = 0;
+    for (uint32_t ch = 0; ch < n_chunks; ch++) {
+        ovf_chunk_lo[ch] = (uint32_t)z;
+        uint64_t oe = 0;
+        for (; z < ovf_q.size() && ovf_q[z] < chunk_first[ch + 1]; z++) { obase[z] = oe; oe += qent[ovf_q[z]]; }
+        oe_max = std::max(oe_max, oe);
+    }
+    ovf_chunk_lo[n_chunks] = (uint32_t)ovf_q.size();
+    HIP_TRY(b->d_ovf_base.reserve(obase.size() * 8));
+    HIP_TRY(b->d_ovf_a.reserve(std::max<uint64_t>(oe_max, 1) * sizeof(PfOvfElem)));
+    HIP_TRY(b->d_ovf_b.reserve(std::max<uint64_t>(oe_max, 1) * sizeof(PfOvfElem)));
+    HIP_TRY(b->d_ovf_ocount.reserve(ovf_q.size() * (size_t)B * 4));
+    HIP_TRY(b->d_ovf_totals.reserve(ovf_q.size() * (size_t)(PF_MAX_SEG + 2) * 4));
+    HIP_TRY(hipMemcpyAsync(b->d_ovf_base.p, obase.data(), obase.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(b->d_ovf_ocount.p, 0, ovf_q.size() * (size_t)B * 4, s));
+    HIP_TRY(hipMemsetAsync(b->d_ovf_totals.p, 0, ovf_q.size() * (size_t)(PF_MAX_SEG + 2) * 4, s));
+    HIP_TRY(hipStreamSynchronize(s));   // obase is pageable
+    O.q_final = b->d_qfinal.as<uint32_t>();
+    return MMGPU_OK;
+}
+
+// stage 3 (per chunk: q_first, cand_origin)
+PfSelectArgs make_select_args(const mmgpu_ctx *c, const PfIndex &P, const mmgpu_pf_batch_t *b, const PfEnv &env, bool overflow_queries) {
     PfSelectArgs S;
     S.surv = P.w_surv.as<PfCand>();
     S.surv_count = b->d_surv_count.as<uint32_t>();
@@ -1127,7 +1195,7 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     S.hit_count = b->d_hit_count.as<uint32_t>();
     S.q_diag_thr = b->d_diag_thr.as<uint32_t>();
     S.cand_base = b->d_cand_base.as<uint32_t>();
-    S.bins = B;
+    S.bins = b->bins;
     S.xhits = nullptr;
     S.global_ids = nullptr;
     S.q_nseg = nullptr;
@@ -1139,7 +1207,7 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
         const uint64_t db_all = b->exchange ? c->shard.global_n : c->db.n;
         uint64_t cap = std::max<uint64_t>(1000000, db_all) / 2;
         if (b->exchange) cap = std::max<uint64_t>(1, cap / std::max<uint32_t>(1, c->shard.n_shards));
-        if (const char *e = getenv("MMGPU_PF_SORT_CAP")) cap = strtoull(e, nullptr, 10);     // tests: a small database reaches the branch
+        if (env.has_sort_cap) cap = env.sort_cap;     // tests: a small database reaches the branch
         S.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
         S.cand_count = (b->par.nucleotide || b->par.kmer_score) ? nullptr : b->d_cand_count.as<uint32_t>();
     }
@@ -1149,55 +1217,92 @@ extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
     S.q_off = S.peb = S.list_base = nullptr;
     S.lists = nullptr;
     if (b->exchange) {
-        if (!c->shard.on) return fail(MMGPU_ERR_STATE, "mmgpu_pf_run: the batch was prepared for a sharded run, but no shard is set");
         S.xhits = b->d_hits.as<mmgpu_pf_xhit>();
         S.hits = nullptr;
         S.global_ids = c->shard.d_global_ids.as<uint32_t>();
-        S.q_nseg = ovf_q.empty() ? nullptr : b->d_qnseg.as<uint32_t>();
+        S.q_nseg = overflow_queries ? b->d_qnseg.as<uint32_t>() : nullptr;
         S.q_off = b->d_qoff.as<uint32_t>();
         S.peb = b->d_peb.as<uint32_t>();
         S.list_base = b->d_list_base.as<uint32_t>();
         S.lists = P.w_lists.as<PfList>();
     }
-    for (uint32_t ch = 0; ch < n_chunks; ch++) {
-        const uint32_t q0 = chunk_first[ch], cn = chunk_first[ch + 1] - q0;
-        hipEvent_t *cev = &b->chunk_ev[(size_t)4 * ch];
-        // ---- stage 2: replay, ungapped score, best element per target ----
-        D.q_first = q0;
-        D.n_queries = cn;
-        D.cand_origin = (uint32_t)qebase[q0];
-        if (D.big_list) D.big_count = b->d_work_count.as<uint32_t>() + ch;
-        if (b->par.kmer_score) HIP_TRY(launch_pf_count(D, cev[0], cev[1], s));
-        else {
-            HIP_TRY(launch_pf_dedup(D, cev[0], cev[1], s));
-            // candidates on targets of 32768 residues or more: computeLongScore and the batches of scoreDiagonalAndUpdateHits (a shard
-            // leaves such queries flagged: the unsplit re-run scores them)
-            if ((c->db.max_len >= 32768u || b->long_queries_on_device) && !b->exchange && !b->par.nucleotide) HIP_TRY(launch_pf_long(D, b->long_queries_on_device, s));
+    return S;
+}
+
+// ---- stage 2 of one chunk: replay, ungapped score, best element per target (+ long targets, + the overflow queries' flushes) ----
+int PfRun::score_chunk(uint32_t ch, PfDedupArgs &D, PfOvfArgs &O) {
+    const uint32_t B = b->bins;
+    hipEvent_t *cev = &b->chunk_ev[(size_t)4 * ch];
+    D.q_first = chunk_first[ch];
+    D.n_queries = chunk_first[ch + 1] - chunk_first[ch];
+    D.cand_origin = (uint32_t)qebase[chunk_first[ch]];
+    if (D.big_list) D.big_count = b->d_work_count.as<uint32_t>() + ch;
+    if (b->par.kmer_score) HIP_TRY(launch_pf_count(D, cev[0], cev[1], s));
+    else {
+        HIP_TRY(launch_pf_dedup(D, cev[0], cev[1], s));
+        // candidates on targets of 32768 residues or more: computeLongScore and the batches of scoreDiagonalAndUpdateHits (a shard
+        // leaves such queries flagged: the unsplit re-run scores them)
+        if ((c->db.max_len >= 32768u || b->long_queries_on_device) && !b->exchange && !b->par.nucleotide) HIP_TRY(launch_pf_long(D, b->long_queries_on_device, s));
+    }
+    const uint32_t z0 = ovf_chunk_lo[ch], z1 = ovf_chunk_lo[ch + 1];
+    if (z1 > z0) {
+        // one launch per flush (the total kept after flush k decides what flush k+1 does)
+        O.D = D;
+        O.ovf_queries = b->d_ovf_queries.as<uint32_t>() + z0;
+        O.n_ovf = z1 - z0;
+        O.ovf_base = b->d_ovf_base.as<uint64_t>() + z0;
+        O.buf_a = b->d_ovf_a.as<PfOvfElem>();
+        O.buf_b = b->d_ovf_b.as<PfOvfElem>();
+        O.o_count = b->d_ovf_ocount.as<uint32_t>() + (size_t)z0 * B;
+        O.totals = b->d_ovf_totals.as<uint32_t>() + (size_t)z0 * (PF_MAX_SEG + 2);
+        uint32_t chunk_seg = 0;
+        for (uint32_t zz = z0; zz < z1; zz++) chunk_seg = std::max(chunk_seg, h_nseg[ovf_q[zz]]);
+        for (uint32_t step = 1; step <= chunk_seg + 1; step++) {
+            O.step = step;
+            HIP_TRY(launch_pf_overflow(O, s));
         }
-        const uint32_t z0 = ovf_chunk_lo[ch], z1 = ovf_chunk_lo[ch + 1];
-        if (z1 > z0) {
-            // one launch per flush (the total kept after flush k decides what flush k+1 does)
-            O.D = D;
-            O.ovf_queries = b->d_ovf_queries.as<uint32_t>() + z0;
-            O.n_ovf = z1 - z0;
-            O.ovf_base = b->d_ovf_base.as<uint64_t>() + z0;
-            O.buf_a = b->d_ovf_a.as<PfOvfElem>();
-            O.buf_b = b->d_ovf_b.as<PfOvfElem>();
-            O.o_count = b->d_ovf_ocount.as<uint32_t>() + (size_t)z0 * B;
-            O.totals = b->d_ovf_totals.as<uint32_t>() + (size_t)z0 * (PF_MAX_SEG + 2);
-            uint32_t chunk_seg = 0;
-            for (uint32_t zz = z0; zz < z1; zz++) chunk_seg = std::max(chunk_seg, h_nseg[ovf_q[zz]]);
-            for (uint32_t step = 1; step <= chunk_seg + 1; step++) {
-                O.step = step;
-                HIP_TRY(launch_pf_overflow(O, s));
-            }
-        }
-        HIP_TRY(hipEventRecord(cev[2], s));
+    }
+    HIP_TRY(hipEventRecord(cev[2], s));
+    return MMGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int mmgpu_pf_run(mmgpu_ctx *c, mmgpu_pf_batch_t *b) {
+    if (!c || !b) return fail(MMGPU_ERR_ARG, "mmgpu_pf_run: NULL argument");
+    if (!c->pf) return fail(MMGPU_ERR_STATE, "mmgpu_pf_run: no index loaded");
+    HIP_TRY(hipSetDevice(c->device));
+    PfRun R{c, b, *c->pf, c->stream, b->nq};
+    R.P.w_owner = b;
+    hipStream_t s = c->stream;
+    const uint32_t nq = b->nq;
+    b->status.assign(nq, MMGPU_PF_OK);
+    for (uint32_t i = 0; i < nq; i++)
+        if (b->long_query[i]) b->status[i] = MMGPU_PF_LONG_SEQ;
+    b->q_lists.assign(nq, 0);
+    b->q_entries.assign(nq, 0);
+    if (nq == 0) { b->ran = true; return MMGPU_OK; }
+    HIP_TRY(hipEventRecord(b->ev[0], s));
+    if (int e = R.similar_kmers()) return e;
+    HIP_TRY(hipEventRecord(b->ev[1], s));
+    if (int e = R.overflow_segments()) return e;
+    if (int e = R.tiles()) return e;
+    if (int e = R.plan_chunks()) return e;
+    if (int e = R.gather_split()) return e;
+    HIP_TRY(hipEventRecord(b->ev[2], s));
+    if (b->exchange && !c->shard.on) return fail(MMGPU_ERR_STATE, "mmgpu_pf_run: the batch was prepared for a sharded run, but no shard is set");
+    PfDedupArgs D = make_dedup_args(c, R.P, b, !R.ovf_q.empty());
+    PfSelectArgs S = make_select_args(c, R.P, b, R.env, !R.ovf_q.empty());
+    PfOvfArgs O;
+    if (int e = R.work_list(D)) return e;
+    if (int e = R.overflow_flush_buffers(O)) return e;
+    for (uint32_t ch = 0; ch < R.n_chunks; ch++) {
+        if (int e = R.score_chunk(ch, D, O)) return e;
         // ---- stage 3: top max_hits per query ----
-        S.q_first = q0;
+        S.q_first = D.q_first;
         S.cand_origin = D.cand_origin;
-        HIP_TRY(launch_pf_select(S, cn, s));
-        HIP_TRY(hipEventRecord(cev[3], s));
+        HIP_TRY(launch_pf_select(S, D.n_queries, s));
+        HIP_TRY(hipEventRecord(b->chunk_ev[(size_t)4 * ch + 3], s));
     }
     HIP_TRY(hipEventRecord(b->ev[4], s));
     b->ran = true;

@@ -732,6 +732,11 @@ __global__ __launch_bounds__(256) void sw_from_pf_kernel(SwFromPfArgs A) {
 }  // namespace
 
 hipError_t launch_sw_from_pf(const SwFromPfArgs &A, uint32_t nq, hipStream_t stream) {
+    // the kernel orders a list in np2 * 4 bytes of dynamic LDS: the longest list it is given must keep that within the 64 KB a
+    // workgroup may ask for without the launch attribute that raises the ceiling
+    static_assert((SW_PF_MAX_LIST & (SW_PF_MAX_LIST - 1)) == 0 && (size_t)SW_PF_MAX_LIST * sizeof(uint32_t) <= 65536,
+                  "SW_PF_MAX_LIST: a power of two whose dwords fit 64 KB of dynamic LDS");
+    if (A.stride > (uint32_t)SW_PF_MAX_LIST) return hipErrorInvalidValue;
     if (nq == 0) return hipSuccess;
     uint32_t np2 = 1;
     while (np2 < A.stride) np2 <<= 1;
