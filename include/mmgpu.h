@@ -87,12 +87,20 @@ int mmgpu_load_targets(mmgpu_ctx *ctx, const uint8_t *residues, const uint64_t *
 /* Loading a database drops a resident prefilter index (it indexes the previous database): call mmgpu_pf_load_index /
  * mmgpu_pf_build_index again, and free prefilter batches prepared against the old index first. */
 
-/* ---- gapped alignment (behind Alignment::run) -------------------------------------------------- */
+/* ---- gapped alignment (behind Alignment::run) --------------------------------------------------
+ * The acceptance rule.  The kernels compute the plain cell-by-cell Gotoh recurrence; the reference's striped lazy-F loops
+ * (StripedSmithWaterman.cpp:205-230, :399-411) give the same numbers only for
+ *     gap_open > gap_extend >= 0   and   min(P) + min(comp_bias) + gap_extend > -gap_open
+ * where min(P) is the lowest substitution score the query can meet (the matrix minimum, or the minimum of a profile query's
+ * rows) and min(comp_bias) the lowest composition-bias value of the query, both <= 0 (why: oracle/sw_oracle.c).  mmgpu_sw_prepare
+ * and its siblings return MMGPU_ERR_UNSUPPORTED for a batch that holds a query outside the rule - e.g. gap_open == gap_extend,
+ * PAM30 or VTML40 at 11/1, a homopolymer query at 8/2: the reference accepts those settings, so the host runs such queries
+ * through its own aligner (integration/MMGpuMatcher.cpp does).  Negative costs or gap_open > 32767 are MMGPU_ERR_ARG. */
 typedef struct {
     const int8_t *mat; /* alphabet*alphabet, row-major: Matcher::tinySubMat (Matcher.cpp:29-36) */
     int alphabet;      /* 21 for amino acids */
-    int gap_open;      /* cost of the first gap residue, par.gapOpen (11) */
-    int gap_extend;    /* par.gapExtend (1) */
+    int gap_open;      /* cost of the first gap residue, par.gapOpen (11); > gap_extend (the rule above) */
+    int gap_extend;    /* par.gapExtend (1); >= 0 */
 } mmgpu_sw_params;
 
 typedef struct {

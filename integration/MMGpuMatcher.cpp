@@ -108,10 +108,12 @@ bool MMGpuMatcher::alignBlock(const std::vector<Query> &queries, int covMode, fl
     par.alphabet = m->alphabetSize;
     par.gap_open = gapOpen;
     par.gap_extend = gapExtend;
-    // The device computes the textbook Gotoh recurrence; the reference's striped lazy-F loop equals it only while
-    // min(P) + gapExtend > -gapOpen (include/mmgpu.h, mmgpu_sw_prepare refuses a batch otherwise).  With small gap
-    // penalties (--gap-open 9 --gap-extend 2) a query with a strongly negative composition bias leaves that regime: its
-    // pairs go to the host's own Matcher::getSWResult as a whole (refusedPairs), the other queries of the block to the device.
+    // The device computes the textbook Gotoh recurrence; the reference's striped lazy-F loop equals it only inside the
+    // acceptance rule (include/mmgpu.h mmgpu_sw_params; mmgpu_sw_prepare refuses a batch otherwise):
+    //     gapOpen > gapExtend >= 0   and   min(P) + min(comp_bias) + gapExtend > -gapOpen
+    // With --gap-open <= --gap-extend the whole run leaves it, with small gap penalties (--gap-open 9 --gap-extend 2) a query
+    // with a strongly negative composition bias does: such a query's pairs go to the host's own Matcher::getSWResult as a
+    // whole (refusedPairs), the other queries of the block to the device.
     std::vector<unsigned char> hostQuery(nq, 0);
     size_t nHost = 0, nHostPairs = 0;
     {
@@ -126,7 +128,7 @@ bool MMGpuMatcher::alignBlock(const std::vector<Query> &queries, int covMode, fl
             } else {
                 for (int i = 0; i < qu.L; i++) minCb = std::min(minCb, (int)bias[q][i]);
             }
-            if (!(minP + minCb + gapExtend > -gapOpen)) {     // (also without pairs: the device checks every query it is given)
+            if (gapOpen <= gapExtend || !(minP + minCb + gapExtend > -gapOpen)) {     // (also without pairs: the device checks every query it is given)
                 hostQuery[q] = 1;
                 nHost++;
                 if (!ids[q].empty()) nHostPairs += ids[q].size();

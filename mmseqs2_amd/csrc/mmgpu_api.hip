@@ -659,10 +659,14 @@ int SwPrepare::check_params() {
     if (!c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_sw_prepare: no targets loaded");
     if (par->alphabet != c->db.alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: alphabet differs from the loaded targets");
     if (mode != MMGPU_SW_SCORE_END && mode != MMGPU_SW_START && mode != MMGPU_SW_START_NOT_WORD) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: unknown mode");
-    if (par->gap_open < par->gap_extend || par->gap_extend < 0 || par->gap_open > 32767)
-        return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: need 0 <= gap_extend <= gap_open");
-    // The cell-by-cell recurrence equals the reference's striped lazy-F result only if opening a gap right after
-    // a gap in the other direction never beats a substitution (StripedSmithWaterman.cpp:205): checked per query in copy_query
+    if (par->gap_extend < 0 || par->gap_open < 0 || par->gap_open > 32767)
+        return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: need 0 <= gap_extend and 0 <= gap_open <= 32767");
+    // The acceptance rule (include/mmgpu.h mmgpu_sw_params, oracle/sw_oracle.c): the cell-by-cell recurrence equals the
+    // reference's striped lazy-F result only if  gap_open > gap_extend >= 0  and  min(P) + min(comp_bias) + gap_extend > -gap_open.
+    // The reference itself runs outside it (with other numbers), so such a batch is UNSUPPORTED, not a bad argument: the host
+    // falls back to its own aligner.  The second half is checked per query in copy_query.
+    if (par->gap_open <= par->gap_extend)
+        return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: gap_open <= gap_extend (the reference's int16 pass is not the plain recurrence there)");
     for (int i = 0; i < par->alphabet * par->alphabet; i++) minp = std::min<int>(minp, par->mat[i]);
     return MMGPU_OK;
 }

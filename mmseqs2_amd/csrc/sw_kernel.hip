@@ -740,7 +740,13 @@ hipError_t launch_sw_from_pf(const SwFromPfArgs &A, uint32_t nq, hipStream_t str
     if (nq == 0) return hipSuccess;
     uint32_t np2 = 1;
     while (np2 < A.stride) np2 <<= 1;
-    hipLaunchKernelGGL(sw_from_pf_kernel, dim3(nq), dim3(256), (size_t)np2 * sizeof(uint32_t), stream, A);
+    const size_t lds = (size_t)np2 * sizeof(uint32_t);
+    if (lds > 65536) return hipErrorInvalidValue;      // (unreachable after the stride check; the kernel's LDS array must never be short)
+    // strides 8193 - 16384 ask for the full 64 KB: say so to the runtime instead of relying on its default ceiling
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(sw_from_pf_kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(sw_from_pf_kernel, dim3(nq), dim3(256), lds, stream, A);
     return hipGetLastError();
 }
 

@@ -105,6 +105,11 @@ int mmgpu_sw_prepare(mmgpu_ctx *c, const mmgpu_sw_params *p, const mmgpu_sw_quer
     b->mode = mode;
     // the device library's precondition (mmgpu_api.hip, sw_prepare_impl): outside it the textbook recurrence the kernels
     // compute is not the reference's striped loop; the stand-in refuses the same batches so that the host side is tested for it
+    // the acceptance rule: gap_open > gap_extend >= 0 and min(P) + min(comp_bias) + gap_extend > -gap_open
+    if (p->gap_open <= p->gap_extend) {
+        delete b;
+        return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: gap_open <= gap_extend (the reference's int16 pass is not the plain recurrence there)");
+    }
     int minp = 0;
     for (int i = 0; i < p->alphabet * p->alphabet; i++) minp = std::min<int>(minp, p->mat[i]);
     for (uint32_t i = 0; i < nq; i++) {
