@@ -73,6 +73,15 @@ __device__ __forceinline__ unsigned from_lane_above(unsigned head, unsigned v) {
     return __builtin_amdgcn_update_dpp(head, v, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
 }
 
+// Build knob for A/B measurements (no test builds with 0; the default is what the suite and the bench run):
+// MMGPU_SW_PREFETCH=0 fetches the profile rows in the column that uses them, as before the prefetch.
+#ifndef MMGPU_SW_PREFETCH
+#define MMGPU_SW_PREFETCH 1
+#endif
+// Empty asm that takes a value in and out of a VGPR: the instruction producing it has to stand where the source has it.
+// Used on the E update (and the multi-tile bodies' column maximum) in phase 2 of the column loop - see there.
+#define SW_KEEP_IN_ROW(x) asm volatile("" : "+v"(x))
+
 __host__ __device__ constexpr int lane_stride_bytes(int R) {
     // R*2 bytes of scores per lane, rounded up to an odd number of 16-byte slots (bank spread)
     int slots = (R * 2 + 15) / 16;
@@ -125,7 +134,8 @@ constexpr int SW_REV_JOB_HITS = 1024;   // most hits a reverse-scan job may hold
 static_assert(SW_REV_JOB_HITS == SW_REV_JOB_MAX, "host and kernel disagree on the reverse job size");
 constexpr int SW_LDS_HEADER = SW_REV_JOB_HITS * 2 + 64;
 
-template <int R, bool MULTI, bool REV>
+// PF: the profile rows of a column are fetched one column ahead (see the column loop)
+template <int R, bool MULTI, bool REV, bool PF>
 __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
     using T = Tile<R>;
     // dynamic LDS: a 1 KB header (job-local scheduling state, below) followed by the query profile of the tile
@@ -282,9 +292,8 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             unsigned vmax = 0, bestcol = 0xFFFFFFFFu;
             unsigned rev_rowA = 0, rev_rowB = 0;   // REV: first row holding the forward score in the column that reached it
             unsigned Hup_prev = 0;
-            unsigned out_H = 0, out_F = 0, out_let = pad_letter * 0x101u;
+            unsigned out_H = 0, out_F = 0;
 
-            unsigned la0 = 0, lb0 = 0;
             // Four columns' letters per dword load (every lane of the group loads the same word).  Forward: targets
             // start 4-byte aligned and the residue buffer ends with max_len + 64 bytes of slack (mmgpu_load_targets), so
             // no clamping is needed: columns past a target's end are replaced by the padding letter below.  Reverse:
@@ -317,40 +326,14 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                 for (int k = 0; k < UPD; ++k) up[k] = scr_in[min(k, last)];
             }
 
-            // blocks of four columns (one dword of letters per target) where the dword path is used, else one block
-            for (int s0 = 0; s0 < nsteps; s0 += 4) {
-            const int jn = min(4, nsteps - s0);
-#pragma nounroll
-            for (int j = 0; j < jn; ++j) {
-                const int s = s0 + j;
-                // ---- inputs of this step: from the lane above, or the tile boundary for the head lane ----
-                {
-                    const unsigned sh = (unsigned)(REV ? 3 - j : j) * 8u;   // wave-uniform
-                    la0 = __builtin_amdgcn_ubfe(wA, sh, 8u);
-                    lb0 = __builtin_amdgcn_ubfe(wB, sh, 8u);
-                }
-                const unsigned head_let = (s < colsA ? la0 : pad_letter) | ((s < colsB ? lb0 : pad_letter) << 8);
-                const unsigned Hup = from_lane_above(up[0].x, out_H);
-                unsigned f = from_lane_above(up[0].y, out_F);
-                const unsigned let = from_lane_above(head_let, out_let);
-                if (has_above) {
-#pragma unroll
-                    for (int k = 0; k + 1 < UPD; ++k) up[k] = up[k + 1];
-                    int c = s + UPD; if (c > ncols - 1) c = ncols - 1; if (c < 0) c = 0;
-                    up[UPD - 1] = scr_in[c];
-                }
-
-                const unsigned a = let & 0xFFu, b = (let >> 8) & 0xFFu;
+            // R scores per target as ND = ceil(R / 2) packed dwords (odd R: the high half of the last one is row padding
+            // nobody selects): ds_read_b128 for whole 16-byte slots, b64 / b32 for the tail
+            constexpr int ND = (R + 1) / 2;
+            unsigned pav_next[PF ? ND : 1], pbv_next[PF ? ND : 1];   // PF: the rows fetched for the next step
+            auto load_rows = [&](unsigned letters, unsigned *pav, unsigned *pbv) {
+                const unsigned a = letters & 0xFFu, b = (letters >> 8) & 0xFFu;
                 const uint4 *rowA = reinterpret_cast<const uint4 *>(lds + a * T::ROW_STRIDE + g * T::LANE_STRIDE);
                 const uint4 *rowB = reinterpret_cast<const uint4 *>(lds + b * T::ROW_STRIDE + g * T::LANE_STRIDE);
-
-                unsigned hd = Hup_prev;
-                Hup_prev = Hup;
-                unsigned cmax = 0;
-                // R scores per target as ND = ceil(R / 2) packed dwords (odd R: the high half of the last one is row padding
-                // nobody selects): ds_read_b128 for whole 16-byte slots, b64 / b32 for the tail
-                constexpr int ND = (R + 1) / 2;
-                unsigned pav[ND], pbv[ND];
 #pragma unroll
                 for (int k = 0; k < ND / 4; ++k) {
                     const uint4 pa = rowA[k], pb = rowB[k];
@@ -367,13 +350,83 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                     pav[ND - 1] = reinterpret_cast<const unsigned *>(rowA)[ND - 1];
                     pbv[ND - 1] = reinterpret_cast<const unsigned *>(rowB)[ND - 1];
                 }
+            };
+            // PF: the profile rows of a column are fetched one column ahead.  The letters lane g needs in step s + 1 are the
+            // letters lane g - 1 holds in step s (the head lane's come from the letter words), so the hand-off of step s + 1
+            // and its ds_reads are issued in step s, behind the last use of the rows of step s (phase 1) and in front of the
+            // serial chain (phase 2): the LDS round trip is covered by the wavefront's own instructions instead of standing
+            // at the top of every column.  `let` / pav / pbv are carried from step to step; the prologue fetches column 0.
+            // The step after the last one fetches the padding letter's row (s + 1 >= cols), which every tile has: nothing
+            // is read past the profile.  The rows stay in the same registers (the reads stand behind their last use), but
+            // the compiler moves some reads up, which costs 6 - 24 registers per kernel.
+            unsigned let = pad_letter * 0x101u;   // what a lane holds before its first column
+            auto head_letters = [&](int c, int j) -> unsigned {   // column c of the head lane: byte j of the current letter words
+                const unsigned sh = (unsigned)(REV ? 3 - j : j) * 8u;   // wave-uniform
+                const unsigned la0 = __builtin_amdgcn_ubfe(wA, sh, 8u);
+                const unsigned lb0 = __builtin_amdgcn_ubfe(wB, sh, 8u);
+                return (c < colsA ? la0 : pad_letter) | ((c < colsB ? lb0 : pad_letter) << 8);
+            };
+            if (PF) {
+                let = from_lane_above(head_letters(0, 0), let);
+                load_rows(let, pav_next, pbv_next);
+            }
+
+            // blocks of four steps, one dword of letters per target and block.  PF: step s hands on the letters of column
+            // s + 1, so a block is the steps 4k - 1 .. 4k + 2 (the first one the steps 0 .. 2).
+            // Invariant: in block s0 = 4k - 1 (PF) / 4k (not PF), wA / wB hold the k-th letter word, and step j of the block
+            // fetches column 4k + j = byte j of it (reverse: byte 3 - j).
+            for (int s0 = PF ? -1 : 0; s0 < nsteps; s0 += 4) {
+            const int jn = min(4, nsteps - s0);
+#pragma nounroll
+            for (int j = PF && s0 < 0 ? 1 : 0; j < jn; ++j) {
+                const int s = s0 + j;
+                // ---- inputs of this step: from the lane above, or the tile boundary for the head lane ----
+                unsigned head_let = 0;
+                if (!PF) head_let = head_letters(s, j);
+                const unsigned Hup = from_lane_above(up[0].x, out_H);
+                unsigned f = from_lane_above(up[0].y, out_F);
+                if (!PF) let = from_lane_above(head_let, let);
+                if (has_above) {
+#pragma unroll
+                    for (int k = 0; k + 1 < UPD; ++k) up[k] = up[k + 1];
+                    int c = s + UPD; if (c > ncols - 1) c = ncols - 1; if (c < 0) c = 0;
+                    up[UPD - 1] = scr_in[c];
+                }
+                unsigned pav[ND], pbv[ND];
+                if (PF) {
+#pragma unroll
+                    for (int k = 0; k < ND; ++k) { pav[k] = pav_next[k]; pbv[k] = pbv_next[k]; }
+                } else {
+                    load_rows(let, pav, pbv);
+                }
+
+                unsigned hd = Hup_prev;
+                Hup_prev = Hup;
+                unsigned cmax = 0;
                 // Phase 1 (no dependencies between rows): everything that only needs the previous column -
                 // diagonal + score, max with E, and E - ge.  Phase 2 is the serial F chain down the strip
                 // (max -> sub -> max per row) with the off-chain ops of the row (f - ge, column maximum, E
                 // update) available to sit behind each dependent VOP3P op.  Compared with the single-loop form
                 // the compiler needs 23 fewer register moves and 10 fewer wait states per column at R = 24
-                // (346 -> 313 instructions); pinning the order with sched_barrier / asm anchors was tried and
-                // costs more wait states than it saves.
+                // (346 -> 313 instructions).
+                //
+                // A packed op that reads the result of the packed op right in front of it costs a wait state (s_nop).  A row
+                // of phase 2 is six ops, three of them the chain h -> t -> f'; with the other three between the links
+                // (h, f - ge, t, cmax, f', E[r]) no op reads its predecessor.  Left alone, the compiler sinks all R updates of
+                // E (in the multi-tile bodies the cmax chain too) out of the rows, past the `nm != vmax` branch (past the
+                // boundary store), into a block of their own: five ops per row and a wait state in each, 1.75 R + 2 per
+                // column, one issue slot in seven.  SW_KEEP_IN_ROW is an EMPTY asm on the value: it emits nothing (so the
+                // hazard recognizer still sees real neighbours), but the update has to be done where the row is.  What was
+                // tried and does not work on this toolchain: an asm per op or two-operand asms that chain the ops (the
+                // recognizer pads around every asm boundary: 44 -> 73 and -> 97 wait states at R = 24),
+                // __builtin_amdgcn_sched_barrier after each row (no effect: the sinking happens before scheduling), taking
+                // `nm` in front of the boundary store instead of the anchor on cmax (49 instead of 2).  If a later compiler
+                // stops honouring the anchor (tests/test_sw_isa_audit.py notices), the structural alternatives are: rotate
+                // the body so that the `nm != vmax` bookkeeping of column s runs at the top of step s + 1 (Hp[] and col are
+                // still there; the tail of the step is then straight-line code with no join block to sink into), or fold
+                // the E update into the chain's data flow.
+                // The schedule is sensitive to the shape of the source around it: with pav / pbv declared outside the column
+                // loop the multi-tile bodies get a wait state per row back (scripts/sw_isa_audit.py after every change here).
                 unsigned pre[R], es[R];
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
@@ -385,19 +438,24 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                     pre[r] = pk_max_s(pk_add_sat(r == 0 ? hd : Hp[r - 1], P), E[r]);
                     es[r] = pk_sub_sat_u(E[r], ge2);
                 }
+                if (PF) {   // the next column's letters and profile rows
+                    let = from_lane_above(head_letters(s + 1, j), let);
+                    load_rows(let, pav_next, pbv_next);
+                }
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const unsigned h = pk_max_s(pre[r], f);
                     const unsigned fs = pk_sub_sat_u(f, ge2);
                     const unsigned t = pk_sub_sat_u(h, go2);
                     cmax = pk_max_u(cmax, h);
+                    if (MULTI) SW_KEEP_IN_ROW(cmax);
                     f = pk_max_u(fs, t);
                     E[r] = pk_max_u(es[r], t);
+                    SW_KEEP_IN_ROW(E[r]);
                     Hp[r] = h;
                 }
                 out_H = Hp[R - 1];
                 out_F = f;
-                out_let = let;
 
                 const int col = s - g;
                 if (has_below && g == GROUP - 1 && col >= 0 && col < ncols) scr_out[col] = make_uint2(out_H, out_F);
@@ -435,7 +493,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             }
             {   // the next four columns' letters; the load after that is in flight for four steps
                 wA = wA_next; wB = wB_next;
-                const int k = (s0 >> 2) + 2;
+                const int k = ((s0 + (PF ? 1 : 0)) >> 2) + 2;
                 wA_next = letters4(pA, endA, k); wB_next = letters4(pB, endB, k);
             }
             }
@@ -515,12 +573,16 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
 template <int R, bool MULTI, bool BOTH>
 __device__ __forceinline__ void sw_passes(const SwLaunch &L, const SwJob &job) {
     if constexpr (R <= SW_MAX_R) {
-        if (!(BOTH && L.rev_only)) sw_body<R, MULTI, false>(L, job);
+        // the prefetch goes where it costs no wavefront and no wait states: not into the forward-only kernel of R = 25 .. 28
+        // (183 registers, two wavefronts instead of three) and not into the multi-tile bodies (with it the compiler puts a
+        // wait state into every row of phase 2 again, profiles/sw_isa_audit.txt)
+        constexpr bool PF = MMGPU_SW_PREFETCH && !MULTI && (BOTH || R <= 24);
+        if (!(BOTH && L.rev_only)) sw_body<R, MULTI, false, PF>(L, job);
         // multi-tile queries get their reverse scan from sw_rev_multi_kernel (below), per query instead of per job
         if constexpr (BOTH && !MULTI) {
             __threadfence_block();   // the forward results of this job, written by other waves of the workgroup
             __syncthreads();
-            sw_body<R, MULTI, true>(L, job);
+            sw_body<R, MULTI, true, PF>(L, job);
         }
     }
 }
@@ -551,7 +613,12 @@ __global__ __launch_bounds__(WAVES * 64)
 __attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_SW_WAVES_G0F)
                                            : (G == 1 ? (BOTH ? MMGPU_SW_WAVES_G1B : MMGPU_SW_WAVES_G1F) : SW_MIN_WAVES),
                                    // upper bound: the forward + reverse kernel of the middle group is at the edge of a third wavefront per
-                                   // SIMD (168 - 170 registers) and runs slower with it (83.4 against 78.7 ms for the stage, round 6) - pinned
+                                   // SIMD (168 - 170 registers) and runs slower with it (83.4 against 78.7 ms for the stage, round 6) - pinned.
+                                   // Re-measured with the wait states out of phase 2 and the rows fetched a column ahead (183 registers at
+                                   // two wavefronts): 75.41 ms for the stage at 2, 74.57 ms at 3 (profiles/sw_column_loop_bench.txt) - but at 3
+                                   // the compiler fits 168 registers only with 44 bytes of scratch per lane (spills around, not inside, the
+                                   // column loops).  Kept at 2: no kernel of this file uses scratch (tests/test_sw_isa_audit.py); the 0.8 ms
+                                   // are there for whoever gets this kernel to 168 registers without spilling.
                                    G == 1 && BOTH ? MMGPU_SW_WAVES_G1B : 8))) void sw_kernel(SwLaunch L) {
     SwJob job = L.jobs[blockIdx.x];
     if (L.q_hit_count) {   // fused prefilter -> align hand-over: the list length of the query is only known on the device
@@ -639,7 +706,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(SW_M
     }
     __syncthreads();
     job.shape = (job.shape & 0xFFu) | (scratch_slot << 8);
-#define MMGPU_SW_REV(R) case 32 + (R) - 1: if constexpr ((R) <= SW_MAX_R) sw_body<R, true, true>(L, job); break;
+#define MMGPU_SW_REV(R) case 32 + (R) - 1: if constexpr ((R) <= SW_MAX_R) sw_body<R, true, true, false>(L, job); break;
     switch (job.shape & 0xFFu) {
         MMGPU_SW_REV(8) MMGPU_SW_REV(9) MMGPU_SW_REV(10) MMGPU_SW_REV(11) MMGPU_SW_REV(12) MMGPU_SW_REV(13) MMGPU_SW_REV(14) MMGPU_SW_REV(15)
         MMGPU_SW_REV(16) MMGPU_SW_REV(17) MMGPU_SW_REV(18) MMGPU_SW_REV(19) MMGPU_SW_REV(20) MMGPU_SW_REV(21) MMGPU_SW_REV(22) MMGPU_SW_REV(23)
