@@ -4,8 +4,9 @@
 // reference's arrays kept literally) serves the bands this one declines.
 //
 // The reference walks a row of the band cell by cell because F chains along the row: f[j] = max(H[j-1] - go, f[j-1] - ge).
-// Two restatements make a row data-parallel (both checked against the oracle's literal restatement over 800 random
-// alignments incl. wide and clipped bands, scripts/bt_formulation_check.py, and by the GPU parity tests):
+// Two restatements make a row data-parallel (both checked against the oracle's literal restatement at every setting of
+// tests/sw_param_cases.py - 6/5 and 10/9 included - by tests/test_bt_formulation.py on the model oracle/bt_rows.py, and on
+// the device by tests/test_bt_gpu.py: band classes, doublings, ties on chunk boundaries):
 //   * F from "H without its F term": with Hnf = max(max(E,0), diagonal), f[j] = max(Hnf[j-1] - go, f[j-1] - ge) has the
 //     same value AND the same tie flag (temp1 > temp2, :1551-1557) as the reference's expression on the full H, because
 //     gap_open >= gap_extend and Hnf >= 0.  f is then a max-plus prefix scan: f[l] = max(P[l] - (l-1) ge, f_in - l ge) with
@@ -14,7 +15,8 @@
 //     indexed by the target column; what the frame arrays' zeroed slots (h_b[0], h_b[edge], :1528) amount to is spelled out:
 //     columns outside the previous row's band read 0, and the previous-row H / E seen at the LAST column of row i are 0
 //     when i <= band + 1 or the band is not clipped by the target end (`zero_last`; in the clipped rows with i <= band + 1
-//     this destroys a valid cell - the reference's quirk, kept).
+//     this destroys a valid cell - the reference's quirk, kept; it only lowers E in the last target column, which no
+//     backtrace string can show: tests/test_bt_formulation.py says why).
 // Lanes = 64 consecutive columns of the row (wider bands: chunks with carries), rows in sequence; per row-chunk: three LDS
 // reads, a 6-step DPP scan, two wave shifts, the direction byte.  The band is doubled until the banded maximum reaches the
 // Smith-Waterman score like the reference does; the passes that search for the band run without direction storage, the

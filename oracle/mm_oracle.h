@@ -33,6 +33,13 @@ float mmo_sw_cov(unsigned int start, unsigned int end, unsigned int len);
 int mmo_sw_banded_backtrace(const uint8_t *t, const uint8_t *q, const int8_t *comp_bias, int tlen, int qlen,
                             int score, int gap_open, int gap_extend, const int8_t *mat, int alphabet, char *bt,
                             int bt_cap);
+/* the two entry points above/below with the final half-width of the band as an out-parameter (may be NULL) */
+int mmo_sw_banded_backtrace_band(const uint8_t *t, const uint8_t *q, const int8_t *comp_bias, int tlen, int qlen,
+                                 int score, int gap_open, int gap_extend, const int8_t *mat, int alphabet, char *bt,
+                                 int bt_cap, int *final_band);
+int mmo_sw_align_band(const uint8_t *q, int qlen, const int8_t *comp_bias, const uint8_t *t, int tlen,
+                      const int8_t *mat, int alphabet, int gap_open, int gap_extend, int need_start, int need_bt,
+                      mmo_sw_res *r, char *bt, int bt_cap, int *final_band);
 int mmo_sw_align(const uint8_t *q, int qlen, const int8_t *comp_bias, const uint8_t *t, int tlen,
                  const int8_t *mat, int alphabet, int gap_open, int gap_extend, int need_start, int need_bt,
                  mmo_sw_res *r, char *bt, int bt_cap);

@@ -46,6 +46,7 @@ class Oracle:
             build_oracle()
         L = self.L = ctypes.CDLL(ORACLE_SO)
         L.mmo_sw_align.restype = ctypes.c_int
+        L.mmo_sw_align_band.restype = ctypes.c_int
         L.mmo_sw_bias.restype = ctypes.c_int
         L.mmo_sw_check_params.restype = ctypes.c_int
         L.mmo_sw_score_identical.restype = ctypes.c_int
@@ -77,12 +78,16 @@ class Oracle:
         r = SwRes()
         cap = len(q) + len(t) + 8
         bt = ctypes.create_string_buffer(cap)
-        rc = self.L.mmo_sw_align(_ptr(q), len(q), _ptr(cbp), _ptr(t), len(t), _ptr(mat), mat.shape[0], go, ge,
-                                 int(need_start), int(need_bt), ctypes.byref(r), bt, cap)
+        band = ctypes.c_int(0)
+        rc = self.L.mmo_sw_align_band(_ptr(q), len(q), _ptr(cbp), _ptr(t), len(t), _ptr(mat), mat.shape[0], go, ge,
+                                      int(need_start), int(need_bt), ctypes.byref(r), bt, cap, ctypes.byref(band))
         if rc != 0:
             raise RuntimeError("mmo_sw_align rc=%d" % rc)
-        return dict(score=r.score, q_start=r.q_start, q_end=r.q_end, t_start=r.t_start, t_end=r.t_end,
-                    word=r.word, ident=r.ident, bt=bt.value.decode() if r.bt_len else "")
+        out = dict(score=r.score, q_start=r.q_start, q_end=r.q_end, t_start=r.t_start, t_end=r.t_end,
+                   word=r.word, ident=r.ident, bt=bt.value.decode() if r.bt_len else "")
+        if need_bt:
+            out["band"] = band.value     # final half-width of the banded backtrace; 0 where none was run
+        return out
 
     def block_growth(self, call, cap=4096):
         """runs call() (block_backtrace / sw_block_backtrace_profile / block_align ...) with the block-list capture armed and returns

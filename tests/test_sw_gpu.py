@@ -301,14 +301,24 @@ def test_very_long_query_and_target(gpu, oracle, matrices):
                 assert (int(g["q_start"]), int(g["t_start"])) == (r["q_start"], r["t_start"]), (qi, k)
     pick = np.array([0 * len(tl) + 6, 1 * len(tl) + 6, 2 * len(tl) + 3, 2 * len(tl) + 6], np.uint32)
     info, strs = b.traceback(pick)
+    from tests.bt_cases import classify, required_status
+    n_compared = 0
     for k, p in enumerate(pick.tolist()):
         qi, ti = divmod(p, len(tl))
         if out[qi, ti]["score"] < 40:
             continue
         r = oracle.sw_align(queries[qi]["q"], queries[qi]["comp_bias"], tl[ti], mat, GO, GE, need_start=True, need_bt=True)
-        assert int(info[k]["status"]) in (0, 1), (k, int(info[k]["status"]))
-        if int(info[k]["status"]) == 0:
-            assert strs[k] == r["bt"] and int(info[k]["ident"]) == r["ident"], k
+        # the status each pair must have follows from its rows and final band and the tier limits (tests/bt_cases.py)
+        cl = classify(r)
+        want = required_status(cl["rows"], cl["band"])
+        print("pair %d: rows %d, final band %d -> status %s" % (p, cl["rows"], cl["band"], want))
+        assert want is not None and int(info[k]["status"]) == want, (k, int(info[k]["status"]), want, cl)
+        n_compared += 1
+        if want == 0:
+            assert strs[k] == r["bt"] and int(info[k]["ident"]) == r["ident"] and int(info[k]["bt_len"]) == len(r["bt"]), k
+        else:
+            assert strs[k] == "" and int(info[k]["bt_len"]) == 0, k
+    assert n_compared >= 3
     b.free()
 
 
