@@ -164,25 +164,17 @@ extern "C" int mmgpu_load_targets(mmgpu_ctx *c, const uint8_t *residues, const u
     // padding behind the last.  The device buffer is filled with the pad code, then the targets travel in chunks: the host threads
     // pack chunk j + 1 into one of two pinned staging buffers while the copy engine moves chunk j (a pageable 280 MB buffer packed
     // first and copied then cost 0.14 s for the 1 M targets of configs[2], 2 GB/s).
-    DeviceDb db;
-    uint8_t *stage[2] = {nullptr, nullptr};
-    hipEvent_t moved[2] = {nullptr, nullptr};
-    hipStream_t up = nullptr;
-    auto drop = [&]() {
-        for (int k = 0; k < 2; k++) {
-            if (stage[k]) (void)hipHostFree(stage[k]);
-            if (moved[k]) (void)hipEventDestroy(moved[k]);
-        }
-        if (up) (void)hipStreamDestroy(up);
-    };
-#define DB_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { drop(); free_db(db); return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
-    DB_TRY(dev_malloc_ctx(c, (void **)&db.res, bytes));
-    DB_TRY(dev_malloc_ctx(c, (void **)&db.off4, off4.size() * sizeof(uint32_t)));
-    DB_TRY(dev_malloc_ctx(c, (void **)&db.len, len.size() * sizeof(uint32_t)));
-    DB_TRY(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
-    DB_TRY(hipMemsetAsync(db.res, alphabet, bytes, up));
-    DB_TRY(hipMemcpyAsync(db.off4, off4.data(), off4.size() * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-    DB_TRY(hipMemcpyAsync(db.len, len.data(), len.size() * sizeof(uint32_t), hipMemcpyHostToDevice, up));
+    DbBuild nb;
+    UploadRing ring;      // (after nb: the stream has drained before a failure frees the buffers it copies into)
+    DeviceDb &db = nb.db;
+    HIP_TRY(dev_malloc_ctx(c, (void **)&db.res, bytes));
+    HIP_TRY(dev_malloc_ctx(c, (void **)&db.off4, off4.size() * sizeof(uint32_t)));
+    HIP_TRY(dev_malloc_ctx(c, (void **)&db.len, len.size() * sizeof(uint32_t)));
+    HIP_TRY(ring.open(2));
+    hipStream_t up = ring.up.s;
+    HIP_TRY(hipMemsetAsync(db.res, alphabet, bytes, up));
+    HIP_TRY(hipMemcpyAsync(db.off4, off4.data(), off4.size() * sizeof(uint32_t), hipMemcpyHostToDevice, up));
+    HIP_TRY(hipMemcpyAsync(db.len, len.data(), len.size() * sizeof(uint32_t), hipMemcpyHostToDevice, up));
     const size_t chunk_bytes = (size_t)std::min<uint64_t>(32ull << 20, std::max<uint64_t>((uint64_t)(cur4 - 16) * 4, 4096));
     std::atomic<bool> bad_res(false);
     for (uint32_t first = 0, j = 0; first < n; j++) {
@@ -199,14 +191,10 @@ extern "C" int mmgpu_load_targets(mmgpu_ctx *c, const uint8_t *residues, const u
             last = lo;
         }
         const uint64_t end = last < n ? (uint64_t)off4[last] * 4 : (uint64_t)cur4 * 4;
-        const int k = (int)(j & 1);
-        if (!stage[k]) {
-            DB_TRY(hipHostMalloc((void **)&stage[k], chunk_bytes + 65536 + 64, hipHostMallocDefault));
-            DB_TRY(hipEventCreateWithFlags(&moved[k], hipEventDisableTiming));
-        } else {
-            DB_TRY(hipEventSynchronize(moved[k]));      // the copy out of this buffer two chunks ago
-        }
-        uint8_t *dst = stage[k];
+        const size_t k = j & 1;
+        if (!ring.slots[k].p) HIP_TRY(ring.slots[k].reserve(chunk_bytes + 65536 + 64));
+        else HIP_TRY(ring.wait(k));      // the copy out of this buffer two chunks ago
+        uint8_t *dst = ring.slots[k].p;
         parallel_for((size_t)(last - first), [&, first, base, dst](size_t a, size_t b) {
             for (size_t i = first + a; i < first + b; i++) {
                 const uint8_t *src = residues + offsets[i];
@@ -219,20 +207,18 @@ extern "C" int mmgpu_load_targets(mmgpu_ctx *c, const uint8_t *residues, const u
                 for (uint32_t x = l; x < ((l + 3) & ~3u); x++) out[x] = (uint8_t)alphabet;
             }
         });
-        DB_TRY(hipMemcpyAsync(db.res + base, dst, end - base, hipMemcpyHostToDevice, up));
-        DB_TRY(hipEventRecord(moved[k], up));
+        HIP_TRY(hipMemcpyAsync(db.res + base, dst, end - base, hipMemcpyHostToDevice, up));
+        HIP_TRY(ring.sent(k));
         first = last;
     }
-    DB_TRY(hipStreamSynchronize(up));
-#undef DB_TRY
-    drop();
-    if (bad_res) { free_db(db); return fail(MMGPU_ERR_ARG, "mmgpu_load_targets: residue code >= alphabet"); }
+    HIP_TRY(hipStreamSynchronize(up));
+    if (bad_res) return fail(MMGPU_ERR_ARG, "mmgpu_load_targets: residue code >= alphabet");
     db.n = n;
     db.res_bytes = bytes;
     db.max_len = max_len;
     db.total_residues = total;
     db.alphabet = alphabet;
-    c->db = db;
+    c->db = nb.take_db();
     c->h_len.assign(len.begin(), len.begin() + n);
     uint64_t res_total = 0;
     for (uint32_t i = 0; i < n; i++) res_total += len[i];
@@ -1438,193 +1424,227 @@ extern "C" int mmgpu_sw_batch(mmgpu_ctx *c, const mmgpu_sw_params *par, const mm
 // ---------------------------------------------------------------------------------------------------------
 // backtrace
 // ---------------------------------------------------------------------------------------------------------
+// host copies of the results (and, for device-resident lists, of the slot -> target map): fetched once per run of the batch
+static int sw_host_results(mmgpu_sw_batch_t *b, hipStream_t s) {
+    if (b->h_res_valid) return MMGPU_OK;
+    b->h_res.resize((size_t)b->pairs);
+    if (b->pairs) HIP_TRY(hipMemcpyAsync(b->h_res.data(), b->d_out.p, (size_t)b->pairs * sizeof(mmgpu_sw_hit), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (b->from_pf) {
+        b->h_slot_target.resize((size_t)b->pairs);
+        if (b->pairs) HIP_TRY(hipMemcpy(b->h_slot_target.data(), b->d_slot_target.p, (size_t)b->pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    b->h_res_valid = true;
+    return MMGPU_OK;
+}
+
 // ---- a15: the block aligner's start position / backtrace for int16-range hits (block_kernel.hip) ----
 struct BlockAuto { uint32_t selected = 0, ok = 0, declined = 0, too_large = 0; };      // mmgpu_sw_block_starts: what the device selected / answered
 
-static int block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pair_index, uint32_t n, mmgpu_sw_block *out,
-                           char *bt, size_t bt_cap, size_t *bt_used, uint32_t *growth, uint32_t growth_cap, BlockAuto *au = nullptr) {
-    if (!c || !b || (!au && ((!pair_index && n) || (!out && n)))) return fail(MMGPU_ERR_ARG, "mmgpu_sw_block_backtrace: NULL argument");
-    if (!b->ran) return fail(MMGPU_ERR_STATE, "mmgpu_sw_block_backtrace: batch was never run");
-    if (b->alphabet > 26) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_block_backtrace: alphabet above 26 letters");
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (b->mode < MMGPU_SW_START && !b->from_pf && b->h_out_target.empty())
-        return fail(MMGPU_ERR_STATE, "mmgpu_sw_block_backtrace: the batch keeps no slot -> target map (prepare it with MMGPU_SW_START)");
-    static const bool trace_on = getenv("MMGPU_TRACE") != nullptr;
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_mark = now_s();
-    auto lap = [&](const char *what) {
-        if (!trace_on) return;
-        const double t = now_s();
-        fprintf(stderr, "[mmgpu block aligner] %s %.3f s\n", what, t - t_mark);
-        t_mark = t;
-    };
-    std::vector<BlockJob> jobs;
-    std::vector<uint64_t> bt_off;
-    uint64_t off = 0, longest = 0;
-    DevBuf d_out, d_sel_jobs, d_sel_pairs, d_sel_cnt, d_flags;
-    for (DevBuf *d : {&d_out, &d_sel_jobs, &d_sel_pairs, &d_sel_cnt, &d_flags}) d->bind(c->cache);
+namespace {
+
+// what an entry point wants of block_backtrace
+struct BlockWant {
+    BlockAuto *select = nullptr;    // mmgpu_sw_block_starts: the device picks the pairs, their answers go into the batch's records
+    bool starts_only = false;       // start positions only: no trace, no walk
+    bool no_strings = false;        // start positions / identities / lengths only (implied by starts_only)
+    uint32_t *growth = nullptr;     // mmgpu_sw_block_growth: the block lists
+    uint32_t growth_cap = 0;
+};
+
+// One call of block_backtrace: its arguments and what its steps hand to one another.  The steps run in the order they are declared
+// in.  Three tiers of block_kernel.hip (tier_rounds) take what the four-pairs-per-wavefront kernels of block4_kernel.hip
+// (block4_passes: sequence queries) leave; every launch answers MMGPU_BLOCK_TOO_LARGE for a pair it hands on.
+struct BlockRun {
+    mmgpu_ctx *c;
+    mmgpu_sw_batch_t *b;
+    const uint32_t *pair_index;
+    uint32_t n;                      // pairs asked for; with BlockWant::select: pairs the device selected
+    mmgpu_sw_block *out;             // [n] host copy of the answers (select: in the pinned arena, or out_auto)
+    char *bt;
+    BlockWant want;
+    hipStream_t s;                   // the context's stream
+
+    std::vector<BlockJob> jobs;      // int16-range pairs, longest first once ordered
+    std::vector<BlockJob> slow_jobs; // what block4_passes leaves: profile queries, pairs whose slot would not fit the pool
+    std::vector<uint64_t> bt_off;    // [n] where a pair's string goes (multiples of four)
+    uint64_t off = 0;                // ... and their total
     std::vector<mmgpu_sw_block> out_auto;
-    PinnedLease pinned;      // the context's staging arena, held to the end of the call (`out` may point into it)
-    if (au) {
-        // ---- the device picks the pairs (block_select.hip): int16-range hits that pass the query's start-score threshold ----
-        if (!b->d_qout_off.p) {
-            HIP_TRY(b->d_qout_off.alloc(b->h_qout_off.size() * 4));
-            HIP_TRY(hipMemcpyAsync(b->d_qout_off.p, b->h_qout_off.data(), b->h_qout_off.size() * 4, hipMemcpyHostToDevice, s));
-        }
-        if (!b->from_pf && !b->d_out_target.p) {
-            HIP_TRY(b->d_out_target.alloc(std::max<size_t>(b->h_out_target.size(), 1) * 4));
-            HIP_TRY(hipMemcpyAsync(b->d_out_target.p, b->h_out_target.data(), b->h_out_target.size() * 4, hipMemcpyHostToDevice, s));
-        }
-        HIP_TRY(d_sel_cnt.alloc(32));
-        HIP_TRY(hipMemsetAsync(d_sel_cnt.p, 0, 32, s));
-        BlockSelectArgs A;
-        A.res = b->d_out.as<mmgpu_sw_hit>();
-        A.pairs = (uint32_t)b->pairs;
-        A.qout_off = b->d_qout_off.as<uint32_t>();
-        A.n_queries = (uint32_t)(b->h_qout_off.size() - 1);
-        A.q_minstart = b->d_qminstart.as<int32_t>();
-        A.slot_target = b->from_pf ? b->d_slot_target.as<uint32_t>() : b->d_out_target.as<uint32_t>();
-        A.jobs = nullptr; A.pair_of_slot = nullptr; A.blk = nullptr;
-        A.count = d_sel_cnt.as<uint32_t>();
-        A.cap = 0;      // first pass: count only
-        HIP_TRY(launch_block_select(A, s));
-        uint32_t cnt = 0;
-        HIP_TRY(hipMemcpyAsync(&cnt, d_sel_cnt.p, 4, hipMemcpyDeviceToHost, s));
+    PinnedLease pinned;              // the context's staging arena, held to the end of the call (`out` may point into it)
+    std::vector<int8_t> scores;
+    std::vector<uint32_t> resume;    // per slot: the first minimum block size still to try (bit 16: only the slot was too small)
+    size_t growth_bytes = 0;
+    const char *first_tier_env = getenv("MMGPU_BLOCK_FIRST_TIER");      // test aid: every pair through block_kernel.hip's tier 0 / 1 / 2
+    BlockLaunch L;
+    DevBuf d_out, d_sel_jobs, d_sel_pairs, d_sel_cnt, d_flags, d_btoff, d_bt, d_scores, d_growth, d_jobs[3], d_pool[3], d_busy[3];
+    struct PassBufs {      // what a block4 launch in flight holds: two of them run side by side (everything else, the long head)
+        DevBuf j2, cnt, pool, ck;
+        hipStream_t st = nullptr;
+        Block4Plan plan;
+    } PB[2];
+    // (the streams last: a return with work in flight on one of them waits for it before the buffers above go back to the cache.
+    // They live to the end of the call - the head's beside the two of tier_rounds, three besides the context's at most - and their
+    // holders wait once more for streams the steps have already drained)
+    SideStream head_stream, extra[2];
+    double t_mark = prep_now();
+
+    BlockRun(mmgpu_ctx *c_, mmgpu_sw_batch_t *b_, const uint32_t *pair_index_, uint32_t n_, mmgpu_sw_block *out_, char *bt_, const BlockWant &w)
+        : c(c_), b(b_), pair_index(pair_index_), n(n_), out(out_), bt(bt_), want(w), s(c_->stream) {
+        for (DevBuf *d : {&d_out, &d_sel_jobs, &d_sel_pairs, &d_sel_cnt, &d_flags, &d_btoff, &d_bt, &d_scores, &d_growth, &d_jobs[0], &d_jobs[1],
+                          &d_jobs[2], &d_pool[0], &d_pool[1], &d_pool[2], &d_busy[0], &d_busy[1], &d_busy[2]})
+            d->bind(c->cache);
+        for (PassBufs &x : PB) { x.j2.bind(c->cache); x.cnt.bind(c->cache); x.pool.bind(c->cache); x.ck.bind(c->cache); }
+    }
+    static bool trace_on() {
+        static const bool on = getenv("MMGPU_TRACE") != nullptr;
+        return on;
+    }
+    void lap(const char *what);
+    int select_jobs();
+    int list_jobs();
+    int score_table();
+    int buffers_and_uploads();
+    int block4_launch(PassBufs &B, const std::vector<BlockJob> &todo, int form, uint64_t per_res, uint64_t margin, uint64_t waves_per_cu,
+                      std::vector<BlockJob> &left);
+    int block4_collect(PassBufs &B, std::vector<BlockJob> &left);
+    int block4_passes();
+    int tier_rounds();
+    int scatter_answers();
+    int download_strings();
+};
+
+void BlockRun::lap(const char *what) {
+    if (!trace_on()) return;
+    const double t = prep_now();
+    fprintf(stderr, "[mmgpu block aligner] %s %.3f s\n", what, t - t_mark);
+    t_mark = t;
+}
+
+// the device picks the pairs (block_select.hip): int16-range hits that pass the query's start-score threshold
+int BlockRun::select_jobs() {
+    if (!b->d_qout_off.p) {
+        HIP_TRY(b->d_qout_off.alloc(b->h_qout_off.size() * 4));
+        HIP_TRY(hipMemcpyAsync(b->d_qout_off.p, b->h_qout_off.data(), b->h_qout_off.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    if (!b->from_pf && !b->d_out_target.p) {
+        HIP_TRY(b->d_out_target.alloc(std::max<size_t>(b->h_out_target.size(), 1) * 4));
+        HIP_TRY(hipMemcpyAsync(b->d_out_target.p, b->h_out_target.data(), b->h_out_target.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(d_sel_cnt.alloc(32));
+    HIP_TRY(hipMemsetAsync(d_sel_cnt.p, 0, 32, s));
+    BlockSelectArgs A;
+    A.res = b->d_out.as<mmgpu_sw_hit>();
+    A.pairs = (uint32_t)b->pairs;
+    A.qout_off = b->d_qout_off.as<uint32_t>();
+    A.n_queries = (uint32_t)(b->h_qout_off.size() - 1);
+    A.q_minstart = b->d_qminstart.as<int32_t>();
+    A.slot_target = b->from_pf ? b->d_slot_target.as<uint32_t>() : b->d_out_target.as<uint32_t>();
+    A.jobs = nullptr; A.pair_of_slot = nullptr; A.blk = nullptr;
+    A.count = d_sel_cnt.as<uint32_t>();
+    A.cap = 0;      // first pass: count only
+    HIP_TRY(launch_block_select(A, s));
+    uint32_t cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, d_sel_cnt.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    n = cnt;
+    want.select->selected = n;
+    if (n == 0) return MMGPU_OK;
+    HIP_TRY(d_sel_jobs.alloc((size_t)n * sizeof(BlockJob)));
+    HIP_TRY(d_sel_pairs.alloc((size_t)n * 4));
+    HIP_TRY(d_out.alloc((size_t)n * sizeof(mmgpu_sw_block)));
+    HIP_TRY(hipMemsetAsync(d_sel_cnt.p, 0, 4, s));
+    A.jobs = d_sel_jobs.as<BlockJob>();
+    A.pair_of_slot = d_sel_pairs.as<uint32_t>();
+    A.blk = d_out.as<mmgpu_sw_block>();
+    A.cap = n;
+    HIP_TRY(launch_block_select(A, s));
+    jobs.resize(n);
+    // the selected jobs come back once and all n answers after every launch (block4_collect): through pinned memory where the
+    // context's staging arena can be had for the length of this call (mmgpu_ctx::pinned; a thread preparing the next batch of
+    // the context meanwhile then uploads from pageable memory, as this call copies to it when that thread holds the arena) -
+    // the copies of pageable memory were ~5 ms of a 45 ms call
+    const size_t out_bytes = (size_t)n * sizeof(mmgpu_sw_block), jobs_bytes = (size_t)n * sizeof(BlockJob);
+    const size_t pin_need = upload_pinned_need(out_bytes) + upload_pinned_need(jobs_bytes);
+    void *pin = pinned.acquire(c, pin_need);
+    if (pin) {
+        BlockJob *pj = reinterpret_cast<BlockJob *>(static_cast<char *>(pin) + upload_pinned_need(out_bytes));
+        HIP_TRY(hipMemcpyAsync(pj, d_sel_jobs.p, jobs_bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        n = cnt;
-        au->selected = n;
-        if (n == 0) return MMGPU_OK;
-        HIP_TRY(d_sel_jobs.alloc((size_t)n * sizeof(BlockJob)));
-        HIP_TRY(d_sel_pairs.alloc((size_t)n * 4));
-        HIP_TRY(d_out.alloc((size_t)n * sizeof(mmgpu_sw_block)));
-        HIP_TRY(hipMemsetAsync(d_sel_cnt.p, 0, 4, s));
-        A.jobs = d_sel_jobs.as<BlockJob>();
-        A.pair_of_slot = d_sel_pairs.as<uint32_t>();
-        A.blk = d_out.as<mmgpu_sw_block>();
-        A.cap = n;
-        HIP_TRY(launch_block_select(A, s));
-        jobs.resize(n);
-        // the selected jobs come back once and all n answers after every launch (block4_collect): through pinned memory where the
-        // context's staging arena can be had for the length of this call (mmgpu_ctx::pinned; a thread preparing the next batch of
-        // the context meanwhile then uploads from pageable memory, as this call copies to it when that thread holds the arena) -
-        // the copies of pageable memory were ~5 ms of a 45 ms call
-        const size_t out_bytes = (size_t)n * sizeof(mmgpu_sw_block), jobs_bytes = (size_t)n * sizeof(BlockJob);
-        const size_t pin_need = upload_pinned_need(out_bytes) + upload_pinned_need(jobs_bytes);
-        void *pin = pinned.acquire(c, pin_need);
-        if (pin) {
-            BlockJob *pj = reinterpret_cast<BlockJob *>(static_cast<char *>(pin) + upload_pinned_need(out_bytes));
-            HIP_TRY(hipMemcpyAsync(pj, d_sel_jobs.p, jobs_bytes, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            memcpy(jobs.data(), pj, jobs_bytes);
-            out = static_cast<mmgpu_sw_block *>(pin);
-        } else {
-            HIP_TRY(hipMemcpyAsync(jobs.data(), d_sel_jobs.p, jobs_bytes, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            out_auto.resize(n);
-            out = out_auto.data();
-        }
-        // (string offsets as in the other form: block_kernel.hip - profile queries, pairs beyond the pool - walks back whatever is asked)
-        bt_off.assign(n, 0);
-        for (const BlockJob &j : jobs) {
-            const uint64_t len = (uint64_t)j.q_end + 1 + (uint64_t)j.t_end + 1;
-            bt_off[j.slot] = off;
-            off += (len + 1 + 3) & ~3ull;
-            longest = std::max(longest, len);
-        }
-        lap("device selection + job download");
+        memcpy(jobs.data(), pj, jobs_bytes);
+        out = static_cast<mmgpu_sw_block *>(pin);
     } else {
-        if (!b->h_res_valid) {
-            b->h_res.resize((size_t)b->pairs);
-            if (b->pairs) HIP_TRY(hipMemcpyAsync(b->h_res.data(), b->d_out.p, (size_t)b->pairs * sizeof(mmgpu_sw_hit), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (b->from_pf) {
-                b->h_slot_target.resize((size_t)b->pairs);
-                if (b->pairs) HIP_TRY(hipMemcpy(b->h_slot_target.data(), b->d_slot_target.p, (size_t)b->pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            }
-            b->h_res_valid = true;
-        }
-        bt_off.assign(std::max<uint32_t>(n, 1), 0);
-        for (uint32_t k = 0; k < n; k++) {
-            const uint32_t p = pair_index[k];
-            if (p >= b->pairs) return fail(MMGPU_ERR_ARG, "mmgpu_sw_block_backtrace: pair index out of range");
-            const mmgpu_sw_hit &h = b->h_res[p];
-            out[k].q_start = -1; out[k].t_start = -1; out[k].ident = 0; out[k].bt_len = 0; out[k].bt_off = off; out[k].reserved = 0;
-            bt_off[k] = off;
-            const uint32_t q = (uint32_t)(std::upper_bound(b->h_qout_off.begin(), b->h_qout_off.end(), p) - b->h_qout_off.begin() - 1);
-            // (profile queries run the same kernel with the query's score rows in place of matrix + bias: block_kernel.hip, BkSeq::prof)
-            if (h.score <= 0 || h.word != 1 || h.t_end < 0) {
-                out[k].status = MMGPU_BLOCK_NOT_WORD;
-                continue;
-            }
-            out[k].status = MMGPU_BLOCK_TOO_LARGE;    // overwritten by the kernel
-            BlockJob j;
-            j.query = q;
-            j.target = b->from_pf ? b->h_slot_target[p] : b->h_out_target[p];
-            j.score = h.score; j.q_end = h.q_end; j.t_end = h.t_end;
-            j.slot = k;
-            jobs.push_back(j);
-            const uint64_t len = (uint64_t)h.q_end + 1 + (uint64_t)h.t_end + 1;
-            off += (len + 1 + 3) & ~3ull;      // (multiples of four: the walk kernel of block4_kernel.hip stores a string in dwords)
-            longest = std::max(longest, len);
-        }
-        lap("result download + job list");
+        HIP_TRY(hipMemcpyAsync(jobs.data(), d_sel_jobs.p, jobs_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        out_auto.resize(n);
+        out = out_auto.data();
     }
-    if (bt_used) *bt_used = (size_t)off;
-    const bool starts_only = au != nullptr || (bt == nullptr && bt_cap == MMGPU_BLOCK_STARTS_ONLY);    // start positions only: no trace, no walk
-    const bool no_strings = starts_only || (bt == nullptr && bt_cap == MMGPU_BLOCK_NO_STRINGS);      // start positions / identities / lengths only
-    if (!no_strings && (off > bt_cap || (!bt && off))) return fail(MMGPU_ERR_ARG, "mmgpu_sw_block_backtrace: bt buffer too small (see *bt_used)");
-    if (jobs.empty()) return MMGPU_OK;
-    {   // longest pair first, stable: a counting sort over q_end + t_end (both below 65536)
-        std::vector<uint32_t> first((size_t)longest + 2, 0u);
-        for (const BlockJob &j : jobs) first[(size_t)(j.q_end + j.t_end + 2)]++;      // key = the pair's length
-        uint32_t run = 0;
-        for (size_t len = (size_t)longest + 1; len-- > 0;) { const uint32_t cnt = first[len]; first[len] = run; run += cnt; }
-        std::vector<BlockJob> sorted(jobs.size());
-        for (const BlockJob &j : jobs) sorted[first[(size_t)(j.q_end + j.t_end + 2)]++] = j;
-        jobs.swap(sorted);
+    // (string offsets as in the other form: block_kernel.hip - profile queries, pairs beyond the pool - walks back whatever is asked)
+    bt_off.assign(n, 0);
+    for (const BlockJob &j : jobs) {
+        bt_off[j.slot] = off;
+        off += (block_pair_len(j) + 1 + 3) & ~3ull;
     }
-    // the AAMatrix as ssw_init leaves it: new_simple(1, -1) with the substitution matrix written over it (:708,:1469-1474)
-    std::vector<int8_t> mat((size_t)b->alphabet * b->alphabet), scores(27 * 32, (int8_t)-128);
+    lap("device selection + job download");
+    return MMGPU_OK;
+}
+
+// the caller names the pairs: what is no int16-range hit is answered here (MMGPU_BLOCK_NOT_WORD), the others become jobs
+int BlockRun::list_jobs() {
+    if (int e = sw_host_results(b, s)) return e;
+    bt_off.assign(std::max<uint32_t>(n, 1), 0);
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t p = pair_index[k];
+        if (p >= b->pairs) return fail(MMGPU_ERR_ARG, "mmgpu_sw_block_backtrace: pair index out of range");
+        const mmgpu_sw_hit &h = b->h_res[p];
+        out[k].q_start = -1; out[k].t_start = -1; out[k].ident = 0; out[k].bt_len = 0; out[k].bt_off = off; out[k].reserved = 0;
+        bt_off[k] = off;
+        const uint32_t q = (uint32_t)(std::upper_bound(b->h_qout_off.begin(), b->h_qout_off.end(), p) - b->h_qout_off.begin() - 1);
+        // (profile queries run the same kernel with the query's score rows in place of matrix + bias: block_kernel.hip, BkSeq::prof)
+        if (h.score <= 0 || h.word != 1 || h.t_end < 0) {
+            out[k].status = MMGPU_BLOCK_NOT_WORD;
+            continue;
+        }
+        out[k].status = MMGPU_BLOCK_TOO_LARGE;    // overwritten by the kernel
+        BlockJob j;
+        j.query = q;
+        j.target = b->from_pf ? b->h_slot_target[p] : b->h_out_target[p];
+        j.score = h.score; j.q_end = h.q_end; j.t_end = h.t_end;
+        j.slot = k;
+        jobs.push_back(j);
+        off += (block_pair_len(j) + 1 + 3) & ~3ull;      // (multiples of four: the walk kernel of block4_kernel.hip stores a string in dwords)
+    }
+    lap("result download + job list");
+    return MMGPU_OK;
+}
+
+// the AAMatrix as ssw_init leaves it: new_simple(1, -1) with the substitution matrix written over it (:708,:1469-1474)
+int BlockRun::score_table() {
+    std::vector<int8_t> mat((size_t)b->alphabet * b->alphabet);
+    scores.assign(27 * 32, (int8_t)-128);
     HIP_TRY(hipMemcpy(mat.data(), b->d_mat.p, mat.size(), hipMemcpyDeviceToHost));
     for (int x = 0; x < 26; x++)
         for (int y = 0; y < 26; y++) scores[x * 32 + y] = x == y ? 1 : -1;
     for (int x = 0; x < b->alphabet; x++)
         for (int y = 0; y < b->alphabet; y++) { scores[x * 32 + y] = mat[(size_t)x * b->alphabet + y]; scores[y * 32 + x] = mat[(size_t)x * b->alphabet + y]; }
-    // Three tiers (block_kernel.hip), each a launch over what the one before left undecided (TOO_LARGE), all carved out of ONE
-    // scratch pool (hipMalloc costs ~40 ms per GB on this platform, so the pool is sized for the usual case, not the worst):
-    //   tier 0  blocks <= 512 rows, borders in LDS; slot = block list + TWO trace entries (32 B per 64 rows) per column for the
-    //           256th-longest pair - nearly every pair stays at 32 / 64-row blocks; a pair that is longer or grows further
-    //           overflows its slot and moves on
-    //   tier 1  blocks <= 2048 rows in LDS, slot = the crate's own bound for that size (Trace::new, scan_block.rs:1742-1748)
-    //   tier 2  the crate's 4096 rows, borders in the slot
-    auto pair_len = [](const BlockJob &j) { return (uint64_t)j.q_end + 1 + (uint64_t)j.t_end + 1; };
-    auto slot_size = [](uint64_t len, uint64_t entries_per_col, uint64_t max_rows, bool borders) {
-        return (borders ? (uint64_t)8 * BLOCK_REF_MAX_SIZE * 2 : 0ull) + (((len + 64) * 16 + 31) & ~31ull) + entries_per_col * 32 * (len + 2 * max_rows);
-    };
-    constexpr uint64_t pool_limit = 16384ull << 20;
-    // (small calls: slots for the longest pair, everything starts in tier 0)
-    uint64_t typical_len = pair_len(jobs[jobs.size() > 1024 ? 255 : 0]);
-    DevBuf d_btoff, d_bt, d_scores, d_jobs[3], d_pool[3], d_busy[3];
-    for (DevBuf *d : {&d_btoff, &d_bt, &d_scores, &d_jobs[0], &d_jobs[1], &d_jobs[2], &d_pool[0], &d_pool[1], &d_pool[2], &d_busy[0], &d_busy[1], &d_busy[2]})
-        d->bind(c->cache);
-    if (!au) HIP_TRY(d_out.alloc((size_t)n * sizeof(mmgpu_sw_block)));
-    DevBuf d_growth;
-    d_growth.bind(c->cache);
-    const size_t growth_bytes = growth ? (size_t)n * (1 + 4 * (size_t)growth_cap) * 4 : 0;
-    if (growth) {
+    return MMGPU_OK;
+}
+
+// the answers, string offsets, strings and score table on the device; what every launch of the call has in common (L)
+int BlockRun::buffers_and_uploads() {
+    if (!want.select) HIP_TRY(d_out.alloc((size_t)n * sizeof(mmgpu_sw_block)));
+    growth_bytes = want.growth ? (size_t)n * (1 + 4 * (size_t)want.growth_cap) * 4 : 0;
+    if (want.growth) {
         HIP_TRY(d_growth.alloc(growth_bytes));
         HIP_TRY(hipMemsetAsync(d_growth.p, 0, growth_bytes, s));
     }
     HIP_TRY(d_btoff.alloc(bt_off.size() * 8));
     HIP_TRY(d_bt.alloc((size_t)off + 16));
     HIP_TRY(d_scores.alloc(scores.size()));
-    if (!au) HIP_TRY(hipMemcpyAsync(d_out.p, out, (size_t)n * sizeof(mmgpu_sw_block), hipMemcpyHostToDevice, s));      // (au: block_select_kernel wrote them)
+    if (!want.select) HIP_TRY(hipMemcpyAsync(d_out.p, out, (size_t)n * sizeof(mmgpu_sw_block), hipMemcpyHostToDevice, s));      // (select: block_select_kernel wrote them)
     HIP_TRY(hipMemcpyAsync(d_btoff.p, bt_off.data(), bt_off.size() * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_scores.p, scores.data(), scores.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     lap("buffers + uploads");
-    BlockLaunch L;
     L.q_res = b->d_qres.as<uint8_t>();
     L.q_cb = b->d_qcb.as<int8_t>();
     L.q_off = b->d_qoff.as<uint32_t>();
@@ -1639,224 +1659,194 @@ static int block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pa
     L.out = d_out.as<mmgpu_sw_block>();
     L.bt_off = d_btoff.as<uint64_t>();
     L.bt = d_bt.as<char>();
-    L.growth = growth ? d_growth.as<uint32_t>() : nullptr;
-    L.growth_cap = growth_cap;
-    const char *first_tier_env = getenv("MMGPU_BLOCK_FIRST_TIER");      // test aid: every pair through block_kernel.hip's tier 0 / 1 / 2
-    const int first_tier = first_tier_env ? std::max(0, std::min(2, atoi(first_tier_env))) : 0;
+    L.growth = want.growth ? d_growth.as<uint32_t>() : nullptr;
+    L.growth_cap = want.growth_cap;
     b->block_pairs_tier[0] = b->block_pairs_tier[1] = b->block_pairs_tier[2] = 0;
     b->block_pairs_fast = 0;
     b->block_pairs_skew = 0;
-    // ---- block4_kernel.hip: sequence queries.  Launch 1: four pairs per wavefront, blocks up to 256 rows.  What it answers
-    // TOO_LARGE (blocks would grow further, or the trace overflowed the pair's slot) goes through the skewed form - one pair per
-    // wavefront, its rows pipelined over the columns - with blocks up to 1024 rows, then the crate's 4096; each launch starts at the
-    // minimum block size the one before got to (mmgpu_sw_block::reserved of a TOO_LARGE answer).  With a trace the pairs of a launch
-    // run in groups whose block lists + traces fit the pool, each group = fill launch + walk launch on the context's stream ----
-    std::vector<BlockJob> slow_jobs;
-    if (!first_tier_env) {
-        constexpr uint64_t block4_waves = 16;        // wavefronts per CU
-        constexpr uint64_t block4_per_res = 48;      // trace bytes per residue of a pair, launch 1
-        constexpr uint64_t pool2_limit = 3072ull << 20;
-        struct PassBufs {      // what a launch in flight holds: two of them run side by side (the long head, everything else)
-            DevBuf j2, cnt, pool, ck;
-            hipStream_t st = nullptr;
-            std::vector<Block2Job> jobs;
-        } PB[2];
-        for (PassBufs &x : PB) { x.j2.bind(c->cache); x.cnt.bind(c->cache); x.pool.bind(c->cache); x.ck.bind(c->cache); }
-        PB[0].st = s;
-        hipStream_t head_stream = nullptr;
-        auto drop_head_stream = [&] { if (head_stream) { (void)hipStreamDestroy(head_stream); head_stream = nullptr; } };
-        std::vector<uint32_t> resume((size_t)n, 0u);      // per slot: the first minimum block size still to try (bit 16: only the slot was too small)
-#define B_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { drop_head_stream(); return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
-        // one launch: `todo` (longest first) through form 1 (four pairs per wavefront, 256 rows) or 3 (skewed, one pair per wavefront,
-        // 4096 rows), slots of `per_res` trace bytes per residue of the pair; pairs whose slot would not fit the pool go to `left`
-        auto block4_launch = [&](PassBufs &B, const std::vector<BlockJob> &todo, int form, uint64_t per_res, uint64_t margin, uint64_t waves_per_cu,
-                                 std::vector<BlockJob> &left) -> int {
-            std::vector<Block2Job> &j2 = B.jobs;
-            j2.clear();
-            j2.reserve(todo.size());
-            std::vector<uint32_t> group_begin(1, 0u);
-            uint64_t pool_used = 0, pool_need = 0;
-            const int rows = form == 1 ? BLOCK4_LARGE_SIZE : BLOCK_REF_MAX_SIZE;
-            for (const BlockJob &j : todo) {
-                Block2Job x;
-                x.query = j.query; x.target = j.target; x.score = j.score; x.q_end = j.q_end; x.t_end = j.t_end; x.slot = j.slot;
-                x.pool_off = 0; x.pool_bytes = 0; x.pad = resume[j.slot] & 0xFFFFu;
-                if (!starts_only) {
-                    const uint64_t len = pair_len(j);
-                    const uint64_t bytes = (((len + 64) * sizeof(BkBlock) + 31) & ~31ull) + per_res * (len + margin);
-                    if (bytes > pool2_limit || bytes > 0xFFFFFFFFull) { left.push_back(j); continue; }
-                    if (pool_used + bytes > pool2_limit) { group_begin.push_back((uint32_t)j2.size()); pool_used = 0; }
-                    x.pool_off = pool_used; x.pool_bytes = (uint32_t)bytes;
-                    pool_used += bytes;
-                    pool_need = std::max(pool_need, pool_used);
-                }
-                j2.push_back(x);
-            }
-            group_begin.push_back((uint32_t)j2.size());
-            if (j2.empty()) return MMGPU_OK;
-            const size_t n_groups = group_begin.size() - 1;
-            if (j2.size() * sizeof(Block2Job) > B.j2.bytes) B_TRY(B.j2.alloc(j2.size() * sizeof(Block2Job)));
-            if (n_groups * 4 > B.cnt.bytes) B_TRY(B.cnt.alloc(n_groups * 4));
-            if (pool_need > B.pool.bytes) B_TRY(B.pool.alloc((size_t)pool_need));
-            B_TRY(hipMemcpyAsync(B.j2.p, j2.data(), j2.size() * sizeof(Block2Job), hipMemcpyHostToDevice, B.st));
-            B_TRY(hipMemsetAsync(B.cnt.p, 0, n_groups * 4, B.st));
-            Block2Launch L2;
-            L2.q_res = L.q_res; L2.q_cb = L.q_cb; L2.q_off = L.q_off; L2.t_res = L.t_res; L2.t_off4 = L.t_off4;
-            L2.scores = L.scores; L2.gap_open = L.gap_open; L2.gap_extend = L.gap_extend;
-            L2.out = L.out; L2.bt_off = L.bt_off; L2.bt = no_strings ? nullptr : L.bt;
-            L2.pool = B.pool.as<uint8_t>();
-            L2.growth = L.growth; L2.growth_cap = L.growth_cap;
-            L2.trace_bytes = form == 1 ? 0u : 1u;
-            for (size_t g = 0; g < n_groups; g++) {
-                L2.jobs = B.j2.as<Block2Job>() + group_begin[g];
-                L2.n_jobs = group_begin[g + 1] - group_begin[g];
-                L2.counter = B.cnt.as<uint32_t>() + g;
-                const uint32_t waves = (uint32_t)std::min<uint64_t>(form == 1 ? (L2.n_jobs + 3) / 4 : L2.n_jobs, (uint64_t)std::max(c->compute_units, 1) * waves_per_cu);
-                const size_t ck_bytes = (size_t)waves * (form == 1 ? 4 : 1) * 8 * (size_t)rows;
-                if (ck_bytes > B.ck.bytes) B_TRY(B.ck.alloc(ck_bytes));
-                L2.ck_pool = B.ck.as<uint8_t>();
-                B_TRY(launch_sw_block4(L2, !starts_only, form, waves, B.st));
-                if (!starts_only) B_TRY(launch_sw_block4_walk(L2, B.st));
-            }
-            if (trace_on) fprintf(stderr, "[mmgpu block aligner] %s, blocks <= %d rows, %llu trace bytes per residue: %zu pairs in %zu group(s), pool %.1f MB\n",
-                                  form == 1 ? "four pairs per wavefront" : "one pair per wavefront, rows skewed over columns", rows, (unsigned long long)per_res,
-                                  j2.size(), n_groups, pool_need / 1048576.0);
-            return MMGPU_OK;
-        };
-        // ... and its end: the answers; what it handed on (MMGPU_BLOCK_TOO_LARGE) is appended to `left`
-        auto block4_collect = [&](PassBufs &B, std::vector<BlockJob> &left) -> int {
-            if (B.jobs.empty()) return MMGPU_OK;
-            B_TRY(hipStreamSynchronize(B.st));
-            B_TRY(hipMemcpy(out, d_out.p, (size_t)n * sizeof(mmgpu_sw_block), hipMemcpyDeviceToHost));
-            for (const Block2Job &x : B.jobs)
-                if (out[x.slot].status == MMGPU_BLOCK_TOO_LARGE) {
-                    BlockJob j;
-                    j.query = x.query; j.target = x.target; j.score = x.score; j.q_end = x.q_end; j.t_end = x.t_end; j.slot = x.slot;
-                    const uint32_t rs = (uint32_t)out[x.slot].reserved;
-                    resume[x.slot] = std::max(32u, std::min(rs & 0xFFFFu, (uint32_t)BLOCK_REF_MAX_SIZE)) | (rs & 0x10000u);
-                    left.push_back(j);
-                }
-            if (trace_on && !B.jobs.empty()) {      // where in the (longest-first) launch the handed-on pairs stood
-                size_t by_16th[16] = {};
-                for (size_t k = 0; k < B.jobs.size(); k++)
-                    if (out[B.jobs[k].slot].status == MMGPU_BLOCK_TOO_LARGE) by_16th[k * 16 / B.jobs.size()]++;
-                fprintf(stderr, "[mmgpu block aligner] handed on, by sixteenth of the launch's %zu pairs:", B.jobs.size());
-                for (size_t z : by_16th) fprintf(stderr, " %zu", z);
-                fprintf(stderr, "\n");
-            }
-            B.jobs.clear();
-            return MMGPU_OK;
-        };
-        auto longest_first = [&](std::vector<BlockJob> &v) {
-            std::stable_sort(v.begin(), v.end(), [&](const BlockJob &x, const BlockJob &y) { return pair_len(x) > pair_len(y); });
-        };
-        std::vector<BlockJob> seq_jobs, head, rest, handed, again, skew, skew_again;
-        for (const BlockJob &j : jobs) {      // (`jobs` is sorted longest first)
-            if (!b->h_query_is_profile.empty() && b->h_query_is_profile[j.query]) slow_jobs.push_back(j);
-            else seq_jobs.push_back(j);
-        }
-        const size_t before = slow_jobs.size();
-        // The longest pairs - one per CU - go straight to the skewed form on a stream of their own, beside everything else: the pairs
-        // whose blocks grow to thousands of rows are among them, each a dependent chain of tens of milliseconds that nothing shortens
-        // but starting it first.
-        const size_t n_head = seq_jobs.size() >= 4096 ? std::min<size_t>(seq_jobs.size() / 16, (size_t)std::max(c->compute_units, 1)) : 0;
-        head.assign(seq_jobs.begin(), seq_jobs.begin() + n_head);
-        rest.assign(seq_jobs.begin() + n_head, seq_jobs.end());
-        int rc2;
-        if (n_head) {
-            if (hipStreamCreateWithFlags(&head_stream, hipStreamNonBlocking) != hipSuccess) return fail(MMGPU_ERR_HIP, "mmgpu_sw_block_backtrace: hipStreamCreate");
-            PB[1].st = head_stream;
-            B_TRY(hipStreamSynchronize(s));      // (the uploads above)
-            rc2 = block4_launch(PB[1], head, 3, 1024, 2048, 4, skew_again);
-            if (rc2 != MMGPU_OK) { drop_head_stream(); return rc2; }
-        }
-        // launch 1: everything else, slots for the usual 32 / 64-row blocks (half a byte per cell).  Resident wavefronts by LDS: 3.4 KB of
-        // score table + 8 KB (four pairs' border arrays); the skewed form's 32 KB allow four
-        // (Measured and dropped in round 6: launch 1 cut in two - the longest eighth of the pairs first, so that its hand-ons could start
-        // their chains in the skewed form beside the other seven eighths.  500 of the 536 hand-ons of configs[2] do come from that
-        // eighth, but it takes 15 ms of its own - the longest pairs - and the 500 chains another 25: 44.7 ms per call against 43.5.
-        // The call is as long as ONE pair's chain through blocks of thousands of rows on one wavefront.)
-        rc2 = block4_launch(PB[0], rest, 1, block4_per_res, 512, block4_waves, skew);
-        if (rc2 == MMGPU_OK) rc2 = block4_collect(PB[0], handed);
-        if (rc2 != MMGPU_OK) { drop_head_stream(); return rc2; }
-        lap("four pairs per wavefront + status download");
-        // ... once more for the pairs whose slot was too small (256-row blocks all the way: 128 bytes per residue)
-        for (const BlockJob &j : handed) (resume[j.slot] & 0x10000u ? again : skew).push_back(j);
-        if (!again.empty()) {
-            longest_first(again);
-            rc2 = block4_launch(PB[0], again, 1, 160, 2048, block4_waves, skew);
-            if (rc2 == MMGPU_OK) rc2 = block4_collect(PB[0], skew);
-            if (rc2 != MMGPU_OK) { drop_head_stream(); return rc2; }
-            lap("four pairs per wavefront, larger slots + status download");
-        }
-        // launch 2: the skewed form for blocks beyond 256 rows (a byte per cell: slots for blocks of 1024 rows, then the crate's bound)
-        longest_first(skew);
-        rc2 = block4_launch(PB[0], skew, 3, 1024, 2048, 4, skew_again);
-        if (rc2 == MMGPU_OK) rc2 = block4_collect(PB[0], skew_again);
-        if (rc2 == MMGPU_OK && n_head) rc2 = block4_collect(PB[1], skew_again);
-        if (rc2 != MMGPU_OK) { drop_head_stream(); return rc2; }
-        if (!skew.empty() || n_head) lap("skewed form (and the head) + status download");
-        const size_t n_skew = skew.size() + n_head;
-        if (!skew_again.empty()) {
-            longest_first(skew_again);
-            rc2 = block4_launch(PB[0], skew_again, 3, 4096, 8192, 4, slow_jobs);
-            if (rc2 == MMGPU_OK) rc2 = block4_collect(PB[0], slow_jobs);
-            if (rc2 != MMGPU_OK) { drop_head_stream(); return rc2; }
-            lap("skewed form, the crate's slots + status download");
-        }
-        drop_head_stream();
-#undef B_TRY
-        longest_first(slow_jobs);
-        b->block_pairs_skew = (uint32_t)(n_skew - (slow_jobs.size() - before));
-        b->block_pairs_fast = (uint32_t)(seq_jobs.size() - n_skew);
-    } else {
-        slow_jobs = jobs;
+    return MMGPU_OK;
+}
+
+// one launch: `todo` (longest first) through form 1 (four pairs per wavefront, 256 rows) or 3 (skewed, one pair per wavefront,
+// 4096 rows), slots of `per_res` trace bytes per residue of the pair; pairs whose slot would not fit the pool go to `left`.  With a
+// trace the pairs run in groups whose block lists + traces fit the pool, each group = fill launch + walk launch on the pass's stream
+int BlockRun::block4_launch(PassBufs &B, const std::vector<BlockJob> &todo, int form, uint64_t per_res, uint64_t margin, uint64_t waves_per_cu,
+                            std::vector<BlockJob> &left) {
+    block4_plan(todo, resume, per_res, margin, BLOCK4_POOL_LIMIT, want.starts_only, B.plan, left);
+    const std::vector<Block2Job> &j2 = B.plan.jobs;
+    if (j2.empty()) return MMGPU_OK;
+    const size_t n_groups = B.plan.n_groups();
+    const int rows = form == 1 ? BLOCK4_LARGE_SIZE : BLOCK_REF_MAX_SIZE;
+    if (j2.size() * sizeof(Block2Job) > B.j2.bytes) HIP_TRY(B.j2.alloc(j2.size() * sizeof(Block2Job)));
+    if (n_groups * 4 > B.cnt.bytes) HIP_TRY(B.cnt.alloc(n_groups * 4));
+    if (B.plan.pool_need > B.pool.bytes) HIP_TRY(B.pool.alloc((size_t)B.plan.pool_need));
+    HIP_TRY(hipMemcpyAsync(B.j2.p, j2.data(), j2.size() * sizeof(Block2Job), hipMemcpyHostToDevice, B.st));
+    HIP_TRY(hipMemsetAsync(B.cnt.p, 0, n_groups * 4, B.st));
+    Block2Launch L2;
+    L2.q_res = L.q_res; L2.q_cb = L.q_cb; L2.q_off = L.q_off; L2.t_res = L.t_res; L2.t_off4 = L.t_off4;
+    L2.scores = L.scores; L2.gap_open = L.gap_open; L2.gap_extend = L.gap_extend;
+    L2.out = L.out; L2.bt_off = L.bt_off; L2.bt = want.no_strings ? nullptr : L.bt;
+    L2.pool = B.pool.as<uint8_t>();
+    L2.growth = L.growth; L2.growth_cap = L.growth_cap;
+    L2.trace_bytes = form == 1 ? 0u : 1u;
+    for (size_t g = 0; g < n_groups; g++) {
+        L2.jobs = B.j2.as<Block2Job>() + B.plan.group_begin[g];
+        L2.n_jobs = B.plan.group_begin[g + 1] - B.plan.group_begin[g];
+        L2.counter = B.cnt.as<uint32_t>() + g;
+        const uint32_t waves = (uint32_t)std::min<uint64_t>(form == 1 ? (L2.n_jobs + 3) / 4 : L2.n_jobs, (uint64_t)std::max(c->compute_units, 1) * waves_per_cu);
+        const size_t ck_bytes = (size_t)waves * (form == 1 ? 4 : 1) * 8 * (size_t)rows;
+        if (ck_bytes > B.ck.bytes) HIP_TRY(B.ck.alloc(ck_bytes));
+        L2.ck_pool = B.ck.as<uint8_t>();
+        HIP_TRY(launch_sw_block4(L2, !want.starts_only, form, waves, B.st));
+        if (!want.starts_only) HIP_TRY(launch_sw_block4_walk(L2, B.st));
     }
-    // (what is left: profile queries, pairs whose slot would not fit the pool)
+    if (trace_on()) fprintf(stderr, "[mmgpu block aligner] %s, blocks <= %d rows, %llu trace bytes per residue: %zu pairs in %zu group(s), pool %.1f MB\n",
+                            form == 1 ? "four pairs per wavefront" : "one pair per wavefront, rows skewed over columns", rows, (unsigned long long)per_res,
+                            j2.size(), n_groups, B.plan.pool_need / 1048576.0);
+    return MMGPU_OK;
+}
+
+// ... and its end: the answers; what it handed on (MMGPU_BLOCK_TOO_LARGE) is appended to `left`
+int BlockRun::block4_collect(PassBufs &B, std::vector<BlockJob> &left) {
+    std::vector<Block2Job> &j2 = B.plan.jobs;
+    if (j2.empty()) return MMGPU_OK;
+    HIP_TRY(hipStreamSynchronize(B.st));
+    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * sizeof(mmgpu_sw_block), hipMemcpyDeviceToHost));
+    for (const Block2Job &x : j2)
+        if (out[x.slot].status == MMGPU_BLOCK_TOO_LARGE) {
+            BlockJob j;
+            j.query = x.query; j.target = x.target; j.score = x.score; j.q_end = x.q_end; j.t_end = x.t_end; j.slot = x.slot;
+            const uint32_t rs = (uint32_t)out[x.slot].reserved;
+            resume[x.slot] = std::max(32u, std::min(rs & 0xFFFFu, (uint32_t)BLOCK_REF_MAX_SIZE)) | (rs & 0x10000u);
+            left.push_back(j);
+        }
+    if (trace_on()) {      // where in the (longest-first) launch the handed-on pairs stood
+        size_t by_16th[16] = {};
+        for (size_t k = 0; k < j2.size(); k++)
+            if (out[j2[k].slot].status == MMGPU_BLOCK_TOO_LARGE) by_16th[k * 16 / j2.size()]++;
+        fprintf(stderr, "[mmgpu block aligner] handed on, by sixteenth of the launch's %zu pairs:", j2.size());
+        for (size_t z : by_16th) fprintf(stderr, " %zu", z);
+        fprintf(stderr, "\n");
+    }
+    j2.clear();
+    return MMGPU_OK;
+}
+
+// block4_kernel.hip: sequence queries.  Launch 1: four pairs per wavefront, blocks up to 256 rows.  What it answers TOO_LARGE (blocks
+// would grow further, or the trace overflowed the pair's slot) goes through the skewed form - one pair per wavefront, its rows
+// pipelined over the columns - with blocks up to 1024 rows, then the crate's 4096; each launch starts at the minimum block size the
+// one before got to (mmgpu_sw_block::reserved of a TOO_LARGE answer).
+int BlockRun::block4_passes() {
+    constexpr uint64_t block4_waves = 16;        // wavefronts per CU
+    constexpr uint64_t block4_per_res = 48;      // trace bytes per residue of a pair, launch 1
+    resume.assign((size_t)n, 0u);
+    PB[0].st = s;
+    std::vector<BlockJob> seq_jobs, head, rest, handed, again, skew, skew_again;
+    for (const BlockJob &j : jobs) {      // (`jobs` is sorted longest first)
+        if (!b->h_query_is_profile.empty() && b->h_query_is_profile[j.query]) slow_jobs.push_back(j);
+        else seq_jobs.push_back(j);
+    }
+    const size_t before = slow_jobs.size();
+    // the head launch (block_head_size): the longest pairs in the skewed form, on a stream and with buffers of their own
+    const size_t n_head = block_head_size(seq_jobs.size(), c->compute_units);
+    head.assign(seq_jobs.begin(), seq_jobs.begin() + n_head);
+    rest.assign(seq_jobs.begin() + n_head, seq_jobs.end());
+    if (n_head) {
+        if (head_stream.create() != hipSuccess) return fail(MMGPU_ERR_HIP, "mmgpu_sw_block_backtrace: hipStreamCreate");
+        PB[1].st = head_stream.s;
+        HIP_TRY(hipStreamSynchronize(s));      // (the uploads of buffers_and_uploads)
+        if (int e = block4_launch(PB[1], head, 3, 1024, 2048, 4, skew_again)) return e;
+    }
+    // launch 1: everything else, slots for the usual 32 / 64-row blocks (half a byte per cell).  Resident wavefronts by LDS: 3.4 KB of
+    // score table + 8 KB (four pairs' border arrays); the skewed form's 32 KB allow four
+    // (Measured and dropped in round 6: launch 1 cut in two - the longest eighth of the pairs first, so that its hand-ons could start
+    // their chains in the skewed form beside the other seven eighths.  500 of the 536 hand-ons of configs[2] do come from that
+    // eighth, but it takes 15 ms of its own - the longest pairs - and the 500 chains another 25: 44.7 ms per call against 43.5.
+    // The call is as long as ONE pair's chain through blocks of thousands of rows on one wavefront.)
+    if (int e = block4_launch(PB[0], rest, 1, block4_per_res, 512, block4_waves, skew)) return e;
+    if (int e = block4_collect(PB[0], handed)) return e;
+    lap("four pairs per wavefront + status download");
+    // ... once more for the pairs whose slot was too small (256-row blocks all the way: 128 bytes per residue)
+    for (const BlockJob &j : handed) (resume[j.slot] & 0x10000u ? again : skew).push_back(j);
+    if (!again.empty()) {
+        block_longest_first(again);
+        if (int e = block4_launch(PB[0], again, 1, 160, 2048, block4_waves, skew)) return e;
+        if (int e = block4_collect(PB[0], skew)) return e;
+        lap("four pairs per wavefront, larger slots + status download");
+    }
+    // launch 2: the skewed form for blocks beyond 256 rows (a byte per cell: slots for blocks of 1024 rows, then the crate's bound)
+    block_longest_first(skew);
+    if (int e = block4_launch(PB[0], skew, 3, 1024, 2048, 4, skew_again)) return e;
+    if (int e = block4_collect(PB[0], skew_again)) return e;
+    if (n_head)
+        if (int e = block4_collect(PB[1], skew_again)) return e;
+    if (!skew.empty() || n_head) lap("skewed form (and the head) + status download");
+    const size_t n_skew = skew.size() + n_head;
+    if (!skew_again.empty()) {
+        block_longest_first(skew_again);
+        if (int e = block4_launch(PB[0], skew_again, 3, 4096, 8192, 4, slow_jobs)) return e;
+        if (int e = block4_collect(PB[0], slow_jobs)) return e;
+        lap("skewed form, the crate's slots + status download");
+    }
+    block_longest_first(slow_jobs);
+    b->block_pairs_skew = (uint32_t)(n_skew - (slow_jobs.size() - before));
+    b->block_pairs_fast = (uint32_t)(seq_jobs.size() - n_skew);
+    return MMGPU_OK;
+}
+
+// Three tiers (block_kernel.hip) for what is left - profile queries, pairs whose slot would not fit the pool - each a launch over
+// what the one before left undecided (TOO_LARGE), all carved out of ONE scratch pool per tier (hipMalloc costs ~40 ms per GB on
+// this platform, so the pool is sized for the usual case, not the worst):
+//   tier 0  blocks <= 512 rows, borders in LDS; slot = block list + TWO trace entries (32 B per 64 rows) per column for the
+//           256th-longest pair - nearly every pair stays at 32 / 64-row blocks; a pair that is longer or grows further
+//           overflows its slot and moves on
+//   tier 1  blocks <= 2048 rows in LDS, slot = the crate's own bound for that size (Trace::new, scan_block.rs:1742-1748)
+//   tier 2  the crate's 4096 rows, borders in the slot
+// The tiers of a round run side by side, the second and third on streams of their own.
+int BlockRun::tier_rounds() {
+    if (slow_jobs.empty()) return MMGPU_OK;
+    const int first_tier = first_tier_env ? std::max(0, std::min(2, atoi(first_tier_env))) : 0;
     const uint64_t tier0_entries = first_tier_env ? 2 : BLOCK_MAX_SIZE / 64;
+    // (small calls: slots for the longest pair, everything starts in tier 0)
+    const uint64_t typical_len = block_pair_len(slow_jobs[slow_jobs.size() > 1024 ? 255 : 0]);
     std::vector<BlockJob> wait[3];      // longest first inside each
-    if (!slow_jobs.empty()) typical_len = pair_len(slow_jobs[slow_jobs.size() > 1024 ? 255 : 0]);
-    for (const BlockJob &j : slow_jobs) wait[first_tier == 0 && pair_len(j) > typical_len ? 1 : first_tier].push_back(j);
-    hipStream_t extra[2] = {nullptr, nullptr};
-    auto release_streams = [&] { for (hipStream_t &x : extra) if (x) { (void)hipStreamDestroy(x); x = nullptr; } };
+    for (const BlockJob &j : slow_jobs) wait[first_tier == 0 && block_pair_len(j) > typical_len ? 1 : first_tier].push_back(j);
     while (!wait[0].empty() || !wait[1].empty() || !wait[2].empty()) {
         int n_launched = 0;
         for (int tier = 2; tier >= 0; tier--) {      // (the long chains first)
             std::vector<BlockJob> &todo = wait[tier];
             if (todo.empty()) continue;
-            const uint64_t longest_todo = pair_len(todo.front());
-            const uint64_t slot_bytes = tier == 0   ? slot_size(typical_len, tier0_entries, BLOCK_MAX_SIZE, false)
-                                        : tier == 1 ? slot_size(longest_todo, BLOCK_MID_SIZE / 64, BLOCK_MID_SIZE, false)
-                                                    : slot_size(longest_todo, BLOCK_REF_MAX_SIZE / 64, BLOCK_REF_MAX_SIZE, true);
+            const uint64_t longest_todo = block_pair_len(todo.front());
+            const uint64_t slot_bytes = tier == 0   ? block_tier_slot_bytes(typical_len, tier0_entries, BLOCK_MAX_SIZE, false)
+                                        : tier == 1 ? block_tier_slot_bytes(longest_todo, BLOCK_MID_SIZE / 64, BLOCK_MID_SIZE, false)
+                                                    : block_tier_slot_bytes(longest_todo, BLOCK_REF_MAX_SIZE / 64, BLOCK_REF_MAX_SIZE, true);
             // (tier 0: 16 wavefronts per CU is what its 9 KB of LDS allows; 8 per CU, or 32 with a 128-row first tier, move the call by
             // +12 % / -3 %, profiles/r04_exp_block_occupancy.txt - the kernel is bound by its ~200 instructions per column, not by latency)
-            const uint64_t want = std::min<uint64_t>(todo.size(), (uint64_t)std::max(c->compute_units, 1) * (tier == 0 ? 16 : 4));
-            const uint32_t slots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, pool_limit / slot_bytes));
+            const uint32_t slots = block_tier_slots(todo.size(), c->compute_units, tier == 0 ? 16 : 4, slot_bytes);
             hipStream_t st = s;
             if (n_launched > 0) {
-                if (!extra[n_launched - 1] && hipStreamCreateWithFlags(&extra[n_launched - 1], hipStreamNonBlocking) != hipSuccess) { release_streams(); return fail(MMGPU_ERR_HIP, "mmgpu_sw_block_backtrace: hipStreamCreate"); }
-                st = extra[n_launched - 1];
+                if (extra[n_launched - 1].create() != hipSuccess) return fail(MMGPU_ERR_HIP, "mmgpu_sw_block_backtrace: hipStreamCreate");
+                st = extra[n_launched - 1].s;
             }
-#define R_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { release_streams(); return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
-            if ((size_t)slot_bytes * slots > d_pool[tier].bytes) R_TRY(d_pool[tier].alloc((size_t)slot_bytes * slots));
-            if ((size_t)slots * 4 > d_busy[tier].bytes) R_TRY(d_busy[tier].alloc((size_t)slots * 4));
-            if (todo.size() * sizeof(BlockJob) > d_jobs[tier].bytes) R_TRY(d_jobs[tier].alloc(todo.size() * sizeof(BlockJob)));
-            R_TRY(hipMemsetAsync(d_busy[tier].p, 0, (size_t)slots * 4, st));
-            R_TRY(hipMemcpyAsync(d_jobs[tier].p, todo.data(), todo.size() * sizeof(BlockJob), hipMemcpyHostToDevice, st));
+            if ((size_t)slot_bytes * slots > d_pool[tier].bytes) HIP_TRY(d_pool[tier].alloc((size_t)slot_bytes * slots));
+            if ((size_t)slots * 4 > d_busy[tier].bytes) HIP_TRY(d_busy[tier].alloc((size_t)slots * 4));
+            if (todo.size() * sizeof(BlockJob) > d_jobs[tier].bytes) HIP_TRY(d_jobs[tier].alloc(todo.size() * sizeof(BlockJob)));
+            HIP_TRY(hipMemsetAsync(d_busy[tier].p, 0, (size_t)slots * 4, st));
+            HIP_TRY(hipMemcpyAsync(d_jobs[tier].p, todo.data(), todo.size() * sizeof(BlockJob), hipMemcpyHostToDevice, st));
             L.jobs = d_jobs[tier].as<BlockJob>();
             L.n_jobs = (uint32_t)todo.size();
             L.pool = d_pool[tier].as<uint8_t>();
             L.slot_bytes = slot_bytes;
             L.n_pool_slots = slots;
             L.pool_busy = d_busy[tier].as<uint32_t>();
-            R_TRY(launch_sw_block(L, tier, st));
-            if (trace_on) fprintf(stderr, "[mmgpu block aligner] tier %d: %zu pairs, %u slots of %.1f KB\n", tier, todo.size(), slots, slot_bytes / 1024.0);
+            HIP_TRY(launch_sw_block(L, tier, st));
+            if (trace_on()) fprintf(stderr, "[mmgpu block aligner] tier %d: %zu pairs, %u slots of %.1f KB\n", tier, todo.size(), slots, slot_bytes / 1024.0);
             n_launched++;
         }
-        for (hipStream_t x : extra) if (x) R_TRY(hipStreamSynchronize(x));
-        R_TRY(hipStreamSynchronize(s));
-        R_TRY(hipMemcpy(out, d_out.p, (size_t)n * sizeof(mmgpu_sw_block), hipMemcpyDeviceToHost));
-#undef R_TRY
+        for (const SideStream &x : extra)
+            if (x.s) HIP_TRY(hipStreamSynchronize(x.s));
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * sizeof(mmgpu_sw_block), hipMemcpyDeviceToHost));
         std::vector<BlockJob> next[3];
         for (int tier = 0; tier < 3; tier++) {
             size_t left = 0;
@@ -1865,42 +1855,70 @@ static int block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pa
             b->block_pairs_tier[tier] += (uint32_t)(wait[tier].size() - left);
         }
         for (int tier = 0; tier < 3; tier++) {
-            std::stable_sort(next[tier].begin(), next[tier].end(), [&](const BlockJob &x, const BlockJob &y) { return pair_len(x) > pair_len(y); });
+            block_longest_first(next[tier]);
             wait[tier].swap(next[tier]);
         }
         lap("round of tier launches + status download");
     }
-    release_streams();
-    if (au) {
-        // ---- the answers into the batch's records; what the block aligner declined gets its reverse scan (:873-882) ----
-        HIP_TRY(d_flags.alloc((size_t)b->pairs));
-        HIP_TRY(hipMemsetAsync(d_flags.p, 0, (size_t)b->pairs, s));
-        HIP_TRY(hipMemsetAsync(d_sel_cnt.p, 0, 32, s));
-        BlockScatterArgs S;
-        S.blk = d_out.as<mmgpu_sw_block>();
-        S.pair_of_slot = d_sel_pairs.as<uint32_t>();
-        S.n = n;
-        S.res = b->d_out.as<mmgpu_sw_hit>();
-        S.rev_force = d_flags.as<uint8_t>();
-        S.counts = d_sel_cnt.as<uint32_t>();
-        HIP_TRY(launch_block_scatter(S, s));
-        uint32_t counts[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(counts, d_sel_cnt.p, 12, hipMemcpyDeviceToHost, s));
+    return MMGPU_OK;
+}
+
+// mmgpu_sw_block_starts: the answers into the batch's records; what the block aligner declined gets its reverse scan (:873-882)
+int BlockRun::scatter_answers() {
+    HIP_TRY(d_flags.alloc((size_t)b->pairs));
+    HIP_TRY(hipMemsetAsync(d_flags.p, 0, (size_t)b->pairs, s));
+    HIP_TRY(hipMemsetAsync(d_sel_cnt.p, 0, 32, s));
+    BlockScatterArgs S;
+    S.blk = d_out.as<mmgpu_sw_block>();
+    S.pair_of_slot = d_sel_pairs.as<uint32_t>();
+    S.n = n;
+    S.res = b->d_out.as<mmgpu_sw_hit>();
+    S.rev_force = d_flags.as<uint8_t>();
+    S.counts = d_sel_cnt.as<uint32_t>();
+    HIP_TRY(launch_block_scatter(S, s));
+    uint32_t counts[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, d_sel_cnt.p, 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    want.select->ok = counts[0]; want.select->declined = counts[1]; want.select->too_large = counts[2];
+    if (counts[1]) {
+        if (int e = sw_launch_groups(c, b, true, d_flags.as<uint8_t>())) return e;
         HIP_TRY(hipStreamSynchronize(s));
-        au->ok = counts[0]; au->declined = counts[1]; au->too_large = counts[2];
-        if (counts[1]) {
-            if (int e = sw_launch_groups(c, b, true, d_flags.as<uint8_t>())) return e;
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-        b->h_res_valid = false;
-        lap("answers scattered into the records (+ reverse scan of declined pairs)");
-        return MMGPU_OK;
     }
-    if (off && !no_strings) HIP_TRY(hipMemcpyAsync(bt, d_bt.p, (size_t)off, hipMemcpyDeviceToHost, s));
-    if (growth) HIP_TRY(hipMemcpyAsync(growth, d_growth.p, growth_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));      // the host vectors and the buffers above die with this scope
+    b->h_res_valid = false;
+    lap("answers scattered into the records (+ reverse scan of declined pairs)");
+    return MMGPU_OK;
+}
+
+int BlockRun::download_strings() {
+    if (off && !want.no_strings) HIP_TRY(hipMemcpyAsync(bt, d_bt.p, (size_t)off, hipMemcpyDeviceToHost, s));
+    if (want.growth) HIP_TRY(hipMemcpyAsync(want.growth, d_growth.p, growth_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));      // the host vectors and the buffers of the call die with it
     lap("backtrace strings download");
     return MMGPU_OK;
+}
+
+}  // namespace
+
+static int block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pair_index, uint32_t n, mmgpu_sw_block *out,
+                           char *bt, size_t bt_cap, size_t *bt_used, const BlockWant &want) {
+    if (!c || !b || (!want.select && ((!pair_index && n) || (!out && n)))) return fail(MMGPU_ERR_ARG, "mmgpu_sw_block_backtrace: NULL argument");
+    if (!b->ran) return fail(MMGPU_ERR_STATE, "mmgpu_sw_block_backtrace: batch was never run");
+    if (b->alphabet > 26) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_block_backtrace: alphabet above 26 letters");
+    HIP_TRY(hipSetDevice(c->device));
+    if (b->mode < MMGPU_SW_START && !b->from_pf && b->h_out_target.empty())
+        return fail(MMGPU_ERR_STATE, "mmgpu_sw_block_backtrace: the batch keeps no slot -> target map (prepare it with MMGPU_SW_START)");
+    BlockRun R(c, b, pair_index, n, out, bt, want);
+    if (int e = want.select ? R.select_jobs() : R.list_jobs()) return e;
+    if (bt_used) *bt_used = (size_t)R.off;
+    if (!want.no_strings && (R.off > bt_cap || (!bt && R.off))) return fail(MMGPU_ERR_ARG, "mmgpu_sw_block_backtrace: bt buffer too small (see *bt_used)");
+    if (R.jobs.empty()) return MMGPU_OK;
+    block_longest_first(R.jobs);
+    if (int e = R.score_table()) return e;
+    if (int e = R.buffers_and_uploads()) return e;
+    if (R.first_tier_env) R.slow_jobs = R.jobs;
+    else if (int e = R.block4_passes()) return e;
+    if (int e = R.tier_rounds()) return e;
+    return want.select ? R.scatter_answers() : R.download_strings();
 }
 
 
@@ -1913,7 +1931,10 @@ extern "C" int mmgpu_sw_block_starts(mmgpu_ctx *c, mmgpu_sw_batch_t *b, uint32_t
     if (b->mode != MMGPU_SW_START_NOT_WORD) return fail(MMGPU_ERR_STATE, "mmgpu_sw_block_starts: the batch was not prepared with MMGPU_SW_START_NOT_WORD");
     if (b->owned) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_block_starts: not for batches of owned pairs (sharded runs)");
     BlockAuto au;
-    const int rc = block_backtrace(c, b, nullptr, 0, nullptr, nullptr, MMGPU_BLOCK_STARTS_ONLY, nullptr, nullptr, 0, &au);
+    BlockWant want;
+    want.select = &au;
+    want.starts_only = want.no_strings = true;
+    const int rc = block_backtrace(c, b, nullptr, 0, nullptr, nullptr, 0, nullptr, want);
     if (n_selected) *n_selected = au.selected;
     if (n_declined) *n_declined = au.declined;
     if (n_too_large) *n_too_large = au.too_large;
@@ -1922,13 +1943,20 @@ extern "C" int mmgpu_sw_block_starts(mmgpu_ctx *c, mmgpu_sw_batch_t *b, uint32_t
 
 extern "C" int mmgpu_sw_block_backtrace(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pair_index, uint32_t n, mmgpu_sw_block *out,
                                         char *bt, size_t bt_cap, size_t *bt_used) {
-    return block_backtrace(c, b, pair_index, n, out, bt, bt_cap, bt_used, nullptr, 0);
+    BlockWant want;
+    want.starts_only = bt == nullptr && bt_cap == MMGPU_BLOCK_STARTS_ONLY;
+    want.no_strings = want.starts_only || (bt == nullptr && bt_cap == MMGPU_BLOCK_NO_STRINGS);
+    return block_backtrace(c, b, pair_index, n, out, bt, bt_cap, bt_used, want);
 }
 
 extern "C" int mmgpu_sw_block_growth(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint32_t *pair_index, uint32_t n, mmgpu_sw_block *out,
                                      uint32_t *growth, uint32_t growth_cap) {
     if (!growth || growth_cap == 0) return fail(MMGPU_ERR_ARG, "mmgpu_sw_block_growth: no buffer");
-    return block_backtrace(c, b, pair_index, n, out, nullptr, MMGPU_BLOCK_NO_STRINGS, nullptr, growth, growth_cap);
+    BlockWant want;
+    want.no_strings = true;
+    want.growth = growth;
+    want.growth_cap = growth_cap;
+    return block_backtrace(c, b, pair_index, n, out, nullptr, 0, nullptr, want);
 }
 
 extern "C" int mmgpu_sw_block_tiers(const mmgpu_sw_batch_t *b, uint32_t *first_tier, uint32_t *second_tier) {
@@ -1945,18 +1973,7 @@ extern "C" int mmgpu_sw_traceback(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint3
     if (!b->ran) return fail(MMGPU_ERR_STATE, "mmgpu_sw_traceback: batch was never run");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    // host copies of the results (and, for device-resident lists, of the slot -> target map): fetched once per run of the
-    // batch, callers ask for the size first and for the strings second
-    if (!b->h_res_valid) {
-        b->h_res.resize((size_t)b->pairs);
-        if (b->pairs) HIP_TRY(hipMemcpyAsync(b->h_res.data(), b->d_out.p, (size_t)b->pairs * sizeof(mmgpu_sw_hit), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (b->from_pf) {
-            b->h_slot_target.resize((size_t)b->pairs);
-            if (b->pairs) HIP_TRY(hipMemcpy(b->h_slot_target.data(), b->d_slot_target.p, (size_t)b->pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        }
-        b->h_res_valid = true;
-    }
+    if (int e = sw_host_results(b, s)) return e;      // (callers ask for the size first and for the strings second)
     const std::vector<mmgpu_sw_hit> &res = b->h_res;
     const std::vector<uint32_t> &pf_host = b->h_slot_target;
     std::vector<BtJob> jobs;

@@ -20,6 +20,7 @@
 
 #include "../../include/mmgpu.h"
 #include "nucl_core.h"
+#include "block_plan.h"
 
 namespace mmgpu {
 
@@ -509,14 +510,7 @@ struct BtLaunch {
 };
 
 // ---- block aligner on the device (block_kernel.hip; row a15): int16-range hits ----
-constexpr int BLOCK_MAX_SIZE = 512;        // largest block the first-tier kernel holds in LDS
-constexpr int BLOCK_MID_SIZE = 2048;       // second tier: still in LDS (32 KB)
-constexpr int BLOCK_REF_MAX_SIZE = 4096;   // MAX_SIZE of the reference (StripedSmithWaterman.cpp:37); third tier, borders in HBM
-struct BlockJob {
-    uint32_t query, target;
-    int32_t score, q_end, t_end;
-    uint32_t slot;                // index into out / bt_off
-};
+// (the tier sizes, BlockJob, Block2Job and BkBlock: block_plan.h)
 struct BlockLaunch {
     const BlockJob *jobs;
     uint32_t n_jobs;
@@ -545,17 +539,9 @@ struct BlockLaunch {
 // tier 0: blocks up to BLOCK_MAX_SIZE rows (LDS), 1: up to BLOCK_MID_SIZE (LDS), 2: up to BLOCK_REF_MAX_SIZE rows, border arrays
 // in the first 8 * 4096 * 2 bytes of the pair's scratch slot
 hipError_t launch_sw_block(const BlockLaunch &L, int tier, hipStream_t stream);
-struct BkBlock { uint32_t i, j; uint16_t h, w; uint32_t right, tstart; };   // Trace::block_start / block_size / right + the block's first trace entry
 
 // ---- the same aligner, four pairs per wavefront (block4_kernel.hip): sequence queries; what a launch answers MMGPU_BLOCK_TOO_LARGE
 // goes to the next form ----
-struct Block2Job {
-    uint32_t query, target;
-    int32_t score, q_end, t_end;
-    uint32_t slot;                // index into out / bt_off
-    uint64_t pool_off;            // the pair's scratch (block list + trace) in the pool; unused without a trace
-    uint32_t pool_bytes, pad;     // pad: block4_kernel.hip - the first minimum block size to try (0 = 32)
-};
 struct Block2Launch {
     const Block2Job *jobs;
     uint32_t n_jobs;
@@ -757,6 +743,59 @@ struct DevBuf {
     // grow-only (contents are not preserved)
     hipError_t reserve(size_t n) { return n <= bytes ? hipSuccess : alloc(n + n / 8); }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// A non-blocking stream of one call, beside the context's.  The holder waits for the stream before it destroys it: declare it AFTER
+// the buffers its work uses, so that a return with a launch in flight ends the launch before the buffers go back to the cache.
+struct SideStream {
+    hipStream_t s = nullptr;
+    SideStream() = default;
+    SideStream(const SideStream &) = delete;
+    SideStream &operator=(const SideStream &) = delete;
+    ~SideStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+};
+
+// A pinned staging buffer and the event of the last copy out of it (with_event = false: a buffer for blocking copies, no event)
+struct PinnedStage {
+    uint8_t *p = nullptr;
+    hipEvent_t moved = nullptr;
+    PinnedStage() = default;
+    PinnedStage(const PinnedStage &) = delete;
+    PinnedStage &operator=(const PinnedStage &) = delete;
+    ~PinnedStage() { if (p) (void)hipHostFree(p); if (moved) (void)hipEventDestroy(moved); }
+    hipError_t reserve(size_t bytes, bool with_event = true) {
+        const hipError_t e = hipHostMalloc((void **)&p, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        return with_event ? hipEventCreateWithFlags(&moved, hipEventDisableTiming) : hipSuccess;
+    }
+};
+
+// Host -> device in chunks: a stream of its own and a ring of staging buffers.  The caller fills slot k (after reserve, or after
+// wait when it has been used before), enqueues its copy on `up.s` and calls sent(k).  One thread per slot may do so at a time.  The
+// holder waits for the stream before the staging memory goes.
+struct UploadRing {
+    SideStream up;
+    std::vector<PinnedStage> slots;
+    UploadRing() = default;
+    UploadRing(const UploadRing &) = delete;
+    UploadRing &operator=(const UploadRing &) = delete;
+    ~UploadRing() { if (up.s) (void)hipStreamSynchronize(up.s); }
+    hipError_t open(size_t n_slots) { slots = std::vector<PinnedStage>(n_slots); return up.create(); }
+    hipError_t wait(size_t k) const { return hipEventSynchronize(slots[k].moved); }      // the last copy out of slot k
+    hipError_t sent(size_t k) const { return hipEventRecord(slots[k].moved, up.s); }
+};
+
+// A target database under construction (and the prefilter's masked view of it): freed unless the context takes it
+struct DbBuild {
+    DeviceDb db;
+    uint8_t *masked = nullptr;
+    DbBuild() = default;
+    DbBuild(const DbBuild &) = delete;
+    DbBuild &operator=(const DbBuild &) = delete;
+    ~DbBuild() { dev_free(db.res); dev_free(db.off4); dev_free(db.len); dev_free(masked); }
+    DeviceDb take_db() { DeviceDb d = db; db = DeviceDb(); return d; }
+    uint8_t *take_masked() { uint8_t *m = masked; masked = nullptr; return m; }
 };
 
 template <typename T>

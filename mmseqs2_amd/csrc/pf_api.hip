@@ -290,7 +290,7 @@ extern "C" int mmgpu_host_index_build(const uint8_t *residues, const uint64_t *s
 // ---------------------------------------------------------------------------------------------------------
 // tables every QueryMatcher gets (score matrices, cumulative counts, ungapped matrix): shared by the two ways of
 // obtaining the index (host arrays / built in HBM).  `from_host` = validate and copy the host index as well.
-static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, PfIndex **out) {
+static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, std::unique_ptr<PfIndex> &out) {
     if (!c || !ix) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: NULL argument");
     if (!c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_pf_load_index: load the targets (SequenceLookup) first");
     const bool tables = ix->score3 != nullptr && ix->index3 != nullptr;    // without them: exact k-mer matching only
@@ -314,7 +314,7 @@ static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, PfIn
     }
     HIP_TRY(hipSetDevice(c->device));
     pf_index_free(c);
-    PfIndex *P = new PfIndex();
+    std::unique_ptr<PfIndex> P(new PfIndex());
     P->k = ix->kmer_size;
     P->alphabet = ix->alphabet;
     P->kalph = ix->alphabet - 1;
@@ -327,13 +327,12 @@ static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, PfIn
     P->n_entries = from_host ? ix->n_entries : 0;
     P->has_tables = tables;
     const size_t n3 = P->n3;
-    if (tables && ix->row3 < n3) { delete P; return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: row3 smaller than kalph^3"); }
-#define P_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { delete P; return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
+    if (tables && ix->row3 < n3) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: row3 smaller than kalph^3");
     if (tables) {
-        P_TRY(P->d_s3.alloc(n3 * n3 * sizeof(int16_t)));
-        P_TRY(P->d_i3.alloc(n3 * n3 * sizeof(uint32_t)));
-        P_TRY(hipMemcpy2D(P->d_s3.p, n3 * sizeof(int16_t), ix->score3, ix->row3 * sizeof(int16_t), n3 * sizeof(int16_t), n3, hipMemcpyHostToDevice));
-        P_TRY(hipMemcpy2D(P->d_i3.p, n3 * sizeof(uint32_t), ix->index3, ix->row3 * sizeof(uint32_t), n3 * sizeof(uint32_t), n3, hipMemcpyHostToDevice));
+        HIP_TRY(P->d_s3.alloc(n3 * n3 * sizeof(int16_t)));
+        HIP_TRY(P->d_i3.alloc(n3 * n3 * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy2D(P->d_s3.p, n3 * sizeof(int16_t), ix->score3, ix->row3 * sizeof(int16_t), n3 * sizeof(int16_t), n3, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy2D(P->d_i3.p, n3 * sizeof(uint32_t), ix->index3, ix->row3 * sizeof(uint32_t), n3 * sizeof(uint32_t), n3, hipMemcpyHostToDevice));
     }
     // cumulative counts per row: #entries with score >= c is one lookup instead of a binary search in the row
     auto build_cum = [&](const int16_t *score, size_t row_stride, size_t n, DevBuf &dst, uint32_t *w_out, int32_t *min_out) -> int {
@@ -362,17 +361,17 @@ static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, PfIn
     };
     if (tables) {
         const int rc = build_cum(ix->score3, ix->row3, n3, P->d_cum3, &P->cum_w, &P->score_min);
-        if (rc) { delete P; return fail(rc == 1 ? MMGPU_ERR_ARG : MMGPU_ERR_HIP, rc == 1 ? "mmgpu_pf_load_index: score3 rows are not sorted by descending score" : "mmgpu_pf_load_index: upload failed"); }
+        if (rc) return fail(rc == 1 ? MMGPU_ERR_ARG : MMGPU_ERR_HIP, rc == 1 ? "mmgpu_pf_load_index: score3 rows are not sorted by descending score" : "mmgpu_pf_load_index: upload failed");
     }
     if (tables && P->k != 6) {      // k = 5: (2, 3), k = 7: (2, 2, 3) - KmerGenerator::setDivideStrategy
         const size_t n2 = (size_t)P->kalph * P->kalph;
-        if (ix->row2 < n2) { delete P; return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: row2 smaller than kalph^2"); }
-        P_TRY(P->d_s2.alloc(n2 * n2 * sizeof(int16_t)));
-        P_TRY(P->d_i2.alloc(n2 * n2 * sizeof(uint32_t)));
-        P_TRY(hipMemcpy2D(P->d_s2.p, n2 * sizeof(int16_t), ix->score2, ix->row2 * sizeof(int16_t), n2 * sizeof(int16_t), n2, hipMemcpyHostToDevice));
-        P_TRY(hipMemcpy2D(P->d_i2.p, n2 * sizeof(uint32_t), ix->index2, ix->row2 * sizeof(uint32_t), n2 * sizeof(uint32_t), n2, hipMemcpyHostToDevice));
+        if (ix->row2 < n2) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: row2 smaller than kalph^2");
+        HIP_TRY(P->d_s2.alloc(n2 * n2 * sizeof(int16_t)));
+        HIP_TRY(P->d_i2.alloc(n2 * n2 * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy2D(P->d_s2.p, n2 * sizeof(int16_t), ix->score2, ix->row2 * sizeof(int16_t), n2 * sizeof(int16_t), n2, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy2D(P->d_i2.p, n2 * sizeof(uint32_t), ix->index2, ix->row2 * sizeof(uint32_t), n2 * sizeof(uint32_t), n2, hipMemcpyHostToDevice));
         const int rc = build_cum(ix->score2, ix->row2, n2, P->d_cum2, &P->cum2_w, &P->score2_min);
-        if (rc) { delete P; return fail(rc == 1 ? MMGPU_ERR_ARG : MMGPU_ERR_HIP, rc == 1 ? "mmgpu_pf_load_index: score2 rows are not sorted by descending score" : "mmgpu_pf_load_index: upload failed"); }
+        if (rc) return fail(rc == 1 ? MMGPU_ERR_ARG : MMGPU_ERR_HIP, rc == 1 ? "mmgpu_pf_load_index: score2 rows are not sorted by descending score" : "mmgpu_pf_load_index: upload failed");
     }
     if (from_host) {
         {
@@ -384,9 +383,9 @@ static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, PfIn
                     off32[z] = (uint32_t)ix->offsets[z];
                 }
             });
-            if (bad_off) { delete P; return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: offsets not monotone / out of range"); }
-            P_TRY(upload(P->d_offsets, off32, nullptr));
-            P_TRY(hipDeviceSynchronize());
+            if (bad_off) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: offsets not monotone / out of range");
+            HIP_TRY(upload(P->d_offsets, off32, nullptr));
+            HIP_TRY(hipDeviceSynchronize());
         }
         {
             const size_t ne = (size_t)ix->n_entries;
@@ -409,44 +408,42 @@ static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, PfIn
                     ent[e] = (uint64_t)id | ((uint64_t)pj << 32);
                 }
             });
-            if (bad_ent) { delete P; return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: index entry names a target that is not loaded"); }
-            P_TRY(upload(P->d_entries, ent, nullptr));
-            P_TRY(hipDeviceSynchronize());
+            if (bad_ent) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: index entry names a target that is not loaded");
+            HIP_TRY(upload(P->d_entries, ent, nullptr));
+            HIP_TRY(hipDeviceSynchronize());
         }
     }
     P->h_mat.assign(ix->ungapped_mat, ix->ungapped_mat + ix->alphabet * ix->alphabet);
-    P_TRY(upload(P->d_mat, P->h_mat, nullptr));
-    P_TRY(hipDeviceSynchronize());
-#undef P_TRY
-    *out = P;
+    HIP_TRY(upload(P->d_mat, P->h_mat, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    out = std::move(P);
     return MMGPU_OK;
 }
 
 
 extern "C" int mmgpu_pf_load_index(mmgpu_ctx *c, const mmgpu_pf_index *ix) {
-    PfIndex *P = nullptr;
-    const int rc = pf_setup(c, ix, true, &P);
+    std::unique_ptr<PfIndex> P;
+    const int rc = pf_setup(c, ix, true, P);
     if (rc != MMGPU_OK) return rc;
-    HIP_TRY(pf_index_bitmap(c, P));
-    HIP_TRY(pf_index_cofs(c, P));
-    c->pf = P;
+    HIP_TRY(pf_index_bitmap(c, P.get()));
+    HIP_TRY(pf_index_cofs(c, P.get()));
+    c->pf = P.release();
     return MMGPU_OK;
 }
 
 // IndexBuilder::fillDatabase on the device (ix_kernels.hip): count, scan, scatter, sort every list by seqId.
 extern "C" int mmgpu_pf_build_index(mmgpu_ctx *c, const mmgpu_pf_index *ix, const int16_t *kmer_submat, int kmer_thr) {
     if (!kmer_submat) return fail(MMGPU_ERR_ARG, "mmgpu_pf_build_index: NULL argument");
-    PfIndex *P = nullptr;
-    int rc = pf_setup(c, ix, false, &P);
+    std::unique_ptr<PfIndex> P;
+    const int rc = pf_setup(c, ix, false, P);
     if (rc != MMGPU_OK) return rc;
     hipStream_t s = c->stream;
-#define X_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { delete P; return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
     const uint64_t table = P->table;
-    if (table >= 0xFFFFFFF0ull) { delete P; return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_build_index: k-mer table too large"); }
+    if (table >= 0xFFFFFFF0ull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_build_index: k-mer table too large");
     DevBuf d_counts, d_scratch, d_chunk_off, d_chunk_tot, d_chunk_base, d_tmp, d_long, d_nlong;
-    X_TRY(d_counts.alloc(table * 4));
-    X_TRY(P->d_offsets.alloc((table + 1) * 4));
-    X_TRY(hipMemsetAsync(d_counts.p, 0, table * 4, s));
+    HIP_TRY(d_counts.alloc(table * 4));
+    HIP_TRY(P->d_offsets.alloc((table + 1) * 4));
+    HIP_TRY(hipMemsetAsync(d_counts.p, 0, table * 4, s));
     IxArgs A;
     memset(&A, 0, sizeof(A));
     A.t_res = c->pf_res();
@@ -464,55 +461,54 @@ extern "C" int mmgpu_pf_build_index(mmgpu_ctx *c, const mmgpu_pf_index *ix, cons
         // one uint32 per residue slot of the packed target array
         uint64_t slots = 0;
         for (uint32_t l : c->h_len) slots += ((uint64_t)l + 3) / 4 * 4;
-        X_TRY(d_scratch.alloc((slots + 64) * 4));
+        HIP_TRY(d_scratch.alloc((slots + 64) * 4));
     }
     A.scratch = d_scratch.as<uint32_t>();
-    X_TRY(launch_ix_target(A, false, s));
+    HIP_TRY(launch_ix_target(A, false, s));
     // offsets = exclusive scan of the counts: 64 K chunks, chunk totals summed on the host
     const uint32_t CH = 65536;
     const uint32_t nch = (uint32_t)((table + CH - 1) / CH);
     std::vector<uint32_t> choff(nch + 1);
     for (uint32_t z = 0; z <= nch; z++) choff[z] = (uint32_t)std::min<uint64_t>((uint64_t)z * CH, table);
     std::vector<uint64_t> chtot(nch), chbase(nch);
-    X_TRY(upload(d_chunk_off, choff, s));
-    X_TRY(d_chunk_tot.alloc((size_t)nch * 8));
-    X_TRY(d_chunk_base.alloc((size_t)nch * 8));
-    X_TRY(launch_pf_scan(d_counts.as<uint32_t>(), d_chunk_off.as<uint32_t>(), nch, nullptr, nullptr, d_chunk_tot.as<uint64_t>(), s));
-    X_TRY(hipMemcpyAsync(chtot.data(), d_chunk_tot.p, (size_t)nch * 8, hipMemcpyDeviceToHost, s));
-    X_TRY(hipStreamSynchronize(s));
+    HIP_TRY(upload(d_chunk_off, choff, s));
+    HIP_TRY(d_chunk_tot.alloc((size_t)nch * 8));
+    HIP_TRY(d_chunk_base.alloc((size_t)nch * 8));
+    HIP_TRY(launch_pf_scan(d_counts.as<uint32_t>(), d_chunk_off.as<uint32_t>(), nch, nullptr, nullptr, d_chunk_tot.as<uint64_t>(), s));
+    HIP_TRY(hipMemcpyAsync(chtot.data(), d_chunk_tot.p, (size_t)nch * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     uint64_t run = 0;
     for (uint32_t z = 0; z < nch; z++) { chbase[z] = run; run += chtot[z]; }
-    if (run >= 0xFFFFFFFFull) { delete P; return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_build_index: >= 2^32 index entries per shard"); }
+    if (run >= 0xFFFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_build_index: >= 2^32 index entries per shard");
     P->n_entries = run;
-    X_TRY(hipMemcpyAsync(d_chunk_base.p, chbase.data(), (size_t)nch * 8, hipMemcpyHostToDevice, s));
-    X_TRY(launch_pf_scan(d_counts.as<uint32_t>(), d_chunk_off.as<uint32_t>(), nch, d_chunk_base.as<uint64_t>(), P->d_offsets.as<uint32_t>(), nullptr, s));
-    X_TRY(d_tmp.alloc(std::max<uint64_t>(run, 1) * 8));
-    X_TRY(P->d_entries.alloc(std::max<uint64_t>(run, 1) * 8));
-    X_TRY(hipMemsetAsync(d_counts.p, 0, table * 4, s));
+    HIP_TRY(hipMemcpyAsync(d_chunk_base.p, chbase.data(), (size_t)nch * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_pf_scan(d_counts.as<uint32_t>(), d_chunk_off.as<uint32_t>(), nch, d_chunk_base.as<uint64_t>(), P->d_offsets.as<uint32_t>(), nullptr, s));
+    HIP_TRY(d_tmp.alloc(std::max<uint64_t>(run, 1) * 8));
+    HIP_TRY(P->d_entries.alloc(std::max<uint64_t>(run, 1) * 8));
+    HIP_TRY(hipMemsetAsync(d_counts.p, 0, table * 4, s));
     A.offsets = P->d_offsets.as<uint32_t>();
     A.entries = d_tmp.as<uint64_t>();
-    X_TRY(launch_ix_target(A, true, s));
+    HIP_TRY(launch_ix_target(A, true, s));
     IxSortArgs S;
     S.table = table;
     S.offsets = P->d_offsets.as<uint32_t>();
     S.src = d_tmp.as<uint64_t>();
     S.dst = P->d_entries.as<uint64_t>();
     S.long_cap = (uint32_t)(run / 17 + 1);
-    X_TRY(d_long.alloc((size_t)S.long_cap * 4));
-    X_TRY(d_nlong.alloc(4));
-    X_TRY(hipMemsetAsync(d_nlong.p, 0, 4, s));
+    HIP_TRY(d_long.alloc((size_t)S.long_cap * 4));
+    HIP_TRY(d_nlong.alloc(4));
+    HIP_TRY(hipMemsetAsync(d_nlong.p, 0, 4, s));
     S.long_lists = d_long.as<uint32_t>();
     S.n_long = d_nlong.as<uint32_t>();
-    X_TRY(launch_ix_sort_short(S, s));
+    HIP_TRY(launch_ix_sort_short(S, s));
     uint32_t n_long = 0;
-    X_TRY(hipMemcpyAsync(&n_long, d_nlong.p, 4, hipMemcpyDeviceToHost, s));
-    X_TRY(hipStreamSynchronize(s));
-    X_TRY(launch_ix_sort_long(S, std::min(n_long, S.long_cap), s));
-    X_TRY(hipStreamSynchronize(s));
-#undef X_TRY
-    HIP_TRY(pf_index_bitmap(c, P));
-    HIP_TRY(pf_index_cofs(c, P));
-    c->pf = P;
+    HIP_TRY(hipMemcpyAsync(&n_long, d_nlong.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(launch_ix_sort_long(S, std::min(n_long, S.long_cap), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(pf_index_bitmap(c, P.get()));
+    HIP_TRY(pf_index_cofs(c, P.get()));
+    c->pf = P.release();
     return MMGPU_OK;
 }
 
@@ -611,15 +607,36 @@ struct PfBatchFree {
 };
 }  // namespace
 
-extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const mmgpu_pf_query *qs, uint32_t nq,
-                                mmgpu_pf_batch_t **out) {
-    if (!c || !par || !out || (!qs && nq)) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: NULL argument");
-    if (!c->pf || !c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_pf_prepare: no index loaded");
+namespace {
+// One call of mmgpu_pf_prepare: its arguments, the batch, and the host arrays its three steps hand to one another
+struct PfPrepare {
+    mmgpu_ctx *c;
+    const mmgpu_pf_params *par;
+    const mmgpu_pf_query *qs;
+    uint32_t nq;
+    const PfIndex &P;
+    mmgpu_pf_batch_t *b = nullptr;
+
+    bool exchange = false, any_prof = false;
+    uint64_t db_size = 0, tot = 0;
+    uint32_t max_hits = 0, bins = 0;
+    std::vector<uint8_t> qres, qkind, qisprof, pletter;
+    std::vector<int16_t> qthr, pscore;
+    std::vector<int8_t> qcorr, qrows;
+    std::vector<uint32_t> qident;
+    std::vector<int32_t> qself;
+
+    int check_params();
+    int size_batch();
+    int pack_queries();
+    int upload_and_allocate();
+};
+
+int PfPrepare::check_params() {
     // (with kmer_score every element has a count >= 1, so a cut at 0 is the cut at 1: `mmseqs cluster` runs its first
     // prefilter with --diag-score 0 --min-ungapped-score 0, Cluster.cpp:225-227)
     if (par->min_diag_score < 1 && !par->kmer_score) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: min_diag_score must be >= 1");
     if (par->max_hits < 1) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: max_hits must be >= 1");
-    const PfIndex &P = *c->pf;
     if (!par->exact_kmer && !P.has_tables) return fail(MMGPU_ERR_STATE, "mmgpu_pf_prepare: the index was loaded without similar-k-mer tables (exact k-mer matching only)");
     if (par->nucleotide && c->shard.on) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: nucleotide searches on a sharded database are not implemented");
     if (par->kmer_score) {     // --diag-score 0
@@ -628,22 +645,23 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
             if (qs[i].profile_score) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: kmer_score (--diag-score 0) with profile queries is not implemented");
     }
     // a shard of a multi-GPU run answers for the whole database: list length and cache bins as in the unsplit run
-    const bool exchange = c->shard.on;
-    const uint64_t db_size = exchange ? c->shard.global_n : c->db.n;
-    const uint32_t max_hits = (uint32_t)std::min<uint64_t>(par->max_hits, db_size);
+    exchange = c->shard.on;
+    db_size = exchange ? c->shard.global_n : c->db.n;
+    max_hits = (uint32_t)std::min<uint64_t>(par->max_hits, db_size);
     if (max_hits > (uint32_t)PF_MAX_HITS_BIG) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: max_hits above 131072 is not implemented");
     if (max_hits > (uint32_t)PF_MAX_HITS && exchange) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: max_hits above 4096 on a sharded database is not implemented");
     if (par->ref_bins && (par->ref_bins < 2 || par->ref_bins > 2048 || (par->ref_bins & (par->ref_bins - 1))))
         return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: ref_bins must be a power of two in [2, 2048]");
-    uint32_t bins = 1;
+    bins = 1;
     while ((uint64_t)bins * PF_IDS_PER_BIN < c->db.n) bins <<= 1;
     if (bins > 2048) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: more than 8M targets per shard");
-    HIP_TRY(hipSetDevice(c->device));
-
-    if (c->pf && c->pf->kbase != c->pf->kalph && !par->exact_kmer)
+    if (P.kbase != P.kalph && !par->exact_kmer)
         return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: an index over the full alphabet (profile targets) serves exact k-mer matching only");
-    std::unique_ptr<mmgpu_pf_batch_t, PfBatchFree> owner(new mmgpu_pf_batch_t(), PfBatchFree{c});
-    mmgpu_pf_batch_t *b = owner.get();
+    return MMGPU_OK;
+}
+
+// the batch's own numbers, the query offsets, and the host arrays at their sizes
+int PfPrepare::size_batch() {
     // the batch's buffers come from / go back to the context's block cache: a process prepares batch after batch (and, like the
     // drop-in's prefilter hook, the next one while this one runs), a fresh hipMalloc costs 25 - 40 ms per GB on some hosts
     for (DevBuf *d : {&b->d_qres, &b->d_qthr, &b->d_qcorr, &b->d_qoff, &b->d_qident, &b->d_qself, &b->d_qkind, &b->d_qisprof, &b->d_pscore,
@@ -669,7 +687,6 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
     // whichever elements survive) and the caller re-runs it unsplit
     if (exchange) b->max_db_matches = std::max<uint64_t>(1, b->max_db_matches / std::max<uint32_t>(1, c->shard.n_shards));
     b->q_off.assign(nq + 1, 0);
-    uint64_t tot = 0;
     for (uint32_t i = 0; i < nq; i++) {
         if (!qs[i].q || qs[i].qlen == 0) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: bad query");
         if (qs[i].qlen > 65535) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: query longer than 65535 (Parameters.h:271)");
@@ -690,13 +707,12 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
         any_long_on_device = any_long_on_device || (is_long && !declined);
     }
     b->long_queries_on_device = any_long_on_device;
-    std::vector<uint8_t> qres(tot + 64, 0);    // + slack: the ungapped kernel reads whole dwords
-    std::vector<int16_t> qthr(tot, -1);
-    std::vector<int8_t> qcorr(tot + 64, 0);
-    std::vector<uint32_t> qident(std::max<uint32_t>(nq, 1), 0xFFFFFFFFu);
-    std::vector<int32_t> qself(std::max<uint32_t>(nq, 1), 0);
+    qres.assign(tot + 64, 0);    // + slack: the ungapped kernel reads whole dwords
+    qthr.assign(tot, -1);
+    qcorr.assign(tot + 64, 0);
+    qident.assign(std::max<uint32_t>(nq, 1), 0xFFFFFFFFu);
+    qself.assign(std::max<uint32_t>(nq, 1), 0);
     // profile queries: per-position kind flag, the 20 sorted scores / letters of every position, the ungapped score rows
-    bool any_prof = false;
     for (uint32_t i = 0; i < nq; i++) {
         if (!qs[i].profile_score && !qs[i].profile_index && !qs[i].profile) continue;
         if (!qs[i].profile_score || !qs[i].profile_index || !qs[i].profile || qs[i].profile_row < (uint32_t)PF_PROF_LETTERS)
@@ -704,9 +720,6 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
         if (P.kalph != PF_PROF_LETTERS) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_prepare: profile queries need the 20-letter k-mer alphabet");
         any_prof = true;
     }
-    std::vector<uint8_t> qkind, qisprof, pletter;
-    std::vector<int16_t> pscore;
-    std::vector<int8_t> qrows;
     if (any_prof) {
         qkind.assign(tot + 64, 0);
         qisprof.assign(std::max<uint32_t>(nq, 1), 0);
@@ -715,6 +728,11 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
         qrows.assign((tot + 64) * PF_PROW, 0);
     }
     b->any_profile = any_prof;
+    return MMGPU_OK;
+}
+
+// what the reference computes per query before it matches: thresholds, correction scores, self score, profile rows
+int PfPrepare::pack_queries() {
     std::atomic<bool> bad(false);
     parallel_for(nq, [&](size_t a, size_t e) {
         for (size_t i = a; i < e; i++) {
@@ -775,6 +793,10 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
         }
     });
     if (bad) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: query residue code >= alphabet");
+    return MMGPU_OK;
+}
+
+int PfPrepare::upload_and_allocate() {
     hipStream_t s = c->stream;
     HIP_TRY(upload(b->d_qres, qres, s));
     HIP_TRY(upload(b->d_qthr, qthr, s));
@@ -823,6 +845,22 @@ extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const 
     }
     for (auto &e : b->ev) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipStreamSynchronize(s));
+    return MMGPU_OK;
+}
+}  // namespace
+
+extern "C" int mmgpu_pf_prepare(mmgpu_ctx *c, const mmgpu_pf_params *par, const mmgpu_pf_query *qs, uint32_t nq,
+                                mmgpu_pf_batch_t **out) {
+    if (!c || !par || !out || (!qs && nq)) return fail(MMGPU_ERR_ARG, "mmgpu_pf_prepare: NULL argument");
+    if (!c->pf || !c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_pf_prepare: no index loaded");
+    PfPrepare S{c, par, qs, nq, *c->pf};
+    if (int e = S.check_params()) return e;
+    HIP_TRY(hipSetDevice(c->device));
+    std::unique_ptr<mmgpu_pf_batch_t, PfBatchFree> owner(new mmgpu_pf_batch_t(), PfBatchFree{c});
+    S.b = owner.get();
+    if (int e = S.size_batch()) return e;
+    if (int e = S.pack_queries()) return e;
+    if (int e = S.upload_and_allocate()) return e;
     *out = owner.release();
     return MMGPU_OK;
 }
@@ -1842,16 +1880,14 @@ static uint64_t align4k(uint64_t x) { return (x + 4095ull) & ~4095ull; }
 static int write_section(FILE *f, uint64_t at, const void *dev, size_t bytes) {
     if (fseeko(f, (off_t)at, SEEK_SET) != 0) return fail(MMGPU_ERR_ARG, "mmgpu_db_save: seek failed");
     const size_t chunk = 64ull << 20;
-    uint8_t *stage = nullptr;
-    HIP_TRY(hipHostMalloc((void **)&stage, std::min(chunk, std::max<size_t>(bytes, 1)), hipHostMallocDefault));
-    int rc = MMGPU_OK;
-    for (size_t o = 0; o < bytes && rc == MMGPU_OK; o += chunk) {
+    PinnedStage stage;
+    HIP_TRY(stage.reserve(std::min(chunk, std::max<size_t>(bytes, 1)), false));
+    for (size_t o = 0; o < bytes; o += chunk) {
         const size_t m = std::min(chunk, bytes - o);
-        if (hipMemcpy(stage, static_cast<const uint8_t *>(dev) + o, m, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MMGPU_ERR_HIP, "mmgpu_db_save: device read failed");
-        else if (fwrite(stage, 1, m, f) != m) rc = fail(MMGPU_ERR_ARG, "mmgpu_db_save: write failed (disk full?)");
+        if (hipMemcpy(stage.p, static_cast<const uint8_t *>(dev) + o, m, hipMemcpyDeviceToHost) != hipSuccess) return fail(MMGPU_ERR_HIP, "mmgpu_db_save: device read failed");
+        if (fwrite(stage.p, 1, m, f) != m) return fail(MMGPU_ERR_ARG, "mmgpu_db_save: write failed (disk full?)");
     }
-    (void)hipHostFree(stage);
-    return rc;
+    return MMGPU_OK;
 }
 
 // file -> device: DB_READERS host threads, each with a pinned buffer of its own, take the chunks of a section in turn - pread (the
@@ -1860,21 +1896,22 @@ static int write_section(FILE *f, uint64_t at, const void *dev, size_t bytes) {
 // most of the 0.24 s the 2.97 GB of a 1 M-target database took.)
 constexpr int DB_READERS = 8;
 constexpr size_t DB_CHUNK = 16ull << 20;
-static int upload_section(int device, void *dev, int fd, uint64_t at, size_t bytes, hipStream_t up, uint8_t *const stage[DB_READERS], hipEvent_t const moved[DB_READERS]) {
+static int upload_section(int device, void *dev, int fd, uint64_t at, size_t bytes, const UploadRing &ring) {
     const size_t n_chunks = (bytes + DB_CHUNK - 1) / DB_CHUNK;
     std::atomic<int> bad{0};
     auto reader = [&](int t) {
         if (hipSetDevice(device) != hipSuccess) { bad = 2; return; }
         for (size_t j = (size_t)t; j < n_chunks && !bad; j += DB_READERS) {
             const size_t o = j * DB_CHUNK, m = std::min(DB_CHUNK, bytes - o);
-            if (hipEventSynchronize(moved[t]) != hipSuccess) { bad = 2; return; }
+            if (ring.wait((size_t)t) != hipSuccess) { bad = 2; return; }
+            uint8_t *stage = ring.slots[(size_t)t].p;
             for (size_t a = 0; a < m;) {
-                const ssize_t got = pread(fd, stage[t] + a, m - a, (off_t)(at + o + a));
+                const ssize_t got = pread(fd, stage + a, m - a, (off_t)(at + o + a));
                 if (got <= 0) { bad = 1; return; }
                 a += (size_t)got;
             }
-            if (hipMemcpyAsync(static_cast<uint8_t *>(dev) + o, stage[t], m, hipMemcpyHostToDevice, up) != hipSuccess ||
-                hipEventRecord(moved[t], up) != hipSuccess) { bad = 2; return; }
+            if (hipMemcpyAsync(static_cast<uint8_t *>(dev) + o, stage, m, hipMemcpyHostToDevice, ring.up.s) != hipSuccess ||
+                ring.sent((size_t)t) != hipSuccess) { bad = 2; return; }
         }
     };
     const int nt = (int)std::min<size_t>(DB_READERS, n_chunks);
@@ -2015,41 +2052,22 @@ extern "C" int mmgpu_db_load(mmgpu_ctx *c, const char *path, uint64_t source_fin
     // (what the context holds stays until the file's content has been uploaded and checked: a file that turns out damaged leaves
     // the context as it was)
     const size_t nn = std::max<uint32_t>(h.n, 1);
-    DeviceDb db;
-    uint8_t *masked = nullptr;
-    uint8_t *stage[DB_READERS] = {};
-    hipEvent_t moved[DB_READERS] = {};
-    hipStream_t up = nullptr;
-    PfIndex *P = nullptr;
-    auto drop = [&]() {
-        for (int k = 0; k < DB_READERS; k++) {
-            if (stage[k]) (void)hipHostFree(stage[k]);
-            if (moved[k]) (void)hipEventDestroy(moved[k]);
-        }
-        if (up) (void)hipStreamDestroy(up);
-    };
-    auto undo = [&]() {
-        drop();
-        dev_free(db.res); dev_free(db.off4); dev_free(db.len);
-        if (masked) dev_free(masked);
-        delete P;
-    };
-#define L_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { undo(); return fail(MMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
-#define L_RC(expr) do { const int r__ = (expr); if (r__ != MMGPU_OK) { undo(); return r__; } } while (0)
-    L_TRY(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
-    for (int k = 0; k < DB_READERS; k++) {
-        L_TRY(hipHostMalloc((void **)&stage[k], DB_CHUNK, hipHostMallocDefault));
-        L_TRY(hipEventCreateWithFlags(&moved[k], hipEventDisableTiming));
-    }
-    L_TRY(dev_malloc_ctx(c, (void **)&db.res, (size_t)h.res_bytes));
-    L_TRY(dev_malloc_ctx(c, (void **)&db.off4, nn * 4));
-    L_TRY(dev_malloc_ctx(c, (void **)&db.len, nn * 4));
-    L_RC(upload_section(c->device, db.off4, fd, h.at_off4, nn * 4, up, stage, moved));
-    L_RC(upload_section(c->device, db.len, fd, h.at_len, nn * 4, up, stage, moved));
-    L_RC(upload_section(c->device, db.res, fd, h.at_res, (size_t)h.res_bytes, up, stage, moved));
+    DbBuild nb;
+    std::unique_ptr<PfIndex> P;
+    UploadRing ring;      // (last: its stream has drained before a failure frees what it copies into)
+    DeviceDb &db = nb.db;
+    HIP_TRY(ring.open(DB_READERS));
+    for (PinnedStage &x : ring.slots) HIP_TRY(x.reserve(DB_CHUNK));
+    hipStream_t up = ring.up.s;
+    HIP_TRY(dev_malloc_ctx(c, (void **)&db.res, (size_t)h.res_bytes));
+    HIP_TRY(dev_malloc_ctx(c, (void **)&db.off4, nn * 4));
+    HIP_TRY(dev_malloc_ctx(c, (void **)&db.len, nn * 4));
+    if (int e = upload_section(c->device, db.off4, fd, h.at_off4, nn * 4, ring)) return e;
+    if (int e = upload_section(c->device, db.len, fd, h.at_len, nn * 4, ring)) return e;
+    if (int e = upload_section(c->device, db.res, fd, h.at_res, (size_t)h.res_bytes, ring)) return e;
     if (h.has_masked && want_index) {      // (the masked view serves the prefilter only: a caller that asks for the targets alone gets them alone)
-        L_TRY(dev_malloc_ctx(c, (void **)&masked, (size_t)h.res_bytes));
-        L_RC(upload_section(c->device, masked, fd, h.at_masked, (size_t)h.res_bytes, up, stage, moved));
+        HIP_TRY(dev_malloc_ctx(c, (void **)&nb.masked, (size_t)h.res_bytes));
+        if (int e = upload_section(c->device, nb.masked, fd, h.at_masked, (size_t)h.res_bytes, ring)) return e;
     }
     db.n = h.n;
     db.res_bytes = (size_t)h.res_bytes;
@@ -2057,24 +2075,22 @@ extern "C" int mmgpu_db_load(mmgpu_ctx *c, const char *path, uint64_t source_fin
     db.total_residues = h.total_residues;
     db.alphabet = (int)h.alphabet;
     std::vector<uint32_t> hlen(h.n);
-    if (h.n && pread(fd, hlen.data(), (size_t)h.n * 4, (off_t)h.at_len) != (ssize_t)((size_t)h.n * 4)) { undo(); return fail(MMGPU_ERR_STATE, "mmgpu_db_load: short read (file truncated?)"); }
-    L_TRY(hipStreamSynchronize(up));
+    if (h.n && pread(fd, hlen.data(), (size_t)h.n * 4, (off_t)h.at_len) != (ssize_t)((size_t)h.n * 4)) return fail(MMGPU_ERR_STATE, "mmgpu_db_load: short read (file truncated?)");
+    HIP_TRY(hipStreamSynchronize(up));
     // what arrived is what was saved, and it has the properties the kernels rely on
     DevBuf d_chk;
-    L_TRY(d_chk.alloc(8));
+    HIP_TRY(d_chk.alloc(8));
     auto section_ok = [&](const void *dev, size_t bytes, int which) {
         uint64_t sum = 0;
         return db_section_checksum(dev, bytes, d_chk.as<unsigned long long>(), &sum, up) == hipSuccess && sum == h.sum[which];
     };
     if (!section_ok(db.off4, nn * 4, 0) || !section_ok(db.len, nn * 4, 1) || !section_ok(db.res, (size_t)h.res_bytes, 2) ||
-        (masked && !section_ok(masked, (size_t)h.res_bytes, 3))) {
-        undo();
+        (nb.masked && !section_ok(nb.masked, (size_t)h.res_bytes, 3)))
         return fail(MMGPU_ERR_STATE, "mmgpu_db_load: a section's checksum differs from the one in the header (damaged file)");
-    }
     {
         uint32_t bad = 0;
-        L_TRY(db_validate_layout(db.off4, db.len, h.n, h.res_bytes, h.max_len, nullptr, 0, nullptr, 0, d_chk.as<uint32_t>(), &bad, up));
-        if (bad) { undo(); return fail(MMGPU_ERR_STATE, "mmgpu_db_load: a target of the file lies outside its residue block"); }
+        HIP_TRY(db_validate_layout(db.off4, db.len, h.n, h.res_bytes, h.max_len, nullptr, 0, nullptr, 0, d_chk.as<uint32_t>(), &bad, up));
+        if (bad) return fail(MMGPU_ERR_STATE, "mmgpu_db_load: a target of the file lies outside its residue block");
     }
     // the context takes the new database (pf_setup checks the alphabet against it); the old one is kept aside until the index is in
     DeviceDb old_db = c->db;
@@ -2086,13 +2102,12 @@ extern "C" int mmgpu_db_load(mmgpu_ctx *c, const char *path, uint64_t source_fin
     const bool old_shard = c->shard.on;
     c->pf = nullptr;
     c->shard.on = false;
-    c->db = db;
-    db = DeviceDb();
-    c->pf_masked_res = masked;
-    masked = nullptr;
+    c->db = nb.take_db();
+    c->pf_masked_res = nb.take_masked();
     c->h_len.swap(hlen);
     c->mean_len = h.mean_len;
-    auto back_to_old = [&]() {      // (the index failed: the new database goes, the old one is the context's again)
+    auto back_to_old = [&](int rc) {      // (the index failed: the new database goes, the old one is the context's again)
+        (void)hipStreamSynchronize(up);   // (an upload of the index that failed half-way may have copies in flight)
         db_release(c);
         c->db = old_db;
         c->pf_masked_res = old_masked;
@@ -2100,17 +2115,18 @@ extern "C" int mmgpu_db_load(mmgpu_ctx *c, const char *path, uint64_t source_fin
         c->h_len.swap(old_hlen);
         c->mean_len = old_mean;
         c->shard.on = old_shard;
+        return rc;
     };
     if (want_index) {
-        int rc2 = pf_setup(c, tables, false, &P);
+        int rc2 = pf_setup(c, tables, false, P);
         if (rc2 == MMGPU_OK && (P->table != h.table || P->kbase != h.kbase)) rc2 = fail(MMGPU_ERR_STATE, "mmgpu_db_load: k-mer table size differs from the file's index");
-        if (rc2 != MMGPU_OK) { drop(); delete P; back_to_old(); return rc2; }
+        if (rc2 != MMGPU_OK) return back_to_old(rc2);
         P->n_entries = h.n_entries;
         hipError_t e = P->d_offsets.alloc((P->table + 1) * 4);
         if (e == hipSuccess) e = P->d_entries.alloc(std::max<uint64_t>(P->n_entries, 1) * 8);
         int rc3 = e == hipSuccess ? MMGPU_OK : fail(MMGPU_ERR_HIP, "mmgpu_db_load: out of device memory for the index");
-        if (rc3 == MMGPU_OK) rc3 = upload_section(c->device, P->d_offsets.p, fd, h.at_offsets, (P->table + 1) * 4, up, stage, moved);
-        if (rc3 == MMGPU_OK && P->n_entries) rc3 = upload_section(c->device, P->d_entries.p, fd, h.at_entries, P->n_entries * 8, up, stage, moved);
+        if (rc3 == MMGPU_OK) rc3 = upload_section(c->device, P->d_offsets.p, fd, h.at_offsets, (P->table + 1) * 4, ring);
+        if (rc3 == MMGPU_OK && P->n_entries) rc3 = upload_section(c->device, P->d_entries.p, fd, h.at_entries, P->n_entries * 8, ring);
         if (rc3 == MMGPU_OK && hipStreamSynchronize(up) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: upload failed");
         if (rc3 == MMGPU_OK && (!section_ok(P->d_offsets.p, (P->table + 1) * 4, 4) || !section_ok(P->d_entries.p, P->n_entries * 8, 5)))
             rc3 = fail(MMGPU_ERR_STATE, "mmgpu_db_load: the index's checksum differs from the one in the header (damaged file)");
@@ -2120,11 +2136,10 @@ extern "C" int mmgpu_db_load(mmgpu_ctx *c, const char *path, uint64_t source_fin
                                    P->n_entries, d_chk.as<uint32_t>(), &bad, up) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: layout check failed");
             else if (bad) rc3 = fail(MMGPU_ERR_STATE, "mmgpu_db_load: the file's index is not a k-mer index over these targets (offsets not monotone / entry out of range)");
         }
-        if (rc3 == MMGPU_OK && pf_index_bitmap(c, P) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: bit table failed");
-        if (rc3 == MMGPU_OK && pf_index_cofs(c, P) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: compact offset table failed");
-        if (rc3 != MMGPU_OK) { drop(); delete P; back_to_old(); return rc3; }
-        c->pf = P;
-        P = nullptr;
+        if (rc3 == MMGPU_OK && pf_index_bitmap(c, P.get()) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: bit table failed");
+        if (rc3 == MMGPU_OK && pf_index_cofs(c, P.get()) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: compact offset table failed");
+        if (rc3 != MMGPU_OK) return back_to_old(rc3);
+        c->pf = P.release();
     }
     {   // the old database goes
         (void)hipStreamSynchronize(c->stream);
@@ -2132,9 +2147,6 @@ extern "C" int mmgpu_db_load(mmgpu_ctx *c, const char *path, uint64_t source_fin
         if (old_masked) dev_free(old_masked);
         delete old_pf;
     }
-    drop();
-#undef L_TRY
-#undef L_RC
     return MMGPU_OK;
 }
 

@@ -580,3 +580,64 @@ def test_block_starts_is_the_search_semantics_of_one_call(gpu, matrices, oracle)
             assert (int(got[p]["q_start"]), int(got[p]["t_start"])) == (r["q_start"], r["t_start"]), p
         n_checked += 1
     assert n_sel > 300 and n_checked > 40
+
+
+def _head_launch_workload(matrices, oracle):
+    """92 seeded families (seeds of 90 - 250 residues), one query per family against its 50 members at 80 - 95 % identity: 4600 pairs
+    of one call, of which more than 4096 leave the uint8 range (4515 by the oracle's batch Smith-Waterman for these seeds)"""
+    mat = matrices["blosum62_sw"]
+    sub16 = mat.astype(np.int16)
+    n_fam, members = 92, 50
+    rng = np.random.default_rng(71)
+    sres, soff = wl.random_seqs(rng, n_fam, 170, 45, min_len=90, max_len=250)
+    tres, toff = wl.mutate_many(rng, sres, soff, np.repeat(np.arange(n_fam), members), id_lo=0.8, id_hi=0.95)
+    qres, qoff = wl.mutate_many(rng, sres, soff, np.arange(n_fam), id_lo=0.8, id_hi=0.95)
+    queries = []
+    for f, q in enumerate(wl.split(qres, qoff)):
+        cb = oracle.round_comp_bias(oracle.comp_bias(sub16, matrices["blosum62_pback"], q, 1.0))
+        queries.append(dict(q=q, comp_bias=cb, targets=np.arange(f * members, (f + 1) * members, dtype=np.uint32), min_start_score=0))
+    return mat, queries, tres, toff
+
+
+def test_block_head_launch_equals_the_plain_launches(gpu, matrices, oracle):
+    """4096 or more int16-range sequence pairs in ONE mmgpu_sw_block_backtrace call: the longest of them (one per CU) run in the skewed
+    form on a stream of their own, with buffers of their own, beside launch 1, and are collected after the skewed launch.  The same
+    pairs asked for in calls of at most 2000 indices never take that path: both must answer the same, slot by slot, strings
+    included, and equal the restatement of the crate for the head's pairs and a sample of the others."""
+    mat, queries, tres, toff = _head_launch_workload(matrices, oracle)
+    ts = wl.split(tres, toff)
+    gpu.load_targets(tres, toff, 21)
+    b = gpu.sw_prepare(mat, 11, 1, queries, mode=1)
+    b.run()
+    res = b.fetch()
+    n = len(res)
+    word = (res["word"] == 1) & (res["score"] > 0)
+    n_word = int(word.sum())
+    assert n_word >= 4096, n_word
+    blk, strs = b.block_backtrace(np.arange(n, dtype=np.uint32))
+    parts = [b.block_backtrace(np.arange(lo, min(lo + 2000, n), dtype=np.uint32)) for lo in range(0, n, 2000)]
+    b.free()
+    plain = np.concatenate([p[0] for p in parts])
+    plain_strs = [s for p in parts for s in p[1]]
+    for f in ("status", "q_start", "t_start", "ident", "bt_len"):
+        assert np.array_equal(blk[f], plain[f]), (f, np.nonzero(blk[f] != plain[f])[0][:8])
+    assert strs == plain_strs, next(k for k in range(n) if strs[k] != plain_strs[k])
+    assert (blk["status"] != 2).all(), np.nonzero(blk["status"] == 2)[0][:8]      # MMGPU_BLOCK_TOO_LARGE
+    assert (blk["status"][~word] == 3).all() and (blk["status"][word] != 3).all()
+    # the head (the 256 longest on 256 CUs; ties in length fall either way) and a seeded sample of the others, against the restatement
+    wi = np.nonzero(word)[0]
+    length = res["q_end"][wi].astype(np.int64) + res["t_end"][wi] + 2
+    by_len = wi[np.argsort(-length, kind="stable")]
+    check = np.concatenate([by_len[:256], np.random.default_rng(72).choice(by_len[256:], 256, replace=False)])
+    n_ok = 0
+    for p in check.tolist():
+        qd, r, o = queries[p // 50], res[p], blk[p]
+        w = oracle.block_backtrace(qd["q"], qd["comp_bias"], ts[p], mat, 11, 1, int(r["score"]), int(r["q_end"]), int(r["t_end"]))
+        if w["ok"]:
+            assert int(o["status"]) == 0, p
+            assert (int(o["q_start"]), int(o["t_start"]), int(o["ident"]), int(o["bt_len"]), strs[p]) == \
+                (w["q_start"], w["t_start"], w["ident"], len(w["bt"]), w["bt"]), p
+            n_ok += 1
+        else:
+            assert int(o["status"]) == 1, p
+    assert n_ok >= 400, n_ok
