@@ -498,7 +498,7 @@ struct mmgpu_sw_batch_t {
     uint32_t n_jobs = 0, n_multi_jobs = 0;
     uint32_t n_rev_jobs = 0;      // reverse-scan jobs of the multi-tile queries (mode START), behind the forward jobs in d_jobs
     uint32_t group_begin[SW_GROUPS + 1] = {};
-    size_t group_lds[SW_GROUPS] = {};   // largest profile of any shape present in the group
+    size_t group_lds[SW_GROUPS] = {};   // most profile bytes any job of the group holds: one tile, or all tiles of a resident multi-tile job
     DevBuf d_jobs;
     DevBuf d_scratch;             // multi-tile jobs: [scratch slot][4 waves][4 groups][2 buffers][scratch_cols] x uint2
     DevBuf d_scratch_busy;        // one flag per slot of the pool (sw_kernel claims / releases)
@@ -780,7 +780,9 @@ int SwPrepare::copy_queries() {
         any_multi |= multi;
         const uint32_t shape = (multi ? 32u : 0u) + (uint32_t)rpl - 1;   // [0,32): single tile R = 1..32, [32,64): multi-tile
         const int grp = sw_shape_group(shape);
-        b->group_lds[grp] = std::max(b->group_lds[grp], sw_lds_bytes(rpl, par->alphabet));
+        // a multi-tile job that fits keeps the profiles of all its tiles (sw_multi_resident: the kernel asks the same question)
+        const uint32_t held = multi && sw_multi_resident(sw_tiles(Q.qlen, rpl), rpl, par->alphabet, SW_RESIDENT_LDS) ? sw_tiles(Q.qlen, rpl) : 1u;
+        b->group_lds[grp] = std::max(b->group_lds[grp], (size_t)held * sw_profile_bytes(rpl, par->alphabet));
         // jobs are cut at multiples of one workgroup round (4 waves x 8 targets); for queries of several tiles a
         // single wave's 8 targets already run for milliseconds, so those are cut per wave to shorten the tail
         const uint32_t round = (multi && Q.qlen >= LONG_QUERY) ? JOB_ROUND / 4 : JOB_ROUND;
@@ -1276,6 +1278,7 @@ static int sw_launch_groups(mmgpu_ctx *c, mmgpu_sw_batch_t *b, bool rev_only, co
             L.scratch_cols = b->scratch_cols;
             L.scratch_busy = b->d_scratch_busy.as<uint32_t>();
             L.scratch_slots = std::max<uint32_t>(b->scratch_slots, 1);
+            L.resident_lds = SW_RESIDENT_LDS;
             L.rev_mode = rev_only ? 2 : (b->mode == MMGPU_SW_START_NOT_WORD ? 1 : 0);
             L.rev_only = rev_only ? 1 : 0;
             L.rev_force = rev_force;

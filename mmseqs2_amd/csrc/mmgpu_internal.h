@@ -79,6 +79,9 @@ struct SwLaunch {
     uint32_t scratch_cols;
     uint32_t *scratch_busy;
     uint32_t scratch_slots;
+    // multi-tile jobs whose tiles all fit this many bytes of LDS (sw_multi_resident) build every tile's profile once; the launch's
+    // LDS was sized by the same rule (mmgpu_sw_batch_t::group_lds).  0: none does.
+    uint32_t resident_lds = 0;
     // fused hand-over from a prefilter batch: hits of query q live in slots [q * hit_stride, + q_hit_count[q])
     const uint32_t *q_hit_count;   // null for caller-supplied lists
     uint32_t hit_stride;
@@ -135,7 +138,38 @@ constexpr int SW_GROUPS = MMGPU_SW_GROUPS;
 static_assert(SW_GROUPS == 3 || SW_GROUPS == 4, "three or four kernel groups");
 int sw_shape_group(uint32_t shape);
 hipError_t launch_sw(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream);
-size_t sw_lds_bytes(int rows_per_lane, int alphabet);
+
+// LDS of an alignment workgroup: a header (the reverse pass's packed live hits and the chunk counter) followed by query profiles,
+// one per tile held.  Host (the launch's LDS size) and kernel (which jobs keep all their tiles) use the functions below: both sides
+// of one rule, because a kernel that holds more tiles than the host granted writes past its LDS.
+constexpr int SW_LDS_HEADER = SW_REV_JOB_MAX * 2 + 64;
+__host__ __device__ constexpr int lane_stride_bytes(int R) {
+    // R*2 bytes of scores per lane, rounded up to an odd number of 16-byte slots (bank spread)
+    int slots = (R * 2 + 15) / 16;
+    if ((slots & 1) == 0) slots += 1;
+    return slots * 16;
+}
+// one tile's profile: (alphabet + 1) letters x 16 lanes x the lane stride
+__host__ __device__ constexpr uint32_t sw_profile_bytes(int R, int alphabet) {
+    return (uint32_t)(alphabet + 1) * 16u * (uint32_t)lane_stride_bytes(R);
+}
+// Build knob for A/B measurements: the LDS a multi-tile job may fill with the profiles of all its tiles (header included).  64 KB is
+// what a workgroup may ask for without the launch attribute that raises the ceiling; 0 = no job is resident (every tile's profile is
+// rebuilt in every round of hits, the path of the jobs that do not fit).
+#ifndef MMGPU_SW_RESIDENT_LDS
+#define MMGPU_SW_RESIDENT_LDS 65536
+#endif
+constexpr uint32_t SW_RESIDENT_LDS = MMGPU_SW_RESIDENT_LDS;
+static_assert(SW_RESIDENT_LDS <= 65536u, "a workgroup asks for at most 64 KB of dynamic LDS");
+// tiles of a query of qlen rows at R rows per lane
+__host__ __device__ constexpr uint32_t sw_tiles(uint32_t qlen, int R) { return (qlen + 16u * (uint32_t)R - 1u) / (16u * (uint32_t)R); }
+// a multi-tile job is resident when the profiles of all its tiles and the header fit the budget
+__host__ __device__ constexpr bool sw_multi_resident(uint32_t n_tiles, int R, int alphabet, uint32_t budget) {
+    return (unsigned long long)n_tiles * sw_profile_bytes(R, alphabet) + (unsigned long long)SW_LDS_HEADER <= (unsigned long long)budget;
+}
+// 21 letters, 64 KB: two tiles of any R (56 320 bytes + header at R = 28), three of R <= 24; not three of R >= 25, not four
+static_assert(sw_multi_resident(2, 28, 21, 65536) && sw_multi_resident(3, 24, 21, 65536) && !sw_multi_resident(3, 25, 21, 65536) &&
+              !sw_multi_resident(4, 22, 21, 65536) && !sw_multi_resident(2, 8, 21, 0), "residency rule");
 
 // ---------------------------------------------------------------------------------------------------------
 // prefilter (pf_kernels.hip)

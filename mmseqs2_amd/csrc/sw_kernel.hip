@@ -31,6 +31,9 @@
 //    branch); a 16-lane DPP/shuffle reduction at the end applies the reference's tie rules.
 //  * queries longer than one tile loop over tiles inside the kernel; the H/F row leaving the last lane
 //    is parked in a double-buffered global scratch line and re-enters at the head lane of the next tile.
+//    Where the profiles of all tiles fit the workgroup's LDS (two tiles always, three up to R = 24 with 21 letters:
+//    sw_multi_resident, mmgpu_internal.h) they are built once per job and the tile loop only moves the LDS base;
+//    otherwise the one profile is rebuilt per tile, between two barriers.
 //
 // Bytes per cell that ever touch HBM: (tlen + 28) / (qlen * tlen) ~ 0.003 - this kernel
 // is bound by VALU issue, not by HBM.
@@ -82,19 +85,14 @@ __device__ __forceinline__ unsigned from_lane_above(unsigned head, unsigned v) {
 // Used on the E update (and the multi-tile bodies' column maximum) in phase 2 of the column loop - see there.
 #define SW_KEEP_IN_ROW(x) asm volatile("" : "+v"(x))
 
-__host__ __device__ constexpr int lane_stride_bytes(int R) {
-    // R*2 bytes of scores per lane, rounded up to an odd number of 16-byte slots (bank spread)
-    int slots = (R * 2 + 15) / 16;
-    if ((slots & 1) == 0) slots += 1;
-    return slots * 16;
-}
-
+// (lane_stride_bytes and the size of a tile's profile: mmgpu_internal.h, shared with the host's LDS sizing)
 template <int R>
 struct Tile {
     static constexpr int ROWS = GROUP * R;
     static constexpr int LANE_STRIDE = lane_stride_bytes(R);
     static constexpr int ROW_STRIDE = GROUP * LANE_STRIDE;   // bytes per letter
 };
+static_assert(GROUP == 16, "sw_profile_bytes and sw_tiles (mmgpu_internal.h) assume 16-lane groups");
 
 // Build P[letter][row] for rows [tile_base, tile_base + ROWS) of the query (or of the reversed query).
 // Rows past the query end and the extra letter `alphabet` (padding column of a finished target) are
@@ -132,7 +130,7 @@ __device__ __forceinline__ bool sw_rev_wanted(const SwLaunch &L, uint32_t slot, 
 
 constexpr int SW_REV_JOB_HITS = 1024;   // most hits a reverse-scan job may hold (mmgpu_internal.h: SW_REV_JOB_MAX)
 static_assert(SW_REV_JOB_HITS == SW_REV_JOB_MAX, "host and kernel disagree on the reverse job size");
-constexpr int SW_LDS_HEADER = SW_REV_JOB_HITS * 2 + 64;
+static_assert(SW_LDS_HEADER == SW_REV_JOB_HITS * 2 + 64, "the header holds the live hits and the scheduling words");
 
 // PF: the profile rows of a column are fetched one column ahead (see the column loop)
 template <int R, bool MULTI, bool REV, bool PF>
@@ -162,7 +160,18 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
         const uint32_t po = L.q_prof_off[job.query];
         if (po != 0xFFFFFFFFu) prof = L.q_prof + po;
     }
-    const int n_tiles = MULTI ? (qlen + T::ROWS - 1) / T::ROWS : 1;
+    const int n_tiles = MULTI ? (int)sw_tiles((uint32_t)qlen, R) : 1;
+    // A multi-tile job whose tiles all fit the LDS the host granted by the same rule keeps every tile's profile: built once, in
+    // front of the chunk loop, which then runs without a barrier - its wavefronts take chunks as they finish, like the single-tile
+    // bodies.  The other jobs rebuild the one profile they have room for per tile and round.  (workgroup-uniform)
+    const uint32_t tile_bytes = sw_profile_bytes(R, L.alphabet);
+    const bool resident = MULTI && sw_multi_resident((uint32_t)n_tiles, R, L.alphabet, L.resident_lds);
+    const bool dynamic = !MULTI || resident;   // chunks handed out through next_chunk, no barrier in the loop
+    auto build_all_tiles = [&]() {
+        for (int tile = 0; tile < n_tiles; ++tile)
+            build_profile<R, REV>(lds + (uint32_t)tile * tile_bytes, q, cb, qlen, tile * T::ROWS, L.mat, L.alphabet, prof);
+        __syncthreads();
+    };
 
     const unsigned go2 = (unsigned)L.gap_open * 0x10001u;
     const unsigned ge2 = (unsigned)L.gap_extend * 0x10001u;
@@ -173,6 +182,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
         build_profile<R, REV>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
         __syncthreads();
     }
+    if (MULTI && !REV && resident) build_all_tiles();
 
     uint32_t n_hits = job.hit_end - job.hit_begin;
     // Reverse pass: only the pairs whose forward score reaches the query's start-score threshold are scanned
@@ -206,20 +216,21 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             build_profile<R, REV>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
             __syncthreads();
         }
+        if (MULTI && resident) build_all_tiles();
     }
     const uint32_t n_iter = (n_hits + WAVES * HITS_PER_WAVE - 1) / (WAVES * HITS_PER_WAVE);
 
-    for (uint32_t it = 0; !MULTI || it < n_iter; ++it) {
-        // Single-tile jobs: a wave takes the next chunk of 8 hits when it is done with its last one (the hits are
-        // sorted by length, so fixed wave <-> chunk striping would give wave 0 the longest chunk of every round).
-        // Multi-tile jobs rebuild the profile per tile with all threads, so their waves stay in step.
+    for (uint32_t it = 0; dynamic || it < n_iter; ++it) {
+        // Single-tile and resident jobs: a wave takes the next chunk of 8 hits when it is done with its last one (the hits
+        // are sorted by length, so fixed wave <-> chunk striping would give wave 0 the longest chunk of every round).
+        // The other multi-tile jobs rebuild the profile per tile with all threads, so their waves stay in step.
         uint32_t chunk = it * WAVES + wave;
-        if (!MULTI) {
+        if (dynamic) {
             if (lane == 0) chunk = atomicAdd(next_chunk, 1u);
             chunk = __builtin_amdgcn_readfirstlane(chunk);
         }
         const uint32_t slot0 = chunk * HITS_PER_WAVE;
-        if (!MULTI && slot0 >= n_hits) break;   // wave-uniform; MULTI keeps every wave in the barrier loop
+        if (dynamic && slot0 >= n_hits) break;   // wave-uniform; the jobs in step keep every wave in the barrier loop
 
         // ---- the two targets of this group ------------------------------------------------------
         const uint32_t sA = slot0 + grp * 2, sB = sA + 1;
@@ -265,11 +276,17 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
 
         for (int tile = 0; tile < n_tiles; ++tile) {
             const int tile_base = tile * T::ROWS;
-            if (MULTI) {
+            if (MULTI && !resident) {
                 __syncthreads();   // everyone is done reading the previous tile's profile
                 build_profile<R, REV>(lds, q, cb, qlen, tile_base, L.mat, L.alphabet, prof);
                 __syncthreads();
             }
+            // the profile of this tile: the one there is, or this tile's of the resident ones (no barrier: nobody writes them).
+            // Without the barriers nothing but program order stands between tile t's stores to its scratch line (lane 15 of a
+            // group) and tile t + 1's loads from it (the group's head lane): the hand-over of the boundary row relies on both
+            // being lanes of ONE wavefront, whose vector memory operations on the same addresses complete in order.  A group
+            // spread over two wavefronts would need a fence and a barrier here again.
+            const unsigned char *const lds_tile = MULTI && resident ? lds + (uint32_t)tile * tile_bytes : lds;
             const uint2 *scr_in = MULTI ? scr + (size_t)((tile + 1) & 1) * L.scratch_cols : nullptr;
             uint2 *scr_out = MULTI ? scr + (size_t)(tile & 1) * L.scratch_cols : nullptr;
             const bool has_above = MULTI && tile > 0;
@@ -332,8 +349,8 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             unsigned pav_next[PF ? ND : 1], pbv_next[PF ? ND : 1];   // PF: the rows fetched for the next step
             auto load_rows = [&](unsigned letters, unsigned *pav, unsigned *pbv) {
                 const unsigned a = letters & 0xFFu, b = (letters >> 8) & 0xFFu;
-                const uint4 *rowA = reinterpret_cast<const uint4 *>(lds + a * T::ROW_STRIDE + g * T::LANE_STRIDE);
-                const uint4 *rowB = reinterpret_cast<const uint4 *>(lds + b * T::ROW_STRIDE + g * T::LANE_STRIDE);
+                const uint4 *rowA = reinterpret_cast<const uint4 *>(lds_tile + a * T::ROW_STRIDE + g * T::LANE_STRIDE);
+                const uint4 *rowB = reinterpret_cast<const uint4 *>(lds_tile + b * T::ROW_STRIDE + g * T::LANE_STRIDE);
 #pragma unroll
                 for (int k = 0; k < ND / 4; ++k) {
                     const uint4 pa = rowA[k], pb = rowB[k];
@@ -830,10 +847,6 @@ uint32_t sw_multi_resident_blocks(size_t lds_bytes, bool both_passes, int comput
     if (e != hipSuccess || per_cu < 1) per_cu = 8;
     per_cu = per_cu + 1 > 8 ? 8 : per_cu + 1;
     return (uint32_t)per_cu * (uint32_t)(compute_units > 0 ? compute_units : 256);
-}
-
-size_t sw_lds_bytes(int rows_per_lane, int alphabet) {
-    return (size_t)(alphabet + 1) * GROUP * lane_stride_bytes(rows_per_lane);
 }
 
 hipError_t launch_sw_rev_multi(const SwLaunch &L, size_t lds_bytes, hipStream_t stream) {
