@@ -29,85 +29,11 @@
 #include <type_traits>
 
 #include "mmgpu_internal.h"
+#include "pf_device.h"
 
 namespace mmgpu {
 
 namespace {
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
-// __ballot() takes an int: a bool argument is materialised (v_cndmask 0 / 1) and compared with zero again - two VALU
-// instructions per ballot in kernels that are bound by instruction issue.  The builtin takes the condition as it is.
-__device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
-// Inclusive scans over the wavefront with DPP moves (row shifts inside the 16-lane rows, then the row ends handed to the
-// following rows): six VALU operations instead of six ds_bpermute round trips.
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111 /* row_shr:1 */, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112 /* row_shr:2 */, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114 /* row_shr:4 */, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118 /* row_shr:8 */, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142 /* row_bcast:15 */, 0xA, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143 /* row_bcast:31 */, 0xC, 0xF, false);
-    return (uint32_t)x;
-}
-__device__ __forceinline__ int wave_incl_max_scan(int v) {      // v >= 0
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));
-    return v;
-}
-
-// Largest lane m with start[m] <= x, for per-lane non-decreasing `start` with start[0] <= x.  Every lane of
-// the wave must call this (it shuffles).
-__device__ __forceinline__ int seg_find(uint32_t start_mine, uint32_t x) {
-    int lo = 0;
-#pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) {
-        const uint32_t s = __shfl(start_mine, lo + step);
-        if (s <= x) lo += step;
-    }
-    return lo;
-}
-
-// Lanes of the wave whose `key` (low nbits) equals mine, among lanes with active == true.
-__device__ __forceinline__ uint64_t match_lanes(uint32_t key, int nbits, bool active) {
-    const uint64_t act = ballot(active);
-    uint32_t lo = (uint32_t)act, hi = (uint32_t)(act >> 32);
-    for (int b = 0; b < nbits; b++) {
-        // per bit: m &= (my bit set ? lanes with the bit : lanes without) = m & ~(ballot ^ my bit spread over the word):
-        // one v_bfe_i32, one compare, one v_bitop3 per half
-        const int ext = __builtin_amdgcn_sbfe((int)key, (unsigned)b, 1u);      // 0 or -1
-        const uint64_t bal = ballot(ext != 0);
-        lo = __builtin_amdgcn_bitop3_b32(lo, (uint32_t)bal, (uint32_t)ext, 0x90);
-        hi = __builtin_amdgcn_bitop3_b32(hi, (uint32_t)(bal >> 32), (uint32_t)ext, 0x90);
-    }
-    return (uint64_t)lo | ((uint64_t)hi << 32);
-}
-
-__device__ __forceinline__ int highest_lane(uint64_t m) { return 63 - __clzll((long long)m); }
-
-// Largest index in [lo, hi] whose value (base[idx * stride], non-decreasing, base[lo * stride] <= key) is <= key.
-// The whole wavefront probes 64 evenly spaced elements per round: log64 instead of log2 dependent memory round trips.
-__device__ __forceinline__ uint32_t wave_search_le(const uint32_t *base, uint32_t stride, uint32_t lo, uint32_t hi, uint32_t key) {
-    const uint32_t lane = (uint32_t)lane_id();
-    while (hi > lo) {
-        const uint32_t span = hi - lo + 1;
-        const uint32_t step = (span + 63u) / 64u;
-        const uint32_t idx = lo + lane * step;
-        const bool in = idx <= hi;
-        const uint32_t v = in ? base[(size_t)idx * stride] : 0xFFFFFFFFu;
-        const uint64_t le = ballot(in && v <= key);   // a prefix of the lanes
-        const uint32_t k = (uint32_t)__popcll(le) - 1u;
-        lo += k * step;
-        hi = min(hi, lo + step - 1u);
-    }
-    return lo;
-}
 
 // Candidate k of a (query, bin) bucket: the first PF_CAND0 live in a dense [bucket][PF_CAND0] array (a bucket holds ~12
 // candidates at configs[2]; the dense array keeps the replay/score/keepmax kernels inside a few hundred MB instead of
@@ -122,14 +48,6 @@ struct __attribute__((packed, aligned(4))) U32Pair {   // two adjacent uint32 at
 struct __attribute__((packed, aligned(4))) U32Quad {
     uint32_t a, b, c, d;
 };
-
-// XCD-aware order of a grid's workgroups.  The dispatcher places workgroup b on XCD b % 8 (observed, not a contract: a wrong guess
-// only costs speed); each XCD has its own 4 MB L2.  swz gives XCD x the x-th CONTIGUOUS eighth of the work items, in order, so
-// that items that are neighbours in the work order meet in one L2 (bijective for any grid size).
-__device__ __forceinline__ uint32_t xcd_contiguous(uint32_t bid, uint32_t nwg) {
-    const uint32_t xcd = bid & 7u, q = nwg >> 3, r = nwg & 7u;
-    return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (bid >> 3);
-}
 
 // (the work order of the similar-k-mer kernels - PfKmerArgs::order - is built in pf_order.hip)
 
@@ -207,6 +125,42 @@ __device__ __forceinline__ void pf_lookup(const PfKmerArgs &A, uint32_t kmer, ui
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// What the similar-k-mer kernels share.  (The position / order / q_kind preamble of the two sequence kernels stays in each of them: as a
+// function it changed the code of these kernels in every form tried - profiles/pf_device_dedupe_isa.txt.)
+// A position's record: pos_entries (EMIT) or nsim, written by lane 0.
+template <bool EMIT>
+__device__ __forceinline__ void pf_kmers_record(const PfKmerArgs &A, uint32_t gp, uint32_t running, uint32_t nlists) {
+    if (lane_id() == 0) {
+        if (EMIT) A.pos_entries[gp] = running; else A.nsim[gp] = nlists;
+    }
+}
+// Last stage of the sequence kernels: the index lists of the children of this round's parents, 64 at a time.  Lane l holds parent l:
+// its k-mer index so far (parent_idx) and the exclusive prefix of its number of children (excl; total = all of them); child c of a
+// parent is child_idx[c] * mult above it.  The records go to lists[lbase + nlists ..), `running` is the position's entry count so far.
+// NONEMPTY: consult the bit table of the sparse index before a sector of the offset table is touched (pf_kmers_kernel does,
+// pf_kmers7_kernel does not).
+template <bool NONEMPTY>
+__device__ __forceinline__ void emit_lists(const PfKmerArgs &A, uint32_t excl, uint32_t total, uint32_t parent_idx, const uint32_t *child_idx,
+                                           uint32_t mult, uint32_t lbase, uint32_t nlists, uint32_t gp, uint32_t &running) {
+    const int lane = lane_id();
+    for (uint32_t r0 = 0; r0 < total; r0 += 64) {
+        const uint32_t x = r0 + (uint32_t)lane;
+        const bool act = x < total;
+        const int m = seg_find(excl, x);
+        const uint32_t ex_m = __shfl(excl, m);
+        const uint32_t k_p = __shfl(parent_idx, m);
+        uint32_t start = 0, len = 0;
+        if (act) {
+            const uint32_t kmer = k_p + child_idx[x - ex_m] * mult;
+            if (!NONEMPTY || !A.nonempty || ((A.nonempty[kmer >> 5] >> (kmer & 31u)) & 1u)) pf_lookup(A, kmer, start, len);
+        }
+        const uint32_t li = wave_incl_scan(len);
+        if (act) pf_store_list(&A.lists[(size_t)lbase + nlists + x], start, len, running + li - len, gp);
+        running += __shfl(li, 63);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // a5 + first half of a6: one wavefront per query position.
 //   EMIT = false: nsim[gp] = number of similar k-mers of the window starting at gp
 //   EMIT = true : lists[list_base[gp] + r] = index list of the r-th similar k-mer, pos_entries[gp] = sum of lengths
@@ -227,9 +181,7 @@ __global__ __launch_bounds__(256) void pf_kmers_kernel(PfKmerArgs A) {
     if (A.q_kind && A.q_kind[gp]) return;   // position of a profile query: pf_kmers_prof_kernel
     const int thr = A.q_thr[gp];
     if (thr < 0) {   // no window here, or the window contains X (QueryMatcher.cpp:264-268)
-        if (lane == 0) {
-            if (EMIT) A.pos_entries[gp] = 0; else A.nsim[gp] = 0;
-        }
+        pf_kmers_record<EMIT>(A, gp, 0u, 0u);
         return;
     }
     const uint8_t *q = A.q_res + gp;
@@ -266,28 +218,11 @@ __global__ __launch_bounds__(256) void pf_kmers_kernel(PfKmerArgs A) {
         if (EMIT) {
             const uint32_t excl = incl - ni;
             const uint32_t my_idx = inA ? iA[ia] : 0u;
-            for (uint32_t r0 = 0; r0 < total; r0 += 64) {
-                const uint32_t x = r0 + (uint32_t)lane;
-                const bool act = x < total;
-                const int m = seg_find(excl, x);
-                const uint32_t ex_m = __shfl(excl, m);
-                const uint32_t k_a = __shfl(my_idx, m);
-                uint32_t start = 0, len = 0;
-                if (act) {
-                    const uint32_t kmer = k_a + iB[x - ex_m] * nrowA;
-                    // (sparse index: the bit table says whether the list is empty before a sector of the offset table is touched)
-                    if (!A.nonempty || ((A.nonempty[kmer >> 5] >> (kmer & 31u)) & 1u)) pf_lookup(A, kmer, start, len);
-                }
-                const uint32_t li = wave_incl_scan(len);
-                if (act) pf_store_list(&A.lists[(size_t)lbase + nlists + x], start, len, running + li - len, gp);
-                running += __shfl(li, 63);
-            }
+            emit_lists<true>(A, excl, total, my_idx, iB, nrowA, lbase, nlists, gp, running);
         }
         nlists += total;
     }
-    if (lane == 0) {
-        if (EMIT) A.pos_entries[gp] = running; else A.nsim[gp] = nlists;
-    }
+    pf_kmers_record<EMIT>(A, gp, running, nlists);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -306,12 +241,10 @@ __global__ __launch_bounds__(256) void pf_kmers7_kernel(PfKmerArgs A) {
         gp = A.order[gp];
     }
     if (gp >= A.n_pos) return;
-    if (A.q_kind && A.q_kind[gp]) return;
+    if (A.q_kind && A.q_kind[gp]) return;   // position of a profile query: pf_kmers_prof_kernel
     const int thr = A.q_thr[gp];
-    if (thr < 0) {
-        if (lane == 0) {
-            if (EMIT) A.pos_entries[gp] = 0; else A.nsim[gp] = 0;
-        }
+    if (thr < 0) {   // no window here, or the window contains X (QueryMatcher.cpp:264-268)
+        pf_kmers_record<EMIT>(A, gp, 0u, 0u);
         return;
     }
     const uint8_t *q = A.q_res + gp;
@@ -369,28 +302,12 @@ __global__ __launch_bounds__(256) void pf_kmers7_kernel(PfKmerArgs A) {
             const uint32_t total2 = __shfl(incl2, 63);
             if (EMIT) {
                 const uint32_t excl2 = incl2 - n2e;
-                for (uint32_t r0 = 0; r0 < total2; r0 += 64) {
-                    const uint32_t y = r0 + (uint32_t)lane;
-                    const bool act = y < total2;
-                    const int me = seg_find(excl2, y);
-                    const uint32_t ex_e = __shfl(excl2, me);
-                    const uint32_t k_e = __shfl(idx_e, me);
-                    uint32_t start = 0, len = 0;
-                    if (act) {
-                        const uint32_t kmer = k_e + iC[y - ex_e] * mult3;
-                        pf_lookup(A, kmer, start, len);
-                    }
-                    const uint32_t li = wave_incl_scan(len);
-                    if (act) pf_store_list(&A.lists[(size_t)lbase + nlists + y], start, len, running + li - len, gp);
-                    running += __shfl(li, 63);
-                }
+                emit_lists<false>(A, excl2, total2, idx_e, iC, mult3, lbase, nlists, gp, running);
             }
             nlists += total2;
         }
     }
-    if (lane == 0) {
-        if (EMIT) A.pos_entries[gp] = running; else A.nsim[gp] = nlists;
-    }
+    pf_kmers_record<EMIT>(A, gp, running, nlists);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -507,9 +424,7 @@ __global__ __launch_bounds__(256) void pf_kmers_prof_kernel(PfKmerArgs A) {
     if (!A.q_kind[gp]) return;             // position of a sequence query
     const int thr = A.q_thr[gp];
     if (thr < 0) {
-        if (lane == 0) {
-            if (EMIT) A.pos_entries[gp] = 0; else A.nsim[gp] = 0;
-        }
+        pf_kmers_record<EMIT>(A, gp, 0u, 0u);
         return;
     }
     ProfGen G;
@@ -535,9 +450,7 @@ __global__ __launch_bounds__(256) void pf_kmers_prof_kernel(PfKmerArgs A) {
     const int sc0 = act ? (int)G.sc[0][lane] : 0;
     const uint32_t idx0 = act ? (uint32_t)G.le[0][lane] : 0u;
     prof_expand<1, K, EMIT>(A, G, act, sc0, idx0);
-    if (lane == 0) {
-        if (EMIT) A.pos_entries[gp] = G.running; else A.nsim[gp] = G.nlists;
-    }
+    pf_kmers_record<EMIT>(A, gp, G.running, G.nlists);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -667,8 +580,7 @@ __global__ __launch_bounds__(SPW * 64) __attribute__((amdgpu_waves_per_eu(SPLIT_
     __syncthreads();
 
     // ---- phase B: per-(wave, bin) counts and each entry's rank inside its (wave, bin) ----
-    int nbits = 0;
-    while ((1u << nbits) < B) nbits++;
+    const int nbits = pf_bin_shift(B);
     constexpr int ROUNDS = PF_T / (64 * SPW);   // entries per thread
     uint64_t ent[ROUNDS];
     uint32_t rk[ROUNDS];
@@ -984,6 +896,7 @@ __device__ __forceinline__ uint64_t score_chunk(const PfDedupArgs &A, const int8
             }
         }
         win = win && cnt >= A.min_diag_score;
+        // (wave_append's steps, spelled out: with the call the replay and scoring kernels compile to other code - profiles/pf_device_dedupe_isa.txt)
         const uint64_t wb = ballot(win);
         if (wb) {
             PfCand *surv = A.surv + (A.cand_base[(uint64_t)q * A.bins] - A.cand_origin);
@@ -1055,8 +968,7 @@ __device__ __forceinline__ void replay_bucket_impl(const PfDedupArgs &A, ReplayL
     uint32_t *L = M.last[wave];
     uint32_t *E = M.emit[wave];
     uint8_t *mark = M.mark[wave];
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
+    const int bshift = pf_bin_shift(B);
     auto clear_state = [&]() {      // (the emitted bytes are only read under a set bit: the bits are what is cleared)
         uint4 *P4 = reinterpret_cast<uint4 *>(P);
         for (int k = lane; k < PF_IDS_PER_BIN / 16; k += 64) P4[k] = make_uint4(0u, 0u, 0u, 0u);
@@ -1193,8 +1105,7 @@ __device__ __forceinline__ void replay_bucket_impl(const PfDedupArgs &A, ReplayL
     // a8 + keepMaxElement for the common case of at most 64 candidates, straight from LDS (no second kernel's
     // count -> record -> metadata round trips); larger buckets are left to pf_ungapped_kernel / pf_keepmax_kernel
     if (!SEGS && ncand > 0 && ncand <= 64) {
-        PfCand c;
-        c.id = 0; c.arr = 0; c.score = 0; c.diag = 0; c.pad = 0;
+        PfCand c = pf_cand_zero();
         if ((uint32_t)lane < ncand) {
             const uint32_t kd = M.cand[wave][0][lane];
             c.id = ((kd & 0xFFFu) << bshift) | bin;
@@ -1203,23 +1114,18 @@ __device__ __forceinline__ void replay_bucket_impl(const PfDedupArgs &A, ReplayL
             c.score = M.cand[wave][2][lane];
         }
         uint64_t cells = score_chunk(A, M.smat, bucket, q, 0, ncand, ncand, c, bshift);
-        if (A.cell_counter) {
-            for (int dd = 1; dd < 64; dd <<= 1) cells += __shfl_xor((unsigned long long)cells, dd);
-            if (lane == 0 && cells) atomicAdd((unsigned long long *)&A.cell_counter[q], (unsigned long long)cells);
-        }
+        if (A.cell_counter) wave_sum_to((unsigned long long *)&A.cell_counter[q], cells);
     }
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REPLAY_WAVES_PER_EU))) void pf_replay_kernel(PfDedupArgs A) {
     __shared__ ReplayLds M;
-    const int wave = (int)(threadIdx.x >> 6);
-    for (int k = (int)threadIdx.x; k < 32 * 32; k += 256)      // rows of 32 (seg_cells_n)
-        M.smat[k] = ((k >> 5) < A.alphabet && (k & 31) < A.alphabet) ? A.mat[(k >> 5) * A.alphabet + (k & 31)] : (int8_t)0;
+    pf_load_smat32<256>(M.smat, A.mat, A.alphabet);
     __syncthreads();
     // (the buckets of one query read the same tiles; a contiguous run of queries per XCD measured slower than the round-robin
     // deal - an eighth of the batch's queries is an uneven share of the work: profiles/r05_exp_pf_order.txt)
-    const uint64_t bucket = (uint64_t)A.q_first * A.bins + (uint64_t)blockIdx.x * 4u + (uint32_t)wave;
-    if (bucket >= (uint64_t)(A.q_first + A.n_queries) * A.bins) return;
+    uint64_t bucket;
+    if (!pf_wave_bucket(A, 4u, &bucket)) return;
     if (A.q_nseg && A.q_nseg[(uint32_t)(bucket / A.bins)]) replay_bucket_impl<true>(A, M, bucket);      // wave-uniform
     else replay_bucket_impl<false>(A, M, bucket);
 }
@@ -1231,20 +1137,16 @@ __device__ __forceinline__ void ungapped_bucket(const PfDedupArgs &A, const int8
     const uint32_t ncand = A.cand_count[bucket];
     const uint32_t q = (uint32_t)(bucket / B);
     if (ncand <= 64 || (A.q_nseg && A.q_nseg[q])) return;   // small bins are done; overflow queries have their own path
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
+    const int bshift = pf_bin_shift(B);
     uint64_t cells = 0;
     for (uint32_t cb0 = 0; cb0 < ncand; cb0 += 64) {
         const uint32_t nin = min(64u, ncand - cb0);
-        PfCand c;
-        c.id = 0; c.arr = 0; c.score = 0; c.diag = 0; c.pad = 0;
+        PfCand c = pf_cand_zero();
         if ((uint32_t)lane < nin) c = *cand_slot(A, bucket, cb0 + (uint32_t)lane);
         cells += score_chunk(A, smat, bucket, q, cb0, nin, ncand, c, bshift);
     }
-    if (A.cell_counter) {   // statistics: one counter per query (a single global counter serialises 2.6 M atomics)
-        for (int dd = 1; dd < 64; dd <<= 1) cells += __shfl_xor((unsigned long long)cells, dd);
-        if (lane == 0 && cells) atomicAdd((unsigned long long *)&A.cell_counter[q], (unsigned long long)cells);
-    }
+    // statistics: one counter per query (a single global counter serialises 2.6 M atomics)
+    if (A.cell_counter) wave_sum_to((unsigned long long *)&A.cell_counter[q], cells);
 }
 
 // Round 6: with a work list (A.big_list, written by the replay kernel) the grid is a fixed number of workgroups whose wavefronts
@@ -1252,8 +1154,7 @@ __device__ __forceinline__ void ungapped_bucket(const PfDedupArgs &A, const int8
 __global__ __launch_bounds__(256) void pf_ungapped_kernel(PfDedupArgs A) {
     __shared__ int8_t smat[32 * 32];
     const int wave = (int)(threadIdx.x >> 6);
-    for (int k = (int)threadIdx.x; k < 32 * 32; k += 256)      // rows of 32 (seg_cells_n)
-        smat[k] = ((k >> 5) < A.alphabet && (k & 31) < A.alphabet) ? A.mat[(k >> 5) * A.alphabet + (k & 31)] : (int8_t)0;
+    pf_load_smat32<256>(smat, A.mat, A.alphabet);
     __syncthreads();
     const uint32_t B = A.bins;
     if (A.big_list) {
@@ -1261,6 +1162,7 @@ __global__ __launch_bounds__(256) void pf_ungapped_kernel(PfDedupArgs A) {
         for (uint32_t i = blockIdx.x * 4u + (uint32_t)wave; i < n; i += gridDim.x * 4u) ungapped_bucket(A, smat, (uint64_t)A.q_first * B + A.big_list[i]);
         return;
     }
+    // (pf_wave_bucket, spelled out: with the call this kernel takes one more VGPR - profiles/pf_device_dedupe_isa.txt)
     const uint64_t bucket = (uint64_t)A.q_first * B + (uint64_t)blockIdx.x * 4u + (uint32_t)wave;
     if (bucket >= (uint64_t)(A.q_first + A.n_queries) * B) return;
     ungapped_bucket(A, smat, bucket);
@@ -1279,8 +1181,8 @@ __global__ __launch_bounds__(256) void pf_count_kernel(PfDedupArgs A) {
     __shared__ uint32_t s_emit[4][PF_IDS_PER_BIN / 32];
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const uint32_t B = A.bins;
-    const uint64_t bucket = (uint64_t)A.q_first * B + (uint64_t)blockIdx.x * 4u + (uint32_t)wave;
-    if (bucket >= (uint64_t)(A.q_first + A.n_queries) * B) return;
+    uint64_t bucket;
+    if (!pf_wave_bucket(A, 4u, &bucket)) return;
     const uint32_t q = (uint32_t)(bucket / B), bin = (uint32_t)(bucket % B);
     const uint32_t ntiles = A.q_ntiles[q];
     if (lane == 0) A.cand_count[bucket] = 0;      // nothing for the scoring kernels of the other mode
@@ -1288,8 +1190,7 @@ __global__ __launch_bounds__(256) void pf_count_kernel(PfDedupArgs A) {
     const uint32_t tb = A.q_tile_base[q];
     uint16_t *S = s_state[wave];
     uint32_t *E = s_emit[wave];
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
+    const int bshift = pf_bin_shift(B);
     for (int k = lane; k < PF_IDS_PER_BIN; k += 64) S[k] = 0;
     for (int k = lane; k < PF_IDS_PER_BIN / 32; k += 64) E[k] = 0;
     uint32_t ncand = 0;
@@ -1364,8 +1265,7 @@ __global__ __launch_bounds__(256) void pf_count_kernel(PfDedupArgs A) {
     unsigned long long total_count = 0;
     for (uint32_t c0 = 0; c0 < ncand; c0 += 64) {
         const uint32_t ci = c0 + (uint32_t)lane;
-        PfCand c;
-        c.id = 0; c.arr = 0; c.score = 0; c.diag = 0; c.pad = 0;
+        PfCand c = pf_cand_zero();
         bool win = false;
         if (ci < ncand) {
             c = *cand_slot(A, bucket, ci);
@@ -1373,18 +1273,10 @@ __global__ __launch_bounds__(256) void pf_count_kernel(PfDedupArgs A) {
             total_count += c.score;
             win = c.score >= A.min_diag_score;
         }
-        const uint64_t wb = ballot(win);
-        if (wb) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&A.surv_count[q], (uint32_t)__popcll(wb));
-            base = __shfl(base, 0);
-            if (win) surv[base + (uint32_t)__popcll(wb & below)] = c;
-        }
+        wave_append(&A.surv_count[q], surv, win, c);
     }
-    if (A.cell_counter) {   // statistics_t::doubleMatches = sum of the counts (QueryMatcher.cpp:366-385)
-        for (int dd = 1; dd < 64; dd <<= 1) total_count += __shfl_xor(total_count, dd);
-        if (lane == 0 && total_count) atomicAdd((unsigned long long *)&A.cell_counter[q], total_count);
-    }
+    // statistics_t::doubleMatches = sum of the counts (QueryMatcher.cpp:366-385)
+    if (A.cell_counter) wave_sum_to((unsigned long long *)&A.cell_counter[q], total_count);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1397,47 +1289,35 @@ __device__ __forceinline__ void keepmax_bucket(const PfDedupArgs &A, uint32_t *S
     const uint32_t ncand = A.cand_count[bucket];
     const uint32_t q = (uint32_t)(bucket / B);
     if (ncand <= 64 || (A.q_nseg && A.q_nseg[q])) return;   // scored and reduced already / overflow path
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
+    const int bshift = pf_bin_shift(B);
     for (int k = lane; k < PF_IDS_PER_BIN; k += 64) S[k] = 0;
     for (uint32_t c0 = 0; c0 < ncand; c0 += 64) {
         const uint32_t ci = c0 + (uint32_t)lane;
         if (ci < ncand) {
             const PfCand *cp = cand_slot(A, bucket, ci);
-            const uint32_t cnt = min(255u, cp->score);
-            const uint32_t k2 = (cnt << 24) | (0xFFFFFFu - min(ci, 0xFFFFFEu));
-            atomicMax(&S[cp->id >> bshift], k2);
+            atomicMax(&S[cp->id >> bshift], keepmax_key(min(255u, cp->score), ci));
         }
     }
     PfCand *surv = A.surv + (A.cand_base[(uint64_t)q * B] - A.cand_origin);
     for (uint32_t c0 = 0; c0 < ncand; c0 += 64) {
         const uint32_t ci = c0 + (uint32_t)lane;
         bool win = false;
-        PfCand c;
-        c.id = 0; c.arr = 0; c.score = 0; c.diag = 0; c.pad = 0;
+        PfCand c = pf_cand_zero();
         if (ci < ncand) {
             c = *cand_slot(A, bucket, ci);
             const uint32_t cnt = min(255u, c.score);
-            const uint32_t k2 = (cnt << 24) | (0xFFFFFFu - min(ci, 0xFFFFFEu));
-            win = S[c.id >> bshift] == k2 && cnt >= A.min_diag_score;
+            win = S[c.id >> bshift] == keepmax_key(cnt, ci) && cnt >= A.min_diag_score;
         }
-        const uint64_t wb = ballot(win);
-        if (wb) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&A.surv_count[q], (uint32_t)__popcll(wb));
-            base = __shfl(base, 0);
-            if (win) surv[base + (uint32_t)__popcll(wb & lanes_below(lane))] = c;
-        }
+        wave_append(&A.surv_count[q], surv, win, c);
     }
 }
 
 __global__ __launch_bounds__(256) void pf_keepmax_kernel(PfDedupArgs A) {
     __shared__ uint32_t s_tab[4][PF_IDS_PER_BIN];
     const int wave = (int)(threadIdx.x >> 6);
-    const uint32_t B = A.bins;
     if (A.nucl) return;                                      // pf_keepmax_nucl_kernel
-    const uint64_t bucket = (uint64_t)A.q_first * B + (uint64_t)blockIdx.x * 4u + (uint32_t)wave;
-    if (bucket >= (uint64_t)(A.q_first + A.n_queries) * B) return;
+    uint64_t bucket;
+    if (!pf_wave_bucket(A, 4u, &bucket)) return;
     keepmax_bucket(A, s_tab[wave], bucket);
 }
 
@@ -1447,10 +1327,8 @@ __global__ __launch_bounds__(256) void pf_keepmax_kernel(PfDedupArgs A) {
 // query's survivor count per step (1.4 ms for a chunk's 625 buckets).
 __global__ __launch_bounds__(1024) void pf_keepmax_list_kernel(PfDedupArgs A) {
     __shared__ uint32_t S[PF_IDS_PER_BIN];
-    const int lane = lane_id();
     const uint32_t B = A.bins;
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
+    const int bshift = pf_bin_shift(B);
     const uint32_t n = *A.big_count;
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const uint64_t bucket = (uint64_t)A.q_first * B + A.big_list[i];
@@ -1460,27 +1338,20 @@ __global__ __launch_bounds__(1024) void pf_keepmax_list_kernel(PfDedupArgs A) {
         __syncthreads();
         for (uint32_t ci = threadIdx.x; ci < ncand; ci += 1024) {
             const PfCand *cp = cand_slot(A, bucket, ci);
-            atomicMax(&S[cp->id >> bshift], (min(255u, cp->score) << 24) | (0xFFFFFFu - min(ci, 0xFFFFFEu)));
+            atomicMax(&S[cp->id >> bshift], keepmax_key(min(255u, cp->score), ci));
         }
         __syncthreads();
         PfCand *surv = A.surv + (A.cand_base[(uint64_t)q * B] - A.cand_origin);
         for (uint32_t c0 = 0; c0 < ncand; c0 += 1024) {      // (every wavefront takes part in its ballot)
             const uint32_t ci = c0 + threadIdx.x;
             bool win = false;
-            PfCand c;
-            c.id = 0; c.arr = 0; c.score = 0; c.diag = 0; c.pad = 0;
+            PfCand c = pf_cand_zero();
             if (ci < ncand) {
                 c = *cand_slot(A, bucket, ci);
                 const uint32_t cnt = min(255u, c.score);
-                win = S[c.id >> bshift] == ((cnt << 24) | (0xFFFFFFu - min(ci, 0xFFFFFEu))) && cnt >= A.min_diag_score;
+                win = S[c.id >> bshift] == keepmax_key(cnt, ci) && cnt >= A.min_diag_score;
             }
-            const uint64_t wb = ballot(win);
-            if (wb) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(&A.surv_count[q], (uint32_t)__popcll(wb));
-                base = __shfl(base, 0);
-                if (win) surv[base + (uint32_t)__popcll(wb & lanes_below(lane))] = c;
-            }
+            wave_append(&A.surv_count[q], surv, win, c);
         }
         __syncthreads();
     }
@@ -1570,13 +1441,12 @@ __device__ int wave_long_score(const int8_t *smat, const uint8_t *qr, const uint
 // flagged and go to the host).
 __global__ __launch_bounds__(256) void pf_longq_kernel(PfDedupArgs A) {
     __shared__ int8_t smat[32 * 32];
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    for (int k = (int)threadIdx.x; k < 32 * 32; k += 256)
-        smat[k] = ((k >> 5) < A.alphabet && (k & 31) < A.alphabet) ? A.mat[(k >> 5) * A.alphabet + (k & 31)] : (int8_t)0;
+    const int lane = lane_id();
+    pf_load_smat32<256>(smat, A.mat, A.alphabet);
     __syncthreads();
     const uint32_t B = A.bins;
-    const uint64_t bucket = (uint64_t)A.q_first * B + (uint64_t)blockIdx.x * 4u + (uint32_t)wave;
-    if (bucket >= (uint64_t)(A.q_first + A.n_queries) * B) return;
+    uint64_t bucket;
+    if (!pf_wave_bucket(A, 4u, &bucket)) return;
     const uint32_t q = (uint32_t)(bucket / B);
     const uint32_t qp0 = A.q_off[q];
     const int qlen = (int)(A.q_off[q + 1] - qp0);
@@ -1609,10 +1479,8 @@ __global__ __launch_bounds__(256) void pf_long_kernel(PfDedupArgs A) {
     if (A.nucl || (A.q_nseg && A.q_nseg[q])) return;
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const uint32_t B = A.bins;
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
-    for (int k = (int)threadIdx.x; k < 32 * 32; k += 256)
-        smat[k] = ((k >> 5) < A.alphabet && (k & 31) < A.alphabet) ? A.mat[(k >> 5) * A.alphabet + (k & 31)] : (int8_t)0;
+    const int bshift = pf_bin_shift(B);
+    pf_load_smat32<256>(smat, A.mat, A.alphabet);
     for (int k = (int)threadIdx.x; k < 65536 / 32; k += 256) s_dbits[k] = 0;
     if (threadIdx.x == 0) {
         sh_npool = 0;
@@ -1663,27 +1531,8 @@ __global__ __launch_bounds__(256) void pf_long_kernel(PfDedupArgs A) {
         s_bucket[k] = 0;
     }
     __syncthreads();
-    for (uint32_t size = 2; size <= np2; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t k = threadIdx.x; k < np2 / 2; k += 256) {
-                const uint32_t i = 2 * k - (k & (stride - 1));
-                const uint32_t j = i + stride;
-                const bool up = (i & size) == 0;
-                const uint64_t a = s_key[i], b = s_key[j];
-                if ((a > b) == up) {
-                    s_key[i] = b;
-                    s_key[j] = a;
-                    const uint32_t tc = s_ci[i];
-                    s_ci[i] = s_ci[j];
-                    s_ci[j] = tc;
-                    const uint16_t tb = s_bucket[i];
-                    s_bucket[i] = s_bucket[j];
-                    s_bucket[j] = tb;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    block_bitonic_sort<256>(np2, [&](uint32_t i, uint32_t j) { return s_key[i] > s_key[j]; },
+                            [&](uint32_t i, uint32_t j) { exchange_at(s_key, i, j); exchange_at(s_ci, i, j); exchange_at(s_bucket, i, j); });
     // 3a. whose target scores a long-target element: its own (batch not full), the batch's h-th element's (full batch, when that
     //     one's target is long), nobody's (score 0)
     for (uint32_t p = threadIdx.x; p < npool; p += 256) {
@@ -1740,13 +1589,13 @@ __global__ __launch_bounds__(256) void pf_long_kernel(PfDedupArgs A) {
         __syncthreads();
         for (uint32_t ci = threadIdx.x; ci < ncand; ci += 256) {
             const PfCand *cp = cand_slot(A, bucket, ci);
-            atomicMax(&s_tab[cp->id >> bshift], (pf_el_count(cp->score) << 24) | (0xFFFFFFu - min(ci, 0xFFFFFEu)));
+            atomicMax(&s_tab[cp->id >> bshift], keepmax_key(pf_el_count(cp->score), ci));
         }
         __syncthreads();
         for (uint32_t ci = threadIdx.x; ci < ncand; ci += 256) {
             const PfCand c = *cand_slot(A, bucket, ci);
             const uint32_t cnt = pf_el_count(c.score);
-            if (s_tab[c.id >> bshift] == ((cnt << 24) | (0xFFFFFFu - min(ci, 0xFFFFFEu))) && cnt >= A.min_diag_score)
+            if (s_tab[c.id >> bshift] == keepmax_key(cnt, ci) && cnt >= A.min_diag_score)
                 surv[atomicAdd(&A.surv_count[q], 1u)] = c;
         }
         __syncthreads();
@@ -1771,8 +1620,8 @@ __global__ __launch_bounds__(128) void pf_keepmax_nucl_kernel(PfDedupArgs A) {
     __shared__ uint32_t s_first[2][PF_IDS_PER_BIN];
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const uint32_t B = A.bins;
-    const uint64_t bucket = (uint64_t)A.q_first * B + (uint64_t)blockIdx.x * 2u + (uint32_t)wave;
-    if (bucket >= (uint64_t)(A.q_first + A.n_queries) * B) return;
+    uint64_t bucket;
+    if (!pf_wave_bucket(A, 2u, &bucket)) return;
     const uint32_t ncand = A.cand_count[bucket];
     const uint32_t q = (uint32_t)(bucket / B);
     if (ncand == 0) return;
@@ -1785,32 +1634,23 @@ __global__ __launch_bounds__(128) void pf_keepmax_nucl_kernel(PfDedupArgs A) {
         return;
     }
     uint32_t *K = s_key[wave], *F = s_first[wave];
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
+    const int bshift = pf_bin_shift(B);
     for (int k = lane; k < PF_IDS_PER_BIN; k += 64) { K[k] = 0; F[k] = 0xFFFFFFFFu; }
     auto key_of = [&](const PfCand &c, uint32_t ci) -> uint32_t {
         const uint32_t cnt = min(255u, c.score);
-        return cnt >= 255u ? (0xFF000000u | min(c.score, 0xFFFFFFu)) : ((cnt << 24) | (0xFFFFFFu - min(ci, 0xFFFFFEu)));
+        return cnt >= 255u ? (0xFF000000u | min(c.score, 0xFFFFFFu)) : keepmax_key(cnt, ci);
     };
     // the saturated elements also go to the query's export list: the range the reference sorts is all of them (fetch)
     for (uint32_t c0 = 0; c0 < ncand; c0 += 64) {
         const uint32_t ci = c0 + (uint32_t)lane;
         bool sat = false;
-        PfCand c;
-        c.id = 0; c.arr = 0; c.score = 0; c.diag = 0; c.pad = 0;
+        PfCand c = pf_cand_zero();
         if (ci < ncand) {
             c = *cand_slot(A, bucket, ci);
             atomicMax(&K[c.id >> bshift], key_of(c, ci));
             sat = c.score >= 255u;
         }
-        const uint64_t sb = ballot(sat);
-        if (sb && A.q_nsat) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&A.q_nsat[q], (uint32_t)__popcll(sb));
-            base = __shfl(base, 0);
-            const uint32_t slot = base + (uint32_t)__popcll(sb & lanes_below(lane));
-            if (sat && slot < A.sat_cap) A.sat[(size_t)q * A.sat_cap + slot] = c;
-        }
+        if (A.q_nsat) wave_append(&A.q_nsat[q], A.sat + (size_t)q * A.sat_cap, sat, c, A.sat_cap);
     }
     for (uint32_t c0 = 0; c0 < ncand; c0 += 64) {
         const uint32_t ci = c0 + (uint32_t)lane;
@@ -1823,8 +1663,7 @@ __global__ __launch_bounds__(128) void pf_keepmax_nucl_kernel(PfDedupArgs A) {
     for (uint32_t c0 = 0; c0 < ncand; c0 += 64) {
         const uint32_t ci = c0 + (uint32_t)lane;
         bool win = false;
-        PfCand c;
-        c.id = 0; c.arr = 0; c.score = 0; c.diag = 0; c.pad = 0;
+        PfCand c = pf_cand_zero();
         if (ci < ncand) {
             c = *cand_slot(A, bucket, ci);
             const uint32_t t = c.id >> bshift;
@@ -1836,13 +1675,7 @@ __global__ __launch_bounds__(128) void pf_keepmax_nucl_kernel(PfDedupArgs A) {
                 if (w.diag != c.diag && A.q_flags) atomicOr(&A.q_flags[q], 4u);      // decided with the query's saturated total (fetch)
             }
         }
-        const uint64_t wb = ballot(win);
-        if (wb) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&A.surv_count[q], (uint32_t)__popcll(wb));
-            base = __shfl(base, 0);
-            if (win) surv[base + (uint32_t)__popcll(wb & lanes_below(lane))] = c;
-        }
+        wave_append(&A.surv_count[q], surv, win, c);
     }
 }
 
@@ -1922,8 +1755,7 @@ __global__ __launch_bounds__(256) void pf_overflow_kernel(PfOvfArgs A) {
     __shared__ int8_t smat[32 * 32];
     const PfDedupArgs &D = A.D;
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    for (int k = (int)threadIdx.x; k < 32 * 32; k += 256)      // rows of 32 (seg_cells_n)
-        smat[k] = ((k >> 5) < D.alphabet && (k & 31) < D.alphabet) ? D.mat[(k >> 5) * D.alphabet + (k & 31)] : (int8_t)0;
+    pf_load_smat32<256>(smat, D.mat, D.alphabet);
     __syncthreads();
     const uint32_t B = D.bins;
     const uint64_t w = (uint64_t)blockIdx.x * 4u + (uint32_t)wave;
@@ -1938,8 +1770,7 @@ __global__ __launch_bounds__(256) void pf_overflow_kernel(PfOvfArgs A) {
     const uint64_t bucket = (uint64_t)q * B + bin;
     const uint32_t ncand = D.cand_count[bucket];
     uint32_t *tab = s_tab[wave];
-    int bshift = 0;
-    while ((1u << bshift) < B) bshift++;
+    const int bshift = pf_bin_shift(B);
     const uint64_t below = lanes_below(lane);
     const uint64_t base = A.ovf_base[qi] + (uint64_t)(D.cand_base[bucket] - D.cand_base[(uint64_t)q * B]);
     PfOvfElem *O = A.buf_a + base, *S = A.buf_b + base;
@@ -2080,7 +1911,7 @@ __global__ __launch_bounds__(256) void pf_overflow_kernel(PfOvfArgs A) {
         const uint32_t idx = r0 + (uint32_t)lane;
         if (idx < n) {
             const uint32_t cnt = min(255u, cur[idx].score);
-            atomicMax(&tab[cur[idx].id >> bshift], (cnt << 24) | (0xFFFFFFu - min(idx, 0xFFFFFEu)));
+            atomicMax(&tab[cur[idx].id >> bshift], keepmax_key(cnt, idx));
         }
     }
     PfOvfElem *dst = cur == O ? S : O;
@@ -2100,7 +1931,7 @@ __global__ __launch_bounds__(256) void pf_overflow_kernel(PfOvfArgs A) {
         }
         const uint64_t kb = ballot(keep);
         if (final_step) {
-            if (kb) {
+            if (kb) {      // (wave_append's steps, spelled out for the same reason as in score_chunk)
                 uint32_t sb = 0;
                 if (lane == 0) sb = atomicAdd(&D.surv_count[q], (uint32_t)__popcll(kb));
                 sb = __shfl(sb, 0);
@@ -2137,15 +1968,6 @@ __global__ __launch_bounds__(256) void pf_overflow_kernel(PfOvfArgs A) {
 
 // ---------------------------------------------------------------------------------------------------------
 // a9: one workgroup per query over the query's surviving elements (one per target).
-__device__ __forceinline__ uint32_t rescaled_count(uint32_t score, float fms) {
-    // rescoreHits, QueryMatcher.cpp:576-581
-    const uint32_t ns = score - 255u;
-    const float sc = (float)min(ns, 65535u);
-    const float r = __fmul_rn(__fdiv_rn(sc, fms), 255.0f);
-    const double dd = (double)r + 0.5;
-    return (uint32_t)(int)dd & 0xFFu;
-}
-
 // Ordinal, in the query's stream of similar-k-mer lists, of the list that holds arrival index `arr`: the part of the
 // CPU's arrival order that does not depend on which targets a shard holds (windows and their similar k-mers are a
 // function of the query alone), used to order elements of different shards of a multi-GPU run (pf_shard_kernels.hip).
@@ -2206,13 +2028,7 @@ __global__ __launch_bounds__(256) void pf_select_kernel(PfSelectArgs A) {
     for (uint32_t k = threadIdx.x; k < n; k += 256) atomicAdd(&hist[pf_el_count(S[k].score)], 1u);
     __syncthreads();
     if (threadIdx.x == 0) {
-        // computeScoreThreshold, QueryMatcher.h:211-221
-        uint32_t found = 0, thr = 0;
-        for (thr = 255; thr > 0; thr--) {
-            found += hist[thr];
-            if (found >= max_hits) break;
-        }
-        const uint32_t dthr = max(A.min_diag_score, thr);
+        const uint32_t dthr = pf_score_threshold(hist, max_hits, A.min_diag_score);
         sh_thr = dthr;
         sh_trunc = (dthr >= 255u && !A.kmer_score) ? 1u : 0u;   // getResult<KMER_SCORE> has no truncated-threshold path
         sh_nelig = 0;
@@ -2221,9 +2037,7 @@ __global__ __launch_bounds__(256) void pf_select_kernel(PfSelectArgs A) {
     __syncthreads();
     const uint32_t dthr = sh_thr;
     const bool trunc = sh_trunc != 0;
-    int ms = A.q_self_score[q] - 255;
-    ms = ms > 1 ? ms : 1;
-    ms = ms < 65535 ? ms : 65535;
+    const int ms = pf_self_clamp(A.q_self_score[q]);
     const float fms = (float)ms;
     const uint32_t refmask = A.ref_bins - 1;
 
@@ -2308,21 +2122,7 @@ __global__ __launch_bounds__(256) void pf_select_kernel(PfSelectArgs A) {
                 __syncthreads();
                 for (uint32_t k = m + threadIdx.x; k < mp2; k += 256) skey[k] = ~0ull;
                 __syncthreads();
-                for (uint32_t size = 2; size <= mp2; size <<= 1) {
-                    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-                        for (uint32_t k = threadIdx.x; k < mp2 / 2; k += 256) {
-                            const uint32_t i = 2 * k - (k & (stride - 1));
-                            const uint32_t j = i + stride;
-                            const bool up = (i & size) == 0;
-                            const uint64_t a = skey[i], b = skey[j];
-                            if ((a > b) == up) {
-                                skey[i] = b;
-                                skey[j] = a;
-                            }
-                        }
-                        __syncthreads();
-                    }
-                }
+                block_bitonic_sort<256>(mp2, [&](uint32_t i, uint32_t j) { return skey[i] > skey[j]; }, [&](uint32_t i, uint32_t j) { exchange_at(skey, i, j); });
                 if (threadIdx.x == 0) sh_prefix = skey[rem - 1];      // the rem-th smallest key of the class: everything up to it is taken
                 __syncthreads();
                 break;
@@ -2352,11 +2152,7 @@ __global__ __launch_bounds__(256) void pf_select_kernel(PfSelectArgs A) {
                         A.xhits[(size_t)q * A.hit_stride + slot] = x;
                     }
                 } else if (slot < sort_cap) {
-                    uint32_t pref;
-                    const uint32_t cnt = pf_el_count(c.score);
-                    if (trunc) pref = 255u + (rescaled_count(pf_el_exact(c.score), fms) * (uint32_t)ms / 255u);
-                    else pref = (cnt >= 255u && !A.kmer_score) ? pf_el_exact(c.score) : cnt;
-                    skey[slot] = ((uint64_t)(0xFFFFFFFFu - pref) << 32) | (uint64_t)c.id;
+                    skey[slot] = pf_hit_key(pf_pref_score(trunc, A.kmer_score, pf_el_count(c.score), pf_el_exact(c.score), ms), c.id);
                     sdiag[slot] = c.diag;
                 }
             }
@@ -2385,43 +2181,13 @@ __global__ __launch_bounds__(256) void pf_select_kernel(PfSelectArgs A) {
     }
     if (BIG) __threadfence();
     __syncthreads();
-    for (uint32_t size = 2; size <= np2; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t k = threadIdx.x; k < np2 / 2; k += 256) {
-                const uint32_t i = 2 * k - (k & (stride - 1));
-                const uint32_t j = i + stride;
-                const bool up = (i & size) == 0;
-                const uint64_t a = skey[i], b = skey[j];
-                if ((a > b) == up) {
-                    skey[i] = b;
-                    skey[j] = a;
-                    const uint16_t t = sdiag[i];
-                    sdiag[i] = sdiag[j];
-                    sdiag[j] = t;
-                }
-            }
-            if (BIG) __threadfence();
-            __syncthreads();
-        }
-    }
-    for (uint32_t k = threadIdx.x; k < nsel; k += 256) {
-        mmgpu_pf_hit h;
-        h.id = (uint32_t)skey[k];
-        h.score = (int32_t)(0xFFFFFFFFu - (uint32_t)(skey[k] >> 32));
-        h.diagonal = sdiag[k];
-        h.reserved = 0;
-        out[has_ident + k] = h;
-    }
+    block_bitonic_sort<256, BIG>(np2, [&](uint32_t i, uint32_t j) { return skey[i] > skey[j]; },
+                            [&](uint32_t i, uint32_t j) { exchange_at(skey, i, j); exchange_at(sdiag, i, j); });
+    // self hit first, score USHRT_MAX - UCHAR_MAX for getResult<KMER_SCORE> (:410-413); nothing is selected when max_hits == 0
+    const uint32_t nout = pf_write_hits<256>(out, max_hits > 0 ? has_ident : 0u, ident, A.kmer_score ? 255 : 65535, nsel,
+                                             [&](uint32_t k) { return skey[k]; }, [&](uint32_t k) { return sdiag[k]; });
     if (threadIdx.x == 0) {
-        if (has_ident && max_hits > 0) {   // self hit first, score USHRT_MAX (getResult :408-424)
-            mmgpu_pf_hit h;
-            h.id = ident;
-            h.score = A.kmer_score ? 255 : 65535;      // UCHAR_MAX for getResult<KMER_SCORE> (:410-413)
-            h.diagonal = 0;
-            h.reserved = 0;
-            out[0] = h;
-        }
-        A.hit_count[q] = (max_hits > 0 ? has_ident : 0u) + nsel;
+        A.hit_count[q] = nout;
         A.q_diag_thr[q] = dthr | (trunc ? 0x80000000u : 0u);
     }
 }
@@ -2451,8 +2217,7 @@ __global__ __launch_bounds__(256) void pf_merge_kernel(PfMergeArgs A) {
         const mmgpu_pf_hit *src = A.hits + ((size_t)sp * A.nq + q) * A.stride;
         for (uint32_t k = threadIdx.x; k < n; k += 256) {
             const mmgpu_pf_hit h = src[k];
-            const uint32_t a = (uint32_t)(h.score < 0 ? -h.score : h.score);
-            skey[sbase[sp] + k] = ((uint64_t)(0xFFFFFFFFu - a) << 32) | (uint64_t)(h.id + A.id_offset[sp]);
+            skey[sbase[sp] + k] = pf_hit_key((uint32_t)(h.score < 0 ? -h.score : h.score), h.id + A.id_offset[sp]);
             sdiag[sbase[sp] + k] = h.diagonal;
         }
     }
@@ -2464,34 +2229,40 @@ __global__ __launch_bounds__(256) void pf_merge_kernel(PfMergeArgs A) {
         sdiag[k] = 0;
     }
     __syncthreads();
-    for (uint32_t size = 2; size <= np2; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t k = threadIdx.x; k < np2 / 2; k += 256) {
-                const uint32_t i = 2 * k - (k & (stride - 1));
-                const uint32_t j = i + stride;
-                const bool up = (i & size) == 0;
-                const uint64_t a = skey[i], b = skey[j];
-                if ((a > b) == up) {
-                    skey[i] = b;
-                    skey[j] = a;
-                    const uint16_t t = sdiag[i];
-                    sdiag[i] = sdiag[j];
-                    sdiag[j] = t;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    mmgpu_pf_hit *dst = A.out_hits + (size_t)q * A.n_splits * A.stride;
-    for (uint32_t k = threadIdx.x; k < total; k += 256) {
-        mmgpu_pf_hit h;
-        h.id = (uint32_t)skey[k];
-        h.score = (int32_t)(0xFFFFFFFFu - (uint32_t)(skey[k] >> 32));
-        h.diagonal = sdiag[k];
-        h.reserved = 0;
-        dst[k] = h;
-    }
+    block_bitonic_sort<256>(np2, [&](uint32_t i, uint32_t j) { return skey[i] > skey[j]; },
+                            [&](uint32_t i, uint32_t j) { exchange_at(skey, i, j); exchange_at(sdiag, i, j); });
+    pf_write_hits<256>(A.out_hits + (size_t)q * A.n_splits * A.stride, 0u, 0u, 0, total, [&](uint32_t k) { return skey[k]; },
+                       [&](uint32_t k) { return sdiag[k]; });      // (no self hit: the shards' lists carry it)
     if (threadIdx.x == 0) A.out_counts[q] = total;
+}
+
+// one bit per k-mer: does its index list hold an entry?  (a sparse index - a shard of a multi-GPU run, a small database - answers most
+// similar k-mers of a query from this 8 MB table instead of a 64-byte sector of the 256 MB offset table)
+__global__ __launch_bounds__(256) void pf_bitmap_kernel(const uint32_t *offsets, uint64_t table, uint32_t *bitmap, unsigned long long *nonempty) {
+    const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t k0 = w * 32u;
+    uint32_t bits = 0;
+    if (k0 < table) {
+        uint32_t prev = offsets[k0];
+        for (uint32_t b = 0; b < 32u && k0 + b < table; b++) {
+            const uint32_t next = offsets[k0 + b + 1];
+            if (next != prev) bits |= 1u << b;
+            prev = next;
+        }
+        bitmap[w] = bits;
+    }
+    wave_sum_to(nonempty, (unsigned long long)__popc(bits));
+}
+
+// tile t of query q: (tile_q, tile_idx) = (q, t) - the split kernel's work list, written where it is read
+__global__ __launch_bounds__(256) void pf_tiles_kernel(const uint32_t *q_tile_base, const uint32_t *q_ntiles, uint32_t nq, uint32_t *tile_q, uint32_t *tile_idx) {
+    const uint32_t q = blockIdx.x;
+    if (q >= nq) return;
+    const uint32_t base = q_tile_base[q], n = q_ntiles[q];
+    for (uint32_t t = threadIdx.x; t < n; t += 256) {
+        tile_q[base + t] = q;
+        tile_idx[base + t] = t;
+    }
 }
 
 }  // namespace
@@ -2534,37 +2305,6 @@ hipError_t launch_pf_kmers(const PfKmerArgs &A, bool emit, hipStream_t s) {
         }
     }
     return hipGetLastError();
-}
-
-// one bit per k-mer: does its index list hold an entry?  (a sparse index - a shard of a multi-GPU run, a small database - answers most
-// similar k-mers of a query from this 8 MB table instead of a 64-byte sector of the 256 MB offset table)
-__global__ __launch_bounds__(256) void pf_bitmap_kernel(const uint32_t *offsets, uint64_t table, uint32_t *bitmap, unsigned long long *nonempty) {
-    const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint64_t k0 = w * 32u;
-    uint32_t bits = 0;
-    if (k0 < table) {
-        uint32_t prev = offsets[k0];
-        for (uint32_t b = 0; b < 32u && k0 + b < table; b++) {
-            const uint32_t next = offsets[k0 + b + 1];
-            if (next != prev) bits |= 1u << b;
-            prev = next;
-        }
-        bitmap[w] = bits;
-    }
-    unsigned long long n = (unsigned long long)__popc(bits);
-    for (int d = 1; d < 64; d <<= 1) n += __shfl_xor(n, d);
-    if (lane_id() == 0 && n) atomicAdd(nonempty, n);
-}
-
-// tile t of query q: (tile_q, tile_idx) = (q, t) - the split kernel's work list, written where it is read
-__global__ __launch_bounds__(256) void pf_tiles_kernel(const uint32_t *q_tile_base, const uint32_t *q_ntiles, uint32_t nq, uint32_t *tile_q, uint32_t *tile_idx) {
-    const uint32_t q = blockIdx.x;
-    if (q >= nq) return;
-    const uint32_t base = q_tile_base[q], n = q_ntiles[q];
-    for (uint32_t t = threadIdx.x; t < n; t += 256) {
-        tile_q[base + t] = q;
-        tile_idx[base + t] = t;
-    }
 }
 
 hipError_t launch_pf_tiles(const uint32_t *q_tile_base, const uint32_t *q_ntiles, uint32_t nq, uint32_t *tile_q, uint32_t *tile_idx, hipStream_t s) {

@@ -11,20 +11,11 @@
 // pf_localize_kernel then gives every device the part of the merged lists whose targets it holds (list order kept), as
 // input of the alignment (mmgpu_sw_prepare_from_lists).
 #include "mmgpu_internal.h"
+#include "pf_device.h"
 
 namespace mmgpu {
 
 namespace {
-
-__device__ __forceinline__ uint32_t x_rescaled_count(uint32_t score, float fms) {
-    // rescoreHits, QueryMatcher.cpp:578-581: (score - 255) / maxSelfScore * 255 + 0.5, float arithmetic, cut to a byte
-    uint32_t ns = score - 255u;
-    ns = ns < 65535u ? ns : 65535u;
-    const float sc = (float)ns;
-    const float r = __fmul_rn(__fdiv_rn(sc, fms), 255.0f);
-    const double dd = (double)r + 0.5;
-    return (uint32_t)(int)dd & 0xFFu;
-}
 
 struct XKey {
     uint32_t a, b, c;   // (255 - count) << 11 | bin ; list ordinal ; global id
@@ -79,21 +70,14 @@ __global__ __launch_bounds__(256) void pf_xmerge_kernel(PfXMergeArgs A) {
     __syncthreads();
     const uint32_t max_hits = A.max_hits;
     if (threadIdx.x == 0) {
-        uint32_t found = 0, thr = 0;   // computeScoreThreshold, QueryMatcher.h:211-221
-        for (thr = 255; thr > 0; thr--) {
-            found += hist[thr];
-            if (found >= max_hits) break;
-        }
-        const uint32_t dthr = max(A.min_diag_score, thr);
+        const uint32_t dthr = pf_score_threshold(hist, max_hits, A.min_diag_score);
         sh_thr = dthr;
         sh_trunc = dthr >= 255u ? 1u : 0u;
     }
     __syncthreads();
     const uint32_t dthr = sh_thr;
     const bool trunc = sh_trunc != 0;
-    int ms = A.q_self_score[q] - 255;
-    ms = ms > 1 ? ms : 1;
-    ms = ms < 65535 ? ms : 65535;
+    const int ms = pf_self_clamp(A.q_self_score[q]);
     const float fms = (float)ms;
     const uint32_t refmask = A.ref_bins - 1;
     auto key_of = [&](uint32_t e) -> XKey {
@@ -104,7 +88,7 @@ __global__ __launch_bounds__(256) void pf_xmerge_kernel(PfXMergeArgs A) {
         uint32_t kc;
         if (trunc) {
             el = cnt >= 255u && gid != ident;
-            kc = x_rescaled_count(sc, fms);
+            kc = rescaled_count(sc, fms);
         } else {
             el = cnt >= dthr && gid != ident;
             kc = cnt;
@@ -124,24 +108,15 @@ __global__ __launch_bounds__(256) void pf_xmerge_kernel(PfXMergeArgs A) {
     if (mine) atomicAdd(&sh_nelig, mine);
     __syncthreads();
     // bitonic sort of the permutation by the unsplit run's array order; slots >= total sort to the end
-    for (uint32_t size = 2; size <= np2; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t k = threadIdx.x; k < np2 / 2; k += 256) {
-                const uint32_t i = 2 * k - (k & (stride - 1));
-                const uint32_t j = i + stride;
-                const bool up = (i & size) == 0;
-                const uint32_t pi = s_perm[i], pj = s_perm[j];
-                XKey ki, kj;
-                if (pi < total) ki = key_of(pi); else { ki.a = 0xFFFFFFFFu; ki.b = 0xFFFFFFFFu; ki.c = 0xFFFFFFFFu; }
-                if (pj < total) kj = key_of(pj); else { kj.a = 0xFFFFFFFFu; kj.b = 0xFFFFFFFFu; kj.c = 0xFFFFFFFFu; }
-                if (xkey_less(kj, ki) == up) {
-                    s_perm[i] = (uint16_t)pj;
-                    s_perm[j] = (uint16_t)pi;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    auto key_at = [&](uint32_t slot) -> XKey {
+        const uint32_t e = s_perm[slot];
+        if (e < total) return key_of(e);
+        XKey k;
+        k.a = 0xFFFFFFFFu; k.b = 0xFFFFFFFFu; k.c = 0xFFFFFFFFu;
+        return k;
+    };
+    block_bitonic_sort<256>(np2, [&](uint32_t i, uint32_t j) { return xkey_less(key_at(j), key_at(i)); },
+                            [&](uint32_t i, uint32_t j) { exchange_at(s_perm, i, j); });
     const uint32_t has_ident = ident != 0xFFFFFFFFu ? 1u : 0u;
     const uint32_t want = max_hits > has_ident ? max_hits - has_ident : 0u;
     const uint32_t nsel = min(sh_nelig, want);
@@ -157,11 +132,7 @@ __global__ __launch_bounds__(256) void pf_xmerge_kernel(PfXMergeArgs A) {
         if (k < nsel) {
             const uint32_t e = s_perm[k];
             const uint32_t sc = s_score[e];
-            const uint32_t cnt = min(255u, sc);
-            uint32_t pref;
-            if (trunc) pref = 255u + (x_rescaled_count(sc, fms) * (uint32_t)ms / 255u);
-            else pref = cnt >= 255u ? sc : cnt;
-            rkey[z] = ((uint64_t)(0xFFFFFFFFu - pref) << 32) | (uint64_t)s_gid[e];
+            rkey[z] = pf_hit_key(pf_pref_score(trunc, false, min(255u, sc), sc, ms), s_gid[e]);
             // diagonal: re-read from the record (not kept in LDS)
             uint32_t sp = 0;
             while (sp + 1 < A.n_shards && sbase[sp + 1] <= e) sp++;
@@ -182,42 +153,14 @@ __global__ __launch_bounds__(256) void pf_xmerge_kernel(PfXMergeArgs A) {
     }
     __syncthreads();
     // bitonic sort by (prefScore desc, id asc)   (hit_t::compareHitsByScoreAndId, QueryMatcher.h:38-49)
-    for (uint32_t size = 2; size <= np2b; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t k = threadIdx.x; k < np2b / 2; k += 256) {
-                const uint32_t i = 2 * k - (k & (stride - 1));
-                const uint32_t j = i + stride;
-                const bool up = (i & size) == 0;
-                const uint64_t a = ((uint64_t)s_score[i] << 32) | s_gid[i], b = ((uint64_t)s_score[j] << 32) | s_gid[j];
-                if ((a > b) == up) {
-                    const uint32_t g = s_gid[i], sc = s_score[i];
-                    const uint16_t d = s_perm[i];
-                    s_gid[i] = s_gid[j]; s_score[i] = s_score[j]; s_perm[i] = s_perm[j];
-                    s_gid[j] = g; s_score[j] = sc; s_perm[j] = d;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    mmgpu_pf_hit *out = A.out_hits + (size_t)q * A.out_stride;
-    for (uint32_t k = threadIdx.x; k < nsel; k += 256) {
-        mmgpu_pf_hit h;
-        h.id = s_gid[k];
-        h.score = (int32_t)(0xFFFFFFFFu - s_score[k]);
-        h.diagonal = s_perm[k];
-        h.reserved = 0;
-        out[has_ident + k] = h;
-    }
+    auto key2 = [&](uint32_t k) -> uint64_t { return ((uint64_t)s_score[k] << 32) | s_gid[k]; };
+    block_bitonic_sort<256>(np2b, [&](uint32_t i, uint32_t j) { return key2(i) > key2(j); },
+                            [&](uint32_t i, uint32_t j) { exchange_at(s_gid, i, j); exchange_at(s_score, i, j); exchange_at(s_perm, i, j); });
+    // (no element is selected when max_hits == 0: the self hit, score USHRT_MAX, is what stands at out[0] otherwise)
+    const uint32_t nout = pf_write_hits<256>(A.out_hits + (size_t)q * A.out_stride, max_hits > 0 ? has_ident : 0u, ident, 65535, nsel, key2,
+                                             [&](uint32_t k) { return s_perm[k]; });
     if (threadIdx.x == 0) {
-        if (has_ident && max_hits > 0) {   // self hit first, score USHRT_MAX (getResult :408-424)
-            mmgpu_pf_hit h;
-            h.id = ident;
-            h.score = 65535;
-            h.diagonal = 0;
-            h.reserved = 0;
-            out[0] = h;
-        }
-        A.out_counts[q] = (max_hits > 0 ? has_ident : 0u) + nsel;
+        A.out_counts[q] = nout;
         if (A.out_flags) A.out_flags[q] = sh_inexact;
     }
 }

@@ -38,6 +38,7 @@
 // Bytes per cell that ever touch HBM: (tlen + 28) / (qlen * tlen) ~ 0.003 - this kernel
 // is bound by VALU issue, not by HBM.
 #include "mmgpu_internal.h"
+#include "pf_device.h"
 
 namespace mmgpu {
 
@@ -778,21 +779,7 @@ __global__ __launch_bounds__(256) void sw_from_pf_kernel(SwFromPfArgs A) {
             if (r == 0) atomicMax(stat + 2, (unsigned long long)(0xFFFFu - (mine >> 16)));   // longest target of any list
         }
     } else {
-    for (uint32_t size = 2; size <= np2; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t k = threadIdx.x; k < np2 / 2; k += 256) {
-                const uint32_t i = 2 * k - (k & (stride - 1));
-                const uint32_t j = i + stride;
-                const bool up = (i & size) == 0;
-                const uint32_t a = key[i], b = key[j];
-                if ((a > b) == up) {
-                    key[i] = b;
-                    key[j] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    block_bitonic_sort<256>(np2, [&](uint32_t i, uint32_t j) { return key[i] > key[j]; }, [&](uint32_t i, uint32_t j) { exchange_at(key, i, j); });
     for (uint32_t r = threadIdx.x; r < n; r += 256) {
         const uint32_t k = key[r] & 0xFFFFu;
         A.hit_target[base + r] = hits[k].id;
@@ -808,8 +795,7 @@ __global__ __launch_bounds__(256) void sw_from_pf_kernel(SwFromPfArgs A) {
     }
     if (threadIdx.x == 0) A.count_copy[q] = n;
     // statistics (cells = forward DP cells, Alignment.cpp:380,530 convention)
-    for (int d = 1; d < 64; d <<= 1) cells += __shfl_xor(cells, d);
-    if ((threadIdx.x & 63u) == 0 && cells) atomicAdd(stat, cells);
+    wave_sum_to(stat, cells);
     if (threadIdx.x == 0 && n) atomicAdd(stat + 1, (unsigned long long)n);
 }
 
