@@ -168,6 +168,29 @@ int mmgpu_sw_prepare_from_pf(mmgpu_ctx *ctx, const mmgpu_sw_params *params, cons
  * targets, d_counts [n_queries] uint32.  The lists are copied during the call. */
 int mmgpu_sw_prepare_from_lists(mmgpu_ctx *ctx, const mmgpu_sw_params *params, const mmgpu_sw_query *queries, uint32_t n_queries,
                                 int mode, const void *d_hits, const void *d_counts, uint32_t stride, mmgpu_sw_batch_t **batch);
+/* A batch over masked targets (Alignment::computeAlternativeAlignment, Alignment.cpp:569-601: --alt-ali overwrites the target
+ * residues [dbStartPos, dbEndPos) of an accepted hit with X and aligns again).  Every pair of the lists gets a private copy of
+ * its target, gathered on the device out of the resident database, in which the residues of the pair's spans read as
+ * mask_letter; the resident database is not touched.  queries as for mmgpu_sw_prepare.  A pair may own any number of spans,
+ * none included; spans may be empty (t_from == t_to), overlap, touch and come in any order.  MMGPU_ERR_ARG: masks == NULL, a
+ * span_off that is not monotone, mask_letter outside [0, alphabet), a span with t_from > t_to or t_to > the target's length.
+ * MMGPU_ERR_UNSUPPORTED: more than 16 GiB of copies.  The batch is an ordinary batch in every later call (run, fetch,
+ * fetch_device, reverse_pairs, traceback, block_backtrace, block_starts, block_growth, batch_stats, kernel_ms, free): same
+ * indices, same records, all three modes, sequence and profile queries.  The lists of a prefilter batch, device lists and the
+ * owned pairs of a sharded run have no masked form. */
+typedef struct { uint32_t t_from, t_to; } mmgpu_sw_span;      /* residues [t_from, t_to) of the pair's target read as mask_letter */
+typedef struct {
+    const uint32_t *span_off;    /* [P + 1], P = sum of n_targets; pair p (query-major, list order = the result array's order)
+                                    owns spans[span_off[p] .. span_off[p+1]) */
+    const mmgpu_sw_span *spans;
+    int mask_letter;             /* aa2num['X'] (20) */
+} mmgpu_sw_masks;
+int mmgpu_sw_prepare_masked(mmgpu_ctx *ctx, const mmgpu_sw_params *params, const mmgpu_sw_query *queries, uint32_t n_queries,
+                            int mode, const mmgpu_sw_masks *masks, mmgpu_sw_batch_t **batch);
+/* test aid, like mmgpu_pf_debug_masked_targets: the batch's copy of pair p's target as the kernels see it -
+ * ((len + 3) & ~3) bytes, pad letters included; *len = the target's length.  out == NULL with cap == 0 is the size query: it sets
+ * *len and returns MMGPU_OK.  MMGPU_ERR_STATE for a batch that is not masked, MMGPU_ERR_ARG when cap is too small.  Synchronises. */
+int mmgpu_sw_debug_masked_target(mmgpu_ctx *ctx, mmgpu_sw_batch_t *batch, uint32_t pair, uint8_t *out, size_t cap, uint32_t *len);
 int mmgpu_sw_run(mmgpu_ctx *ctx, mmgpu_sw_batch_t *batch);
 int mmgpu_sw_fetch(mmgpu_ctx *ctx, mmgpu_sw_batch_t *batch, mmgpu_sw_hit *out);
 /* The reverse scan (StripedSmithWaterman.cpp:1129-1204) after the fact, for exactly the pairs named (indices into the batch's result

@@ -42,6 +42,10 @@ class SwQuery(ctypes.Structure):
                 ("profile_letters", ctypes.c_uint32)]
 
 
+class SwMasks(ctypes.Structure):      # mmgpu_sw_masks
+    _fields_ = [("span_off", c_p), ("spans", c_p), ("mask_letter", ctypes.c_int)]
+
+
 class NuclParams(ctypes.Structure):
     _fields_ = [("mat", c_p), ("reverse", c_p), ("gap_open", ctypes.c_int), ("gap_extend", ctypes.c_int), ("zdrop", ctypes.c_int),
                 ("past_end_query", ctypes.c_int), ("past_end_target", ctypes.c_int), ("wrapped", ctypes.c_int)]
@@ -83,6 +87,7 @@ EXPORTED_SYMBOLS = [
     "mmgpu_multi_pf_stride", "mmgpu_multi_pf_free", "mmgpu_multi_sw_from_pf", "mmgpu_multi_has_unsplit", "mmgpu_multi_pf_redone",
     "mmgpu_pf_exchange_redo_unsplit",
     "mmgpu_db_save", "mmgpu_db_probe", "mmgpu_db_load",
+    "mmgpu_sw_prepare_masked", "mmgpu_sw_debug_masked_target",
 ]
 
 
@@ -158,6 +163,8 @@ def load_library():
     L.mmgpu_sw_batch.argtypes = [c_p, ctypes.POINTER(SwParams), c_p, ctypes.c_uint32, ctypes.c_int, c_p]
     L.mmgpu_sw_prepare.argtypes = [c_p, ctypes.POINTER(SwParams), c_p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(c_p)]
     L.mmgpu_sw_prepare_from_pf.argtypes = [c_p, ctypes.POINTER(SwParams), c_p, ctypes.c_uint32, ctypes.c_int, c_p, ctypes.POINTER(c_p)]
+    L.mmgpu_sw_prepare_masked.argtypes = [c_p, ctypes.POINTER(SwParams), c_p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(SwMasks), ctypes.POINTER(c_p)]
+    L.mmgpu_sw_debug_masked_target.argtypes = [c_p, c_p, ctypes.c_uint32, c_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
     L.mmgpu_sw_run.argtypes = [c_p, c_p]
     L.mmgpu_nucl_align.argtypes = [c_p, ctypes.POINTER(NuclParams), c_p, ctypes.c_uint32, c_p, ctypes.c_uint32, c_p, c_p,
                                    ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
@@ -529,6 +536,15 @@ class SwBatch:
             lists.append(np.stack([b[:, 0], b[:, 1], b[:, 2] >> 16, b[:, 2] & 0xFFFF, b[:, 3]], axis=1))
         return out, lists
 
+    def debug_masked_target(self, pair):
+        """mmgpu_sw_debug_masked_target (test aid, batches of sw_prepare_masked): -> (the copy of pair `pair`'s target as the kernels
+        read it, uint8[(len + 3) & ~3] with its pad letters, len)"""
+        n = ctypes.c_uint32()
+        self.gpu._check(self.gpu.L.mmgpu_sw_debug_masked_target(self.gpu.ctx, self.handle, int(pair), None, 0, ctypes.byref(n)))      # the size query
+        out = np.zeros((n.value + 3) & ~3, np.uint8)
+        self.gpu._check(self.gpu.L.mmgpu_sw_debug_masked_target(self.gpu.ctx, self.handle, int(pair), _ptr(out), out.size, ctypes.byref(n)))
+        return out, n.value
+
     def block_tiers(self):
         """mmgpu_sw_block_tiers: (pairs decided with <= 512-row blocks, pairs that needed the 4096-row launch) of the last call"""
         a, b = ctypes.c_uint32(), ctypes.c_uint32()
@@ -635,6 +651,37 @@ class MMGpu:
         par, arr, keep = self._marshal(mat, gap_open, gap_extend, queries)
         h = c_p()
         self._check(self.L.mmgpu_sw_prepare(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), mode, ctypes.byref(h)))
+        return SwBatch(self, h, keep)
+
+    def sw_prepare_masked(self, mat, gap_open, gap_extend, queries, mode=1, mask_letter=20):
+        """mmgpu_sw_prepare_masked: queries as for sw_prepare plus `masks`: one [k][2] integer array of (t_from, t_to) spans per entry
+        of `targets` (None or empty: no span; `masks` itself None or absent: none for the query).  The residues [t_from, t_to) of the
+        pair's private copy of its target read as mask_letter.  -> an ordinary SwBatch"""
+        par, arr, keep = self._marshal(mat, gap_open, gap_extend, queries)
+        span_off, spans = [0], []
+        for qd in queries:
+            n_t = len(qd["targets"])
+            masks = qd.get("masks")
+            if masks is None:
+                masks = [None] * n_t
+            if len(masks) != n_t:
+                raise ValueError("masks must hold one entry per target")
+            for m in masks:
+                m = np.zeros((0, 2), np.int64) if m is None else np.asarray(m, np.int64).reshape(-1, 2)
+                if m.size and (m.min() < 0 or m.max() > 0xFFFFFFFF):
+                    raise ValueError("span bounds must fit uint32")
+                spans.append(m)
+                span_off.append(span_off[-1] + len(m))
+        if span_off[-1] > 0xFFFFFFFF:
+            raise ValueError("more than 2^32 spans")
+        span_off = np.asarray(span_off, np.uint32)
+        spans = np.ascontiguousarray(np.concatenate(spans) if spans else np.zeros((0, 2)), np.uint32)
+        return self._sw_prepare_masked_raw(par, arr, keep, len(queries), span_off, spans, mode, mask_letter)
+
+    def _sw_prepare_masked_raw(self, par, arr, keep, nq, span_off, spans, mode, mask_letter):
+        mk = SwMasks(_ptr(span_off), _ptr(spans), int(mask_letter))
+        h = c_p()
+        self._check(self.L.mmgpu_sw_prepare_masked(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), nq, mode, ctypes.byref(mk), ctypes.byref(h)))
         return SwBatch(self, h, keep)
 
     def sw_marshal_queries(self, mat, gap_open, gap_extend, queries):
@@ -903,6 +950,77 @@ class MMGpu:
         off = np.ascontiguousarray(id_offsets, np.uint32)
         self._check(self.L.mmgpu_pf_merge_splits(self.ctx, c_p(d_hits_ptr), c_p(d_counts_ptr), n_splits, nq, stride, _ptr(off),
                                                  c_p(d_out_hits_ptr), c_p(d_out_counts_ptr)))
+
+
+def alt_next_spans(spans, records, accepted):
+    """The span bookkeeping of alt_alignments, without a device: spans = per pair the list of (t_from, t_to) masked so far, or
+    None for a pair that has dropped out; records = the pairs' latest alignments (SW_HIT_DTYPE, or anything with t_start /
+    t_end per pair); accepted = bool per pair.  -> the spans of the next round: a pair that is not accepted (or was out already)
+    is None from now on, an accepted one gains [t_start, t_end) - as Alignment::computeAlternativeAlignment overwrites
+    dbStartPos .. dbEndPos - 1 (Alignment.cpp:577-579); a one-residue alignment (t_start == t_end) adds the empty span."""
+    out = []
+    for p, sp in enumerate(spans):
+        if sp is None or not bool(accepted[p]):
+            out.append(None)
+            continue
+        out.append(list(sp) + [(int(records[p]["t_start"]), int(records[p]["t_end"]))])
+    return out
+
+
+def alt_alignments(gpu, mat, gap_open, gap_extend, queries, first, n_alt, accept, mask_letter=20, want_bt=False):
+    """The batch form of Alignment::computeAlternativeAlignment (Alignment.cpp:569-601, --alt-ali n_alt), round-synchronous over
+    all pairs of all queries.  queries as for sw_prepare; first = the records (SW_HIT_DTYPE, query-major, list order) of the accepted
+    first alignments; accept(query_index, records) -> bool[] is the caller's checkCriteria.  Every round masks [t_start, t_end)
+    of the latest alignment of every pair still alive, runs one masked batch (mode MMGPU_SW_START) over those pairs and drops the
+    pairs whose new alignment is not accepted; it ends after n_alt rounds or when no pair is left.
+    -> per pair the list of accepted further alignments in round order: dicts of the record's fields (+ bt, ident with want_bt)."""
+    n_t = [len(qd["targets"]) for qd in queries]
+    base = np.concatenate([[0], np.cumsum(n_t)]).astype(np.int64)
+    total = int(base[-1])
+    if len(first) != total:
+        raise ValueError("first must hold one record per pair")
+    spans = alt_next_spans([[] for _ in range(total)], first, np.ones(total, bool))
+    result = [[] for _ in range(total)]
+    for _ in range(int(n_alt)):
+        alive = [p for p in range(total) if spans[p] is not None]
+        if not alive:
+            break
+        sub, owner = [], []      # the live pairs of every query that still has one
+        for qi, qd in enumerate(queries):
+            ps = [p for p in range(int(base[qi]), int(base[qi + 1])) if spans[p] is not None]
+            if not ps:
+                continue
+            d = dict(qd)
+            d["targets"] = np.asarray(qd["targets"], np.uint32)[[p - int(base[qi]) for p in ps]]
+            d["masks"] = [spans[p] for p in ps]
+            sub.append(d)
+            owner.append((qi, ps))
+        b = gpu.sw_prepare_masked(mat, gap_open, gap_extend, sub, mode=1, mask_letter=mask_letter)
+        try:
+            b.run()
+            rec = b.fetch()
+            if want_bt:
+                info, strs = b.traceback(np.arange(len(rec), dtype=np.uint32))
+        finally:
+            b.free()
+        latest = [None] * total
+        ok = np.zeros(total, bool)
+        k = 0
+        for qi, ps in owner:
+            r = rec[k:k + len(ps)]
+            a = np.asarray(accept(qi, r), bool)
+            for z, p in enumerate(ps):
+                latest[p] = r[z]
+                ok[p] = a[z]
+                if a[z]:
+                    d = {f: int(r[z][f]) for f in SW_HIT_DTYPE.names}
+                    if want_bt:
+                        d["bt"] = strs[k + z] if int(info[k + z]["status"]) == 0 else None
+                        d["ident"] = int(info[k + z]["ident"])
+                    result[p].append(d)
+            k += len(ps)
+        spans = alt_next_spans(spans, latest, ok)
+    return result
 
 
 def split_max_hits(max_hits, n_splits):

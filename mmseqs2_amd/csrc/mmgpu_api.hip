@@ -534,7 +534,34 @@ struct mmgpu_sw_batch_t {
     bool o_dense = false;          // a rank's send buffer overflowed once: every rank's buffer holds all slots from now on
     DevBuf o_lhits, o_lcounts, o_lslot;        // merged lists restricted to this shard's targets (local ids) + their list positions
     DevBuf o_send, o_counter, o_recv, o_recv_counters, o_full, o_status;
+    // mmgpu_sw_prepare_masked: the batch's own targets - one masked copy per pair in DeviceDb's layout, id = pair ordinal
+    // (hit_target, h_out_target and the jobs of the later calls name these ids)
+    bool masked = false;
+    DevBuf m_res, m_off4, m_len;
+    std::vector<uint32_t> m_h_len;
+    uint32_t m_max_len = 0;
 };
+
+// the targets a batch's kernels read: the resident database, or the batch's masked copies
+static TargetView sw_targets(const mmgpu_ctx *c, const mmgpu_sw_batch_t *b) {
+    TargetView v;
+    if (b && b->masked) {
+        v.res = b->m_res.as<uint8_t>();
+        v.off4 = b->m_off4.as<uint32_t>();
+        v.len = b->m_len.as<uint32_t>();
+        v.n = (uint32_t)b->m_h_len.size();
+        v.max_len = b->m_max_len;
+        v.h_len = b->m_h_len.data();
+    } else {
+        v.res = c->db.res;
+        v.off4 = c->db.off4;
+        v.len = c->db.len;
+        v.n = c->db.n;
+        v.max_len = c->db.max_len;
+        v.h_len = c->h_len.data();
+    }
+    return v;
+}
 
 // which kernel body serves a query of this length: 16 lanes x R rows per tile (any R since round 5: the padding of a tile is
 // below 16 rows, it was below 32 with even R only), at most 16 * SW_MAX_R rows per tile; longer queries are cut into equal tiles
@@ -585,7 +612,9 @@ struct SwPrepare {
     uint32_t nq;
     int mode;
     const DeviceLists *pf;        // null: the lists are the caller's (mmgpu_sw_query::target_ids)
+    const mmgpu_sw_masks *masks;  // mmgpu_sw_prepare_masked: the batch aligns against masked copies of its targets (caller's lists only)
     mmgpu_sw_batch_t *b = nullptr;
+    TargetView tv;                // the targets the lists name: the resident database, or the batch's copies once plan_masked has run
 
     std::vector<uint8_t> qres;
     std::vector<int8_t> qcb, mat;
@@ -608,12 +637,18 @@ struct SwPrepare {
     int minp = 0;
     bool any_multi = false;
     PinnedLease pinned;                   // the context's staging arena, from enqueue_uploads until the call ends (stream drained)
+    // masked batch: the lists over the copies (ids = pair ordinals) that take the caller's place, and what the gather kernel reads
+    std::vector<mmgpu_sw_query> m_queries;
+    std::vector<uint32_t> m_ids, m_src, m_off4;
+    uint64_t m_bytes = 0;
     double mark = prep_now();
 
     void lap(const char *what);
     int check_params();
     void new_batch();
     int size_buffers();
+    int plan_masked();
+    int gather_masked();
     int copy_query(uint32_t i, int *qminp);
     void add_slot_jobs(uint32_t i, uint32_t shape, uint32_t round, bool multi);
     void add_rev_jobs(uint32_t query, uint32_t first, uint32_t n, uint32_t shape, uint64_t cells_per_hit);
@@ -693,6 +728,101 @@ int SwPrepare::size_buffers() {
     return MMGPU_OK;
 }
 
+// A masked batch's targets: pair p of the lists (query-major, list order) gets copy p of an arena laid out like the resident database
+// (mmgpu_load_targets), and the lists are rewritten to name the copies.  Everything after this step schedules over `tv`, the view of
+// the copies; the copies themselves are made at the end of the preparation (gather_masked).
+int SwPrepare::plan_masked() {
+    if (!masks->span_off) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_masked: NULL span_off");
+    if (masks->mask_letter < 0 || masks->mask_letter >= par->alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_masked: mask letter outside the alphabet");
+    const size_t P = (size_t)total_hits;
+    m_ids.resize(P);
+    m_src.resize(P);
+    m_off4.resize(std::max<size_t>(P, 1));
+    b->m_h_len.resize(P);
+    m_queries.assign(qs, qs + nq);
+    uint64_t cur4 = 16;      // the layout of mmgpu_load_targets: 64 B in front, 4-byte boundaries, max_len + 64 B behind
+    uint32_t max_len = 0;
+    size_t p = 0;
+    for (uint32_t i = 0; i < nq; i++) {
+        m_queries[i].target_ids = m_ids.data() + p;
+        for (uint32_t k = 0; k < qs[i].n_targets; k++, p++) {
+            const uint32_t t = qs[i].target_ids[k];
+            if (t >= c->db.n) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_masked: target id out of range");
+            const uint32_t l = c->h_len[t];
+            if (masks->span_off[p + 1] < masks->span_off[p]) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_masked: span_off not monotone");
+            if (!masks->spans && masks->span_off[p + 1] != masks->span_off[p]) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_masked: NULL spans");
+            for (uint32_t z = masks->span_off[p]; z < masks->span_off[p + 1]; z++)
+                if (masks->spans[z].t_from > masks->spans[z].t_to || masks->spans[z].t_to > l)
+                    return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_masked: span outside its target (need t_from <= t_to <= length)");
+            if (cur4 > 0xFFFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare_masked: more than 16 GiB of masked copies in one batch");
+            m_ids[p] = (uint32_t)p;
+            m_src[p] = t;
+            m_off4[p] = (uint32_t)cur4;
+            b->m_h_len[p] = l;
+            max_len = std::max(max_len, l);
+            cur4 += (l + 3) / 4;
+        }
+    }
+    m_bytes = cur4 * 4 + max_len + 64;
+    b->m_max_len = max_len;
+    b->masked = true;
+    qs = m_queries.data();
+    tv = sw_targets(c, b);      // (host side only until gather_masked has allocated the copies)
+    return MMGPU_OK;
+}
+
+// ... and the copies: pad letters everywhere (one memset), then sw_mask_gather_kernel, on the context's stream behind the uploads
+int SwPrepare::gather_masked() {
+    hipStream_t s = c->stream;
+    const size_t P = m_src.size();
+    DevBuf d_src, d_span_off, d_spans;
+    for (DevBuf *d : {&d_src, &d_span_off, &d_spans, &b->m_res, &b->m_off4, &b->m_len}) d->bind(c->cache);
+    const uint32_t s_first = masks->span_off[0], n_spans = masks->span_off[P] - s_first;
+    struct Event {      // MMGPU_TRACE: the memset + kernel between two events
+        hipEvent_t e = nullptr;
+        ~Event() { if (e) (void)hipEventDestroy(e); }
+    } t0, t1;
+    const bool timed = getenv("MMGPU_TRACE") && hipEventCreate(&t0.e) == hipSuccess && hipEventCreate(&t1.e) == hipSuccess;
+    auto enqueue = [&]() -> int {
+        HIP_TRY(b->m_res.alloc((size_t)m_bytes));
+        HIP_TRY(upload(b->m_off4, m_off4, s));
+        HIP_TRY(upload(b->m_len, b->m_h_len, s));
+        HIP_TRY(upload(d_src, m_src, s));
+        HIP_TRY(d_span_off.alloc((P + 1) * 4));
+        HIP_TRY(hipMemcpyAsync(d_span_off.p, masks->span_off, (P + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(d_spans.alloc(std::max<size_t>(n_spans, 1) * sizeof(mmgpu_sw_span)));
+        if (n_spans) HIP_TRY(hipMemcpyAsync(d_spans.p, masks->spans + s_first, (size_t)n_spans * sizeof(mmgpu_sw_span), hipMemcpyHostToDevice, s));
+        if (timed) HIP_TRY(hipEventRecord(t0.e, s));
+        HIP_TRY(hipMemsetAsync(b->m_res.p, par->alphabet, (size_t)m_bytes, s));
+        SwMaskGatherArgs A;
+        A.src_res = c->db.res;
+        A.src_off4 = c->db.off4;
+        A.src_len = c->db.len;
+        A.src_id = d_src.as<uint32_t>();
+        A.dst_res = b->m_res.as<uint8_t>();
+        A.dst_off4 = b->m_off4.as<uint32_t>();
+        A.span_off = d_span_off.as<uint32_t>();
+        A.spans = d_spans.as<mmgpu_sw_span>();
+        A.span_base = s_first;      // (span_off counts from the caller's first span; only the spans from there on were uploaded)
+        A.mask_letter = (uint32_t)masks->mask_letter;
+        A.n_pairs = (uint32_t)P;
+        HIP_TRY(launch_sw_mask_gather(A, s));
+        if (timed) HIP_TRY(hipEventRecord(t1.e, s));
+        return MMGPU_OK;
+    };
+    const int e = enqueue();
+    // the span buffers of this step die with it; after a failure (out of memory for the copies) the batch and its buffers go as well
+    const hipError_t drained = hipStreamSynchronize(s);
+    if (e) return e;
+    HIP_TRY(drained);
+    float ms = 0;
+    if (timed && hipEventElapsedTime(&ms, t0.e, t1.e) == hipSuccess)
+        fprintf(stderr, "[mmgpu sw_prepare] masked copies: %zu pairs, %u spans, arena %llu bytes, memset + sw_mask_gather_kernel %.3f ms\n", P, n_spans,
+                (unsigned long long)m_bytes, ms);
+    tv = sw_targets(c, b);
+    return MMGPU_OK;
+}
+
 // residues, composition bias / profile rows, bias and start-score threshold of query i; *qminp = its lowest substitution score
 int SwPrepare::copy_query(uint32_t i, int *qminp) {
     const mmgpu_sw_query &Q = qs[i];
@@ -746,6 +876,8 @@ void SwPrepare::add_rev_jobs(uint32_t query, uint32_t first, uint32_t n, uint32_
 // a list on the device: fixed jobs over the query's slots, the kernel clips them to the list length (SwLaunch::q_hit_count); order
 // and statistics come from sw_from_pf_kernel.  Hits per job: as many rounds as fit JOB_CELLS at the length the hits will probably
 // have (prefilter hits are mostly about as long as the query; the database mean otherwise)
+// (c->mean_len is the resident database's mean on purpose: only device lists come here, and a masked batch has none - its lists are
+// the caller's, cut over the copies' own lengths in cut_list_jobs_of)
 void SwPrepare::add_slot_jobs(uint32_t i, uint32_t shape, uint32_t round, bool multi) {
     const mmgpu_sw_query &Q = qs[i];
     const uint64_t est_cells = (uint64_t)Q.qlen * ((Q.qlen + c->mean_len) / 2 + 1) * round;
@@ -763,7 +895,7 @@ void SwPrepare::add_slot_jobs(uint32_t i, uint32_t shape, uint32_t round, bool m
     }
     if (multi && mode >= MMGPU_SW_START)
         add_rev_jobs(i, hit_cursor, pf_stride, shape, (uint64_t)Q.qlen * ((Q.qlen + c->mean_len) / 2 + 1));
-    max_tlen = c->db.max_len;
+    max_tlen = tv.max_len;
 }
 
 int SwPrepare::copy_queries() {
@@ -810,18 +942,18 @@ void SwPrepare::cut_list_jobs_of(size_t from, size_t to) {
             ord.resize(Q.n_targets);
             std::iota(ord.begin(), ord.end(), 0u);
             for (uint32_t k = 0; k < Q.n_targets; k++)
-                if (Q.target_ids[k] >= c->db.n) { P.bad = true; break; }
+                if (Q.target_ids[k] >= tv.n) { P.bad = true; break; }
             if (P.bad) continue;
             std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t bb) {
-                return c->h_len[Q.target_ids[a]] > c->h_len[Q.target_ids[bb]];
+                return tv.h_len[Q.target_ids[a]] > tv.h_len[Q.target_ids[bb]];
             });
         }
         for (uint32_t k = 0; k < Q.n_targets; k++) {
             const uint32_t t = Q.target_ids[ord[k]];
             hit_target[D.hit_cursor + k] = t;
             hit_out[D.hit_cursor + k] = D.out_cursor + ord[k];
-            P.sum_cells += (uint64_t)Q.qlen * c->h_len[t];
-            P.max_tlen = std::max(P.max_tlen, c->h_len[t]);
+            P.sum_cells += (uint64_t)Q.qlen * tv.h_len[t];
+            P.max_tlen = std::max(P.max_tlen, tv.h_len[t]);
         }
         // Jobs: consecutive hits of the (length-sorted) list, cut at multiples of one workgroup round (32 targets)
         // once a job holds JOB_CELLS forward cells, at the latest after JOB_HITS hits - a 5000-residue query against
@@ -831,7 +963,7 @@ void SwPrepare::cut_list_jobs_of(size_t from, size_t to) {
             uint32_t e = k;
             while (e < Q.n_targets && e - k < JOB_HITS) {
                 const uint32_t stop = std::min<uint32_t>(e + D.round, Q.n_targets);
-                for (; e < stop; e++) jc += (uint64_t)Q.qlen * c->h_len[hit_target[D.hit_cursor + e]];
+                for (; e < stop; e++) jc += (uint64_t)Q.qlen * tv.h_len[hit_target[D.hit_cursor + e]];
                 // cut at 8, 16 (long queries) or whole workgroup rounds: no wave idles while another runs a second round
                 const uint32_t held = e - k;
                 if (jc >= JOB_CELLS && (held <= 16 || held % JOB_ROUND == 0)) break;
@@ -845,7 +977,7 @@ void SwPrepare::cut_list_jobs_of(size_t from, size_t to) {
             P.cells.push_back(jc);
             k = e;
         }
-        if (Q.n_targets) P.rev_mid_len = c->h_len[hit_target[D.hit_cursor + Q.n_targets / 2]];
+        if (Q.n_targets) P.rev_mid_len = tv.h_len[hit_target[D.hit_cursor + Q.n_targets / 2]];
         if (mode >= MMGPU_SW_START)
             for (uint32_t k = 0; k < Q.n_targets; k++) b->h_out_target[D.out_cursor + k] = Q.target_ids[k];
     }
@@ -999,7 +1131,7 @@ int SwPrepare::order_device_lists() {
     F.hit_count = pf->counts;
     F.stride = pf_stride;
     F.q_off = b->d_qoff.as<uint32_t>();
-    F.t_len = c->db.len;
+    F.t_len = tv.len;
     F.hit_target = b->d_hit_target.as<uint32_t>();
     F.hit_out = b->d_hit_out.as<uint32_t>();
     F.cells = b->d_stats.as<unsigned long long>();
@@ -1027,15 +1159,18 @@ int SwPrepare::order_device_lists() {
 }  // namespace
 
 static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, int mode,
-                           const DeviceLists *pf, mmgpu_sw_batch_t **out) {
+                           const DeviceLists *pf, const mmgpu_sw_masks *masks, mmgpu_sw_batch_t **out) {
     if (!c || !par || !out || (!qs && nq)) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: NULL argument");
-    SwPrepare S{c, par, qs, nq, mode, pf};
+    SwPrepare S{c, par, qs, nq, mode, pf, masks};
     if (int e = S.check_params()) return e;
+    S.tv = sw_targets(c, nullptr);
     HIP_TRY(hipSetDevice(c->device));
     std::unique_ptr<mmgpu_sw_batch_t, SwBatchFree> b(new mmgpu_sw_batch_t(), SwBatchFree{c});
     S.b = b.get();
     S.new_batch();
     if (int e = S.size_buffers()) return e;
+    if (masks)
+        if (int e = S.plan_masked()) return e;
     if (int e = S.copy_queries()) return e;
     S.lap("queries copied, buffers sized");
     if (!S.deferred.empty()) {
@@ -1046,6 +1181,10 @@ static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu
     S.lap("jobs joined");
     if (int e = S.enqueue_uploads()) return e;
     S.lap("uploads enqueued, jobs ordered");
+    if (masks) {
+        if (int e = S.gather_masked()) return e;
+        S.lap("masked copies of the targets gathered");
+    }
     if (int e = pf ? S.order_device_lists() : S.finish_host_lists()) return e;
     S.lap("scratch + stream drained");
     *out = b.release();
@@ -1054,7 +1193,32 @@ static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu
 
 extern "C" int mmgpu_sw_prepare(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq,
                                 int mode, mmgpu_sw_batch_t **out) {
-    return sw_prepare_impl(c, par, qs, nq, mode, nullptr, out);
+    return sw_prepare_impl(c, par, qs, nq, mode, nullptr, nullptr, out);
+}
+
+extern "C" int mmgpu_sw_prepare_masked(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, int mode,
+                                       const mmgpu_sw_masks *masks, mmgpu_sw_batch_t **out) {
+    if (out) *out = nullptr;
+    if (!masks) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_masked: NULL masks");
+    return sw_prepare_impl(c, par, qs, nq, mode, nullptr, masks, out);
+}
+
+// test hook: pair p's copy as the kernels read it, its pad letters included
+extern "C" int mmgpu_sw_debug_masked_target(mmgpu_ctx *c, mmgpu_sw_batch_t *b, uint32_t pair, uint8_t *out, size_t cap, uint32_t *len) {
+    if (!c || !b) return fail(MMGPU_ERR_ARG, "mmgpu_sw_debug_masked_target: NULL argument");
+    if (!b->masked) return fail(MMGPU_ERR_STATE, "mmgpu_sw_debug_masked_target: not a batch of mmgpu_sw_prepare_masked");
+    if (pair >= b->m_h_len.size()) return fail(MMGPU_ERR_ARG, "mmgpu_sw_debug_masked_target: pair index out of range");
+    const uint32_t l = b->m_h_len[pair];
+    const size_t bytes = ((size_t)l + 3) & ~(size_t)3;
+    if (len) *len = l;
+    if (!out && cap == 0) return MMGPU_OK;      // the size query
+    if (cap < bytes || (!out && bytes)) return fail(MMGPU_ERR_ARG, "mmgpu_sw_debug_masked_target: buffer too small (needs (len + 3) & ~3 bytes)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t off4 = 0;
+    HIP_TRY(hipMemcpy(&off4, b->m_off4.as<uint32_t>() + pair, 4, hipMemcpyDeviceToHost));
+    if (bytes) HIP_TRY(hipMemcpy(out, b->m_res.as<uint8_t>() + (size_t)off4 * 4, bytes, hipMemcpyDeviceToHost));
+    return MMGPU_OK;
 }
 
 extern "C" int mmgpu_sw_prepare_from_pf(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq,
@@ -1065,7 +1229,7 @@ extern "C" int mmgpu_sw_prepare_from_pf(mmgpu_ctx *c, const mmgpu_sw_params *par
     if (!pf_batch_device_lists(pf, &L.hits, &L.counts, &L.stride, &pf_nq))
         return fail(MMGPU_ERR_STATE, "mmgpu_sw_prepare_from_pf: the prefilter batch was never run, or is an exchange batch of a sharded run");
     if (pf_nq != nq) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare_from_pf: query count differs from the prefilter batch");
-    return sw_prepare_impl(c, par, qs, nq, mode, &L, out);
+    return sw_prepare_impl(c, par, qs, nq, mode, &L, nullptr, out);
 }
 
 extern "C" int mmgpu_sw_prepare_from_lists(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, int mode,
@@ -1076,7 +1240,7 @@ extern "C" int mmgpu_sw_prepare_from_lists(mmgpu_ctx *c, const mmgpu_sw_params *
     L.hits = (const mmgpu_pf_hit *)d_hits;
     L.counts = (const uint32_t *)d_counts;
     L.stride = stride;
-    return sw_prepare_impl(c, par, qs, nq, mode, &L, out);
+    return sw_prepare_impl(c, par, qs, nq, mode, &L, nullptr, out);
 }
 
 // ---- multi-GPU: every rank aligns the pairs of the merged lists whose target it holds; the records are gathered over the
@@ -1112,7 +1276,7 @@ extern "C" int mmgpu_sw_prepare_owned(mmgpu_ctx *c, const mmgpu_sw_params *par, 
     L.hits = lh.as<mmgpu_pf_hit>();
     L.counts = lc.as<uint32_t>();
     L.stride = stride;
-    if (int e = sw_prepare_impl(c, par, qs, nq, mode, &L, out)) return e;
+    if (int e = sw_prepare_impl(c, par, qs, nq, mode, &L, nullptr, out)) return e;
     mmgpu_sw_batch_t *b = *out;
     b->owned = true;
     b->o_stride = stride;
@@ -1249,6 +1413,7 @@ static int sw_launch_groups(mmgpu_ctx *c, mmgpu_sw_batch_t *b, bool rev_only, co
     }
     HIP_TRY(hipEventRecord(c->fork, c->stream));
     for (int g = 0; g < SW_GROUPS; g++) HIP_TRY(hipStreamWaitEvent(c->side[g], c->fork, 0));
+    const TargetView T = sw_targets(c, b);
     for (int g = SW_GROUPS - 1; g >= 0; g--) {
         hipStream_t st = c->side[g];
         {
@@ -1262,9 +1427,9 @@ static int sw_launch_groups(mmgpu_ctx *c, mmgpu_sw_batch_t *b, bool rev_only, co
             L.q_minstart = b->d_qminstart.as<int32_t>();
             L.q_prof = b->any_profile ? b->d_qprof.as<int8_t>() : nullptr;
             L.q_prof_off = b->any_profile ? b->d_qprof_off.as<uint32_t>() : nullptr;
-            L.t_res = c->db.res;
-            L.t_off4 = c->db.off4;
-            L.t_len = c->db.len;
+            L.t_res = T.res;
+            L.t_off4 = T.off4;
+            L.t_len = T.len;
             L.hit_target = b->d_hit_target.as<uint32_t>();
             L.hit_out = b->d_hit_out.as<uint32_t>();
             L.out = b->d_out.as<mmgpu_sw_hit>();
@@ -1651,8 +1816,9 @@ int BlockRun::buffers_and_uploads() {
     L.q_res = b->d_qres.as<uint8_t>();
     L.q_cb = b->d_qcb.as<int8_t>();
     L.q_off = b->d_qoff.as<uint32_t>();
-    L.t_res = c->db.res;
-    L.t_off4 = c->db.off4;
+    const TargetView T = sw_targets(c, b);
+    L.t_res = T.res;
+    L.t_off4 = T.off4;
     L.scores = d_scores.as<int8_t>();
     L.q_prof = b->any_profile ? b->d_qprof.as<int8_t>() : nullptr;
     L.q_prof_off = b->any_profile ? b->d_qprof_off.as<uint32_t>() : nullptr;
@@ -2022,8 +2188,9 @@ extern "C" int mmgpu_sw_traceback(mmgpu_ctx *c, mmgpu_sw_batch_t *b, const uint3
     L.q_off = b->d_qoff.as<uint32_t>();
     L.q_prof = b->any_profile ? b->d_qprof.as<int8_t>() : nullptr;
     L.q_prof_off = b->any_profile ? b->d_qprof_off.as<uint32_t>() : nullptr;
-    L.t_res = c->db.res;
-    L.t_off4 = c->db.off4;
+    const TargetView T = sw_targets(c, b);
+    L.t_res = T.res;
+    L.t_off4 = T.off4;
     L.mat = b->d_mat.as<int8_t>();
     L.alphabet = b->alphabet;
     L.gap_open = b->gap_open;

@@ -37,6 +37,32 @@ struct DeviceDb {
     size_t res_bytes = 0;        // allocated size of `res`
 };
 
+// The targets an alignment batch reads, in DeviceDb's layout: the context's resident database, or the private masked copies of a
+// batch of mmgpu_sw_prepare_masked (one per pair, id = pair ordinal).  The kernels take res / off4 / len as launch arguments.
+struct TargetView {
+    const uint8_t *res = nullptr;
+    const uint32_t *off4 = nullptr;
+    const uint32_t *len = nullptr;
+    uint32_t n = 0;
+    uint32_t max_len = 0;
+    const uint32_t *h_len = nullptr;   // [n] host copy of the lengths (scheduling)
+};
+
+// sw_mask_kernel.hip: the masked copies of a batch's targets, gathered out of the resident database
+struct SwMaskGatherArgs {
+    const uint8_t *src_res;            // the resident targets
+    const uint32_t *src_off4, *src_len;
+    const uint32_t *src_id;            // [n_pairs] resident id of every pair's target
+    uint8_t *dst_res;                  // the batch's arena (filled with the pad letter before the launch)
+    const uint32_t *dst_off4;          // [n_pairs] start of pair p's copy in units of 4 bytes
+    const uint32_t *span_off;          // [n_pairs + 1]
+    const mmgpu_sw_span *spans;        // residues [t_from, t_to) of the copy read as mask_letter; t_to <= the target's length
+    uint32_t span_base;                // span_off[0]: spans[k - span_base] is span k of span_off's numbering
+    uint32_t mask_letter;
+    uint32_t n_pairs;
+};
+hipError_t launch_sw_mask_gather(const SwMaskGatherArgs &A, hipStream_t stream);
+
 // One workgroup's share of a batch: hits [hit_begin, hit_end) of one query (already sorted by target length).
 struct SwJob {
     uint32_t query;

@@ -168,6 +168,15 @@ int mmgpu_sw_block_growth(mmgpu_ctx *, mmgpu_sw_batch_t *, const uint32_t *, uin
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_block_growth: a test aid, not served through mmgpu_server");
 }
 
+int mmgpu_sw_prepare_masked(mmgpu_ctx *, const mmgpu_sw_params *, const mmgpu_sw_query *, uint32_t, int, const mmgpu_sw_masks *, mmgpu_sw_batch_t **batch) {
+    if (batch) *batch = nullptr;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare_masked: not served through mmgpu_server (the binary runs --alt-ali on the host)");
+}
+
+int mmgpu_sw_debug_masked_target(mmgpu_ctx *, mmgpu_sw_batch_t *, uint32_t, uint8_t *, size_t, uint32_t *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_debug_masked_target: a test aid, not served through mmgpu_server");
+}
+
 int mmgpu_sw_block_tiers(const mmgpu_sw_batch_t *, uint32_t *first_tier, uint32_t *second_tier) {
     if (first_tier) *first_tier = 0;
     if (second_tier) *second_tier = 0;
