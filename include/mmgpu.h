@@ -697,6 +697,59 @@ int mmgpu_pf_last_cells(mmgpu_ctx *ctx, mmgpu_pf_batch_t *batch, uint64_t *cells
 int mmgpu_pf_debug_fetch(mmgpu_ctx *ctx, mmgpu_pf_batch_t *batch, int what, void *dst, size_t cap, size_t *bytes);
 void mmgpu_pf_free(mmgpu_ctx *ctx, mmgpu_pf_batch_t *batch);
 
+/* ---- exhaustive ungapped scan (behind runFilterOnCpu, src/prefiltering/ungappedprefilter.cpp:346-482) ---------------------------
+ * `mmseqs ungappedprefilter` (--prefilter-mode 1): no k-mer index, no sensitivity - every query against every resident target,
+ * scored with the best ungapped diagonal as SmithWaterman::ungapped_alignment computes it on the byte profile of ssw_init
+ * (StripedSmithWaterman.cpp:1817-1876, :1364-1440):
+ *     p(i, x) = mat[x * alphabet + q[i]] + comp_bias[i]
+ *     B       = |min(mat)| + |min(0, min_i comp_bias[i])|           (profile->bias; the minimum over the whole table)
+ *     S(i, j) = max(0, min(255 - B, S(i-1, j-1) + p(i, t[j]))),     score = max S, 0 for an empty target
+ * A query's list holds the targets inside its length window whose score is > min_score, and the query's own target whatever it
+ * scores, in the order of hit_t::compareHitsByScoreAndId (score descending, id ascending), cut at max_hits; diagonal is 0.
+ * SEQUENCE queries over the resident PROTEIN database only: profile queries and nucleotide databases are not served (the
+ * structs have no field for the former; an alphabet above 32 is MMGPU_ERR_UNSUPPORTED).
+ * MMGPU_ERR_ARG: a letter outside the alphabet, 255 - B <= 0, max(p) + B > 255 (the reference's byte profile wraps there), an
+ * empty query.  MMGPU_ERR_STATE: no targets loaded.  MMGPU_ERR_UNSUPPORTED: max_hits above MMGPU_PF_MAX_FUSED_HITS; more than
+ * 4 GiB of scores (n_queries x resident targets bytes: send smaller batches); a context that holds a shard (mmgpu_pf_set_shard). */
+typedef struct {
+    const int8_t *mat;   /* alphabet*alphabet, row-major: tinySubMat (ungappedprefilter.cpp:541-548) */
+    int alphabet;        /* that of the resident targets */
+    int32_t min_score;   /* par.minDiagScoreThr (--min-ungapped-score): a target is listed when score > min_score; -1 lists score 0 too */
+    uint32_t max_hits;   /* par.maxResListLen (--max-seqs), >= 1 */
+} mmgpu_scan_params;
+typedef struct {
+    const uint8_t *q;        /* Sequence::numSequence */
+    uint32_t qlen;
+    const int8_t *comp_bias; /* rounded as ssw_init rounds it (mmgpu_host_round_comp_bias); NULL = none (--comp-bias-corr 0) */
+    uint32_t identity_id;    /* the query's own target (same-database runs, ungappedprefilter.cpp:396), UINT32_MAX = none: as
+                                mmgpu_pf_query::identity_id */
+    uint32_t min_tlen, max_tlen; /* inclusive window of target lengths Util::canBeCovered admits for this query (Util.cpp:542-559:
+                                    monotone in the target length); 0 and UINT32_MAX = every length */
+} mmgpu_scan_query;
+typedef struct mmgpu_scan_batch_t mmgpu_scan_batch_t;
+/* validates the inputs, computes B per query, cuts the jobs, H2D copies; *batch is NULL on failure */
+int mmgpu_scan_prepare(mmgpu_ctx *ctx, const mmgpu_scan_params *params, const mmgpu_scan_query *queries, uint32_t n_queries,
+                       mmgpu_scan_batch_t **batch);
+/* kernel launches only (scan, then selection), asynchronous on the context's stream */
+int mmgpu_scan_run(mmgpu_ctx *ctx, mmgpu_scan_batch_t *batch);
+/* hits [n_queries][hit_stride], hit_stride >= min(max_hits, resident targets); counts [n_queries].  Synchronises. */
+int mmgpu_scan_fetch(mmgpu_ctx *ctx, mmgpu_scan_batch_t *batch, mmgpu_pf_hit *hits, uint32_t hit_stride, uint32_t *counts);
+/* the same lists into caller-owned DEVICE memory, d_hits [n_queries][hit_stride] mmgpu_pf_hit, d_counts [n_queries] uint32: what
+ * mmgpu_sw_prepare_from_lists reads.  Asynchronous on the context's stream. */
+int mmgpu_scan_fetch_device(mmgpu_ctx *ctx, mmgpu_scan_batch_t *batch, void *d_hits, uint32_t hit_stride, void *d_counts);
+/* milliseconds in the kernels of the batch's last run (HIP events on the context's stream; synchronises) */
+int mmgpu_scan_last_kernel_ms(mmgpu_ctx *ctx, mmgpu_scan_batch_t *batch, float *ms);
+/* releases the batch (the context keeps its score scratch, grown to the largest batch, until mmgpu_destroy) */
+void mmgpu_scan_free(mmgpu_ctx *ctx, mmgpu_scan_batch_t *batch);
+/* one-shot form: prepare, run, fetch, free */
+int mmgpu_scan_batch(mmgpu_ctx *ctx, const mmgpu_scan_params *params, const mmgpu_scan_query *queries, uint32_t n_queries,
+                     mmgpu_pf_hit *hits, uint32_t hit_stride, uint32_t *counts);
+/* test aid, like mmgpu_sw_debug_masked_target: the raw score min(255 - B, max S) of every resident target for one query of a batch
+ * that has been run, one uint8 per target in id order, before threshold, identity rule or selection apply (targets outside the
+ * query's window are not scored and read 0).  cap >= resident targets.  MMGPU_ERR_STATE when the batch has not been run or another
+ * scan batch has run on the context since (the scores live in the context's scratch).  Synchronises. */
+int mmgpu_scan_debug_scores(mmgpu_ctx *ctx, mmgpu_scan_batch_t *batch, uint32_t query, uint8_t *out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

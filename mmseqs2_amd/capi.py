@@ -88,6 +88,8 @@ EXPORTED_SYMBOLS = [
     "mmgpu_pf_exchange_redo_unsplit",
     "mmgpu_db_save", "mmgpu_db_probe", "mmgpu_db_load",
     "mmgpu_sw_prepare_masked", "mmgpu_sw_debug_masked_target",
+    "mmgpu_scan_prepare", "mmgpu_scan_run", "mmgpu_scan_fetch", "mmgpu_scan_fetch_device", "mmgpu_scan_last_kernel_ms", "mmgpu_scan_free",
+    "mmgpu_scan_batch", "mmgpu_scan_debug_scores",
 ]
 
 
@@ -124,6 +126,15 @@ class PfParams(ctypes.Structure):
 class PfQuery(ctypes.Structure):
     _fields_ = [("q", c_p), ("qlen", ctypes.c_uint32), ("comp_bias", c_p), ("identity_id", ctypes.c_uint32),
                 ("profile_score", c_p), ("profile_index", c_p), ("profile_row", ctypes.c_uint32), ("profile", c_p)]
+
+
+class ScanParams(ctypes.Structure):      # mmgpu_scan_params
+    _fields_ = [("mat", c_p), ("alphabet", ctypes.c_int), ("min_score", ctypes.c_int32), ("max_hits", ctypes.c_uint32)]
+
+
+class ScanQuery(ctypes.Structure):      # mmgpu_scan_query
+    _fields_ = [("q", c_p), ("qlen", ctypes.c_uint32), ("comp_bias", c_p), ("identity_id", ctypes.c_uint32),
+                ("min_tlen", ctypes.c_uint32), ("max_tlen", ctypes.c_uint32)]
 
 
 class PfShard(ctypes.Structure):
@@ -235,6 +246,15 @@ def load_library():
     L.mmgpu_multi_pf_free.restype = None
     L.mmgpu_multi_sw_from_pf.argtypes = [c_p, ctypes.POINTER(SwParams), c_p, ctypes.c_uint32, ctypes.c_int, c_p, c_p,
                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_float)]
+    L.mmgpu_scan_prepare.argtypes = [c_p, ctypes.POINTER(ScanParams), c_p, ctypes.c_uint32, ctypes.POINTER(c_p)]
+    L.mmgpu_scan_run.argtypes = [c_p, c_p]
+    L.mmgpu_scan_fetch.argtypes = [c_p, c_p, c_p, ctypes.c_uint32, c_p]
+    L.mmgpu_scan_fetch_device.argtypes = [c_p, c_p, c_p, ctypes.c_uint32, c_p]
+    L.mmgpu_scan_last_kernel_ms.argtypes = [c_p, c_p, ctypes.POINTER(ctypes.c_float)]
+    L.mmgpu_scan_free.argtypes = [c_p, c_p]
+    L.mmgpu_scan_free.restype = None
+    L.mmgpu_scan_batch.argtypes = [c_p, ctypes.POINTER(ScanParams), c_p, ctypes.c_uint32, c_p, ctypes.c_uint32, c_p]
+    L.mmgpu_scan_debug_scores.argtypes = [c_p, c_p, ctypes.c_uint32, c_p, ctypes.c_size_t]
     return L
 
 
@@ -282,6 +302,49 @@ PF_QUERY_DTYPE = np.dtype([("q", np.uint64), ("qlen", np.uint32), ("_p0", np.uin
                            ("_p1", np.uint32), ("profile_score", np.uint64), ("profile_index", np.uint64), ("profile_row", np.uint32),
                            ("_p2", np.uint32), ("profile", np.uint64)])
 assert SW_QUERY_DTYPE.itemsize == ctypes.sizeof(SwQuery) and PF_QUERY_DTYPE.itemsize == ctypes.sizeof(PfQuery)
+SCAN_QUERY_DTYPE = np.dtype([("q", np.uint64), ("qlen", np.uint32), ("_p0", np.uint32), ("comp_bias", np.uint64), ("identity_id", np.uint32),
+                             ("min_tlen", np.uint32), ("max_tlen", np.uint32), ("_p1", np.uint32)])
+assert SCAN_QUERY_DTYPE.itemsize == ctypes.sizeof(ScanQuery)
+
+
+def _can_be_covered(cov_thr, cov_mode, qlen, tlen):
+    """Util::canBeCovered (Util.cpp:542-559) for one query length over an array of target lengths, in the reference's float32"""
+    q = np.float32(qlen)
+    t = np.asarray(tlen).astype(np.float32)
+    thr = np.float32(cov_thr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if cov_mode == 0:      # COV_MODE_BIDIRECTIONAL
+            return ((q / t) >= thr) & ((t / q) >= thr)
+        if cov_mode == 1:      # COV_MODE_TARGET
+            return (q / t) >= thr
+        if cov_mode == 2:      # COV_MODE_QUERY
+            return (t / q) >= thr
+        if cov_mode == 3:      # COV_MODE_LENGTH_QUERY
+            return ((t / q) >= thr) & ((t / q) <= np.float32(1.0))
+        if cov_mode == 4:      # COV_MODE_LENGTH_TARGET
+            return ((q / t) >= thr) & ((q / t) <= np.float32(1.0))
+        if cov_mode == 5:      # COV_MODE_LENGTH_SHORTER
+            return (np.minimum(q, t) / np.maximum(q, t)) >= thr
+    return np.ones(t.shape, bool)      # (the reference's default branch)
+
+
+def coverage_window(cov_thr, cov_mode, qlen, target_lengths):
+    """(min_tlen, max_tlen) of mmgpu_scan_query for one query: the reference's predicate evaluated over the distinct target lengths
+    present.  The window is open towards a side on which every length present is admitted (0 below, UINT32_MAX above); cov_thr = 0
+    gives the full window (modes 3 and 4 keep their "not longer than" half of the predicate).  No admitted length: (UINT32_MAX, UINT32_MAX), which no target meets.  Raises if the admitted lengths are
+    not one interval of the lengths present."""
+    if cov_thr == 0 and int(cov_mode) not in (3, 4):
+        return 0, 0xFFFFFFFF
+    lens = np.unique(np.asarray(target_lengths, np.int64))
+    ok = _can_be_covered(cov_thr, int(cov_mode), int(qlen), lens)
+    idx = np.flatnonzero(ok)
+    if len(idx) == 0:
+        return 0xFFFFFFFF, 0xFFFFFFFF
+    if idx[-1] - idx[0] + 1 != len(idx):
+        raise ValueError("coverage_window: the admitted target lengths are not one interval")
+    lo = 0 if idx[0] == 0 else int(lens[idx[0]])
+    hi = 0xFFFFFFFF if idx[-1] == len(lens) - 1 else int(lens[idx[-1]])
+    return lo, hi
 
 
 def host_score_matrix(submat16, span, lib=None):
@@ -418,6 +481,49 @@ class PfBatch:
     def free(self):
         if self.handle is not None:
             self.gpu.L.mmgpu_pf_free(self.gpu.ctx, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ScanBatch:
+    """A prepared exhaustive ungapped scan (mmgpu_scan_*): queries resident in HBM."""
+
+    def __init__(self, gpu, handle, keep, nq, stride):
+        self.gpu, self.handle, self._keep, self.nq, self.stride = gpu, handle, keep, nq, stride
+
+    def run(self):
+        self.gpu._check(self.gpu.L.mmgpu_scan_run(self.gpu.ctx, self.handle))
+
+    def fetch(self):
+        """-> (hits[nq][stride] PF_HIT_DTYPE, counts[nq])"""
+        hits = np.zeros((self.nq, max(self.stride, 1)), PF_HIT_DTYPE)
+        counts = np.zeros(self.nq, np.uint32)
+        self.gpu._check(self.gpu.L.mmgpu_scan_fetch(self.gpu.ctx, self.handle, _ptr(hits), max(self.stride, 1), _ptr(counts)))
+        return hits, counts
+
+    def fetch_device(self, d_hits_ptr, stride, d_counts_ptr):
+        """D2D copy of the lists into caller-owned device memory (raw pointers): what sw_prepare_from_lists reads"""
+        self.gpu._check(self.gpu.L.mmgpu_scan_fetch_device(self.gpu.ctx, self.handle, c_p(d_hits_ptr), stride, c_p(d_counts_ptr)))
+
+    def debug_scores(self, query):
+        """mmgpu_scan_debug_scores (test aid): the raw score byte of every resident target for one query of the last run"""
+        out = np.zeros(max(self.gpu.n_targets, 1), np.uint8)
+        self.gpu._check(self.gpu.L.mmgpu_scan_debug_scores(self.gpu.ctx, self.handle, int(query), _ptr(out), out.size))
+        return out[:self.gpu.n_targets]
+
+    def kernel_ms(self):
+        ms = ctypes.c_float()
+        self.gpu._check(self.gpu.L.mmgpu_scan_last_kernel_ms(self.gpu.ctx, self.handle, ctypes.byref(ms)))
+        return ms.value
+
+    def free(self):
+        if self.handle is not None:
+            self.gpu.L.mmgpu_scan_free(self.gpu.ctx, self.handle)
             self.handle = None
 
     def __del__(self):
@@ -893,6 +999,40 @@ class MMGpu:
         b.free()
         return out
 
+    def _scan_marshal(self, mat, queries, min_score, max_hits):
+        """queries: list of dicts {q: uint8[], comp_bias: int8[]|None (rounded), identity_id: int|None, window: (min_tlen, max_tlen)|None}"""
+        mat = np.ascontiguousarray(mat, np.int8)
+        par = ScanParams(_ptr(mat), mat.shape[0], int(min_score), int(max_hits))
+        arr = (ScanQuery * max(len(queries), 1))()
+        keep = [mat]
+        for i, qd in enumerate(queries):
+            q = np.ascontiguousarray(qd["q"], np.uint8)
+            cb = None if qd.get("comp_bias") is None else np.ascontiguousarray(qd["comp_bias"], np.int8)
+            if cb is not None and len(cb) != len(q):
+                raise ValueError("comp_bias must have the query's length")
+            ident = qd.get("identity_id")
+            lo, hi = qd.get("window") or (0, 0xFFFFFFFF)
+            keep += [q, cb]
+            arr[i] = ScanQuery(_ptr(q), len(q), _ptr(cb), 0xFFFFFFFF if ident is None else int(ident), int(lo), int(hi))
+        return par, arr, keep
+
+    def scan_prepare(self, mat, queries, min_score=15, max_hits=300):
+        """mmgpu_scan_prepare: the exhaustive ungapped scan (`ungappedprefilter`) of sequence queries over the resident targets"""
+        par, arr, keep = self._scan_marshal(mat, queries, min_score, max_hits)
+        h = c_p()
+        self._check(self.L.mmgpu_scan_prepare(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), ctypes.byref(h)))
+        return ScanBatch(self, h, keep, len(queries), min(int(max_hits), self.n_targets))
+
+    def scan_batch(self, mat, queries, min_score=15, max_hits=300):
+        """mmgpu_scan_batch: -> (hits[nq][stride], counts[nq])"""
+        par, arr, keep = self._scan_marshal(mat, queries, min_score, max_hits)
+        stride = max(min(int(max_hits), getattr(self, "n_targets", 0)), 1)
+        hits = np.zeros((max(len(queries), 1), stride), PF_HIT_DTYPE)
+        counts = np.zeros(max(len(queries), 1), np.uint32)
+        self._check(self.L.mmgpu_scan_batch(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), _ptr(hits), stride, _ptr(counts)))
+        del keep
+        return hits[:len(queries)], counts[:len(queries)]
+
     def pf_set_shard(self, n_shards, shard, global_db_size, global_ids, shard_of, local_id):
         """this context holds shard `shard` of a database of global_db_size targets (None-like: pf_clear_shard)"""
         g = np.ascontiguousarray(global_ids, np.uint32)
@@ -950,6 +1090,30 @@ class MMGpu:
         off = np.ascontiguousarray(id_offsets, np.uint32)
         self._check(self.L.mmgpu_pf_merge_splits(self.ctx, c_p(d_hits_ptr), c_p(d_counts_ptr), n_splits, nq, stride, _ptr(off),
                                                  c_p(d_out_hits_ptr), c_p(d_out_counts_ptr)))
+
+
+def exhaustive_search(gpu, scan_mat, sw_mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, mode=1):
+    """Exhaustive search on one device without a list leaving it: scan_prepare + run, fetch_device into a device buffer,
+    sw_prepare_from_lists over it, run, fetch.  queries: dicts with q, comp_bias (rounded int8 or None; the same bias serves both
+    stages, as ssw_init computes it once), identity_id, window, min_start_score.
+    -> (hits[nq][stride], counts[nq], records[nq][stride] SW_HIT_DTYPE: slot k of a row = hit k of the query's list)"""
+    import torch
+    scan = gpu.scan_prepare(scan_mat, queries, min_score, max_hits)
+    scan.run()
+    stride = max(scan.stride, 1)
+    d_hits = torch.zeros(len(queries) * stride * PF_HIT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_counts = torch.zeros(len(queries), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()      # (the buffers are zeroed on torch's stream, filled on the context's)
+    scan.fetch_device(d_hits.data_ptr(), stride, d_counts.data_ptr())
+    sw = gpu.sw_prepare_from_lists(sw_mat, gap_open, gap_extend, queries, d_hits.data_ptr(), d_counts.data_ptr(), stride, mode=mode)
+    sw.run()
+    rec = sw.fetch().reshape(len(queries), stride)
+    hits, counts = scan.fetch()
+    sw.free()
+    scan.free()
+    gpu.synchronize()
+    del d_hits, d_counts
+    return hits, counts, rec
 
 
 def alt_next_spans(spans, records, accepted):

@@ -240,6 +240,7 @@ extern "C" int mmgpu_warmup(mmgpu_ctx *c) {
     mmgpu::warm_block();
     mmgpu::warm_block4();
     mmgpu::warm_bt();
+    mmgpu::warm_scan();
     return MMGPU_OK;
 }
 

@@ -198,6 +198,61 @@ static_assert(sw_multi_resident(2, 28, 21, 65536) && sw_multi_resident(3, 24, 21
               !sw_multi_resident(4, 22, 21, 65536) && !sw_multi_resident(2, 8, 21, 0), "residency rule");
 
 // ---------------------------------------------------------------------------------------------------------
+// exhaustive ungapped scan (scan_kernel.hip): every query against every resident target of its length window
+constexpr int SCAN_CLASSES = 5;                       // rows per lane 8, 16, 24, 32 (one tile), and tiles of 32 for longer queries
+constexpr int SCAN_MULTI = SCAN_CLASSES - 1;
+constexpr int SCAN_MAX_R = 32;                        // rows per lane of the largest tile: 16 lanes x 32 = 512 query rows
+constexpr int SCAN_ROUND = 32;                        // targets a workgroup scores at once: 4 waves x 4 DPP rows x 2 halves
+constexpr int SCAN_JOB_TARGETS = 16 * SCAN_ROUND;     // targets per job of a one-tile query (a multi-tile job is one round)
+constexpr int SCAN_MAX_HITS = 4096;                   // == MMGPU_PF_MAX_FUSED_HITS: keys the selection kernel sorts in LDS
+__host__ __device__ constexpr int scan_class_rows(int cls) { return cls == 0 ? 8 : cls == 1 ? 16 : cls == 2 ? 24 : 32; }
+// columns a pair's scan covers: the longer target's length, rounded up to whole chunks of R columns (the rest reads the pad letter)
+__host__ __device__ constexpr uint32_t scan_cols(uint32_t len, int R) { return (len + (uint32_t)R - 1u) / (uint32_t)R * (uint32_t)R; }
+// dwords of one DPP row's boundary line (multi-tile): two buffers of scan_cols + 1 entries, rounded to whole 64-byte lines
+__host__ __device__ constexpr uint32_t scan_park_row_words(uint32_t longest) { return 2u * ((scan_cols(longest, SCAN_MAX_R) + 1u + 15u) & ~15u); }
+
+struct ScanJob {
+    uint32_t query;
+    uint32_t begin, end;      // positions in the length-sorted id list (longest first)
+    uint32_t pad;
+};
+
+struct ScanLaunch {
+    const ScanJob *jobs;
+    uint32_t n_jobs;
+    const uint8_t *q_res;     // concatenated numeric residues
+    const int8_t *q_cb;       // concatenated rounded composition bias (zeros when absent)
+    const uint32_t *q_off;    // [nq + 1]
+    const int32_t *q_cap;     // [nq] 255 - B
+    const uint8_t *t_res;
+    const uint32_t *t_off4, *t_len;
+    const uint32_t *order;    // [n_targets] ids by length, longest first
+    uint32_t n_targets;
+    const int8_t *mat;
+    int alphabet;
+    uint8_t *scores;          // [nq][n_targets]
+    // multi-tile launches: persistent workgroups, workgroup b owns the boundary lines park + park_off[b] (dwords) for jobs b, b + grid, ..
+    uint32_t *park;
+    const uint64_t *park_off;
+};
+hipError_t launch_scan(const ScanLaunch &L, int cls, uint32_t grid, hipStream_t stream);
+
+struct ScanSelectArgs {
+    const uint8_t *scores;    // [nq][n_targets]
+    const uint32_t *t_len;
+    uint32_t n_targets;
+    const uint32_t *q_ident;  // [nq] UINT32_MAX = none
+    const uint32_t *q_win;    // [nq][2] inclusive window of target lengths
+    int32_t min_score;
+    uint32_t max_hits;
+    mmgpu_pf_hit *hits;       // [nq][stride]
+    uint32_t stride;
+    uint32_t *counts;         // [nq]
+};
+hipError_t launch_scan_select(const ScanSelectArgs &A, uint32_t nq, hipStream_t stream);
+void warm_scan();
+
+// ---------------------------------------------------------------------------------------------------------
 // prefilter (pf_kernels.hip)
 constexpr int PF_T = 4096;             // arrival-ordered index entries per tile (2048: 22 % slower, more tiles)
 constexpr int PF_IDS_PER_BIN = 4096;   // targets per replay bin (one 16 KB LDS state table per wavefront)
@@ -936,6 +991,10 @@ struct mmgpu_ctx {
     void *pinned = nullptr;
     size_t pinned_cap = 0;
     std::atomic<bool> pinned_busy{false};
+    // exhaustive ungapped scan (scan_api.hip): the [query][target] score bytes and the multi-tile boundary lines, grown to the
+    // largest batch and kept; scan_serial names the batch whose scores the scratch holds (mmgpu_scan_debug_scores)
+    mmgpu::DevBuf scan_scores, scan_park;
+    uint64_t scan_serial = 0;
 };
 
 // device memory for a context's long-lived buffers (targets, masked view): when the runtime is out of memory the blocks the

@@ -1,0 +1,346 @@
+// Host side of the exhaustive ungapped scan (include/mmgpu.h, "exhaustive ungapped scan"): validation, the per-query bias,
+// the job lists, launches of scan_kernel.hip.  prepare and run are sequences of named steps over one record each, in the manner of
+// sw_prepare_impl (mmgpu_api.hip).
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mmgpu_internal.h"
+
+using namespace mmgpu;
+
+struct mmgpu_scan_batch_t {
+    uint32_t nq = 0, n_targets = 0, max_hits = 0, stride = 0;
+    int32_t min_score = 0;
+    int alphabet = 0;
+    const uint8_t *db_res = nullptr;      // the resident database the batch was prepared against (a reload invalidates the batch)
+    uint64_t serial = 0;                  // names this batch in mmgpu_ctx::scan_serial
+    bool ran = false;
+    DevBuf d_qres, d_qcb, d_qoff, d_qcap, d_qident, d_qwin, d_mat, d_order, d_jobs, d_park_off, d_hits, d_counts;
+    uint32_t class_begin[SCAN_CLASSES + 1] = {};   // jobs of class k: d_jobs[class_begin[k] .. class_begin[k + 1])
+    uint32_t multi_grid = 0;              // persistent workgroups of the multi-tile launch
+    uint64_t park_words = 0;              // dwords of boundary lines they need
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~mmgpu_scan_batch_t() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
+namespace {
+
+std::atomic<uint64_t> g_scan_serial{0};
+
+// what prepare builds on the host before anything is uploaded
+struct ScanPrepare {
+    mmgpu_ctx *c;
+    const mmgpu_scan_params *par;
+    const mmgpu_scan_query *qs;
+    uint32_t nq;
+    std::vector<uint8_t> qres;
+    std::vector<int8_t> qcb;
+    std::vector<uint32_t> qoff, qident, qwin, order, first_le;   // first_le[L]: position of the first target of length <= L in `order`
+    std::vector<int32_t> qcap;
+    std::vector<ScanJob> jobs;
+    std::vector<uint64_t> park_off;
+};
+
+int scan_check_call(const ScanPrepare &S) {
+    const mmgpu_ctx *c = S.c;
+    if (!S.par || !S.qs || S.nq == 0 || !S.par->mat) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: NULL argument or no queries");
+    if (!c->db.res || c->db.n == 0) return fail(MMGPU_ERR_STATE, "mmgpu_scan_prepare: no targets loaded");
+    if (c->shard.on) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: the context holds a shard of a multi-GPU run");
+    if (S.par->alphabet != c->db.alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: alphabet differs from the loaded targets");
+    if (S.par->alphabet > 32) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: sequence queries over a protein database only (alphabet <= 32)");
+    if (S.par->max_hits == 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: max_hits must be >= 1");
+    if (S.par->max_hits > MMGPU_PF_MAX_FUSED_HITS) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: max_hits above MMGPU_PF_MAX_FUSED_HITS");
+    if ((uint64_t)S.nq * c->db.n > (4ull << 30)) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: more than 4 GiB of scores (queries x resident targets): send smaller batches");
+    return MMGPU_OK;
+}
+
+// residues, bias, window and identity of every query; B and 255 - B as ssw_init derives them (StripedSmithWaterman.cpp:1397-1406)
+int scan_marshal_queries(ScanPrepare &S) {
+    const int alphabet = S.par->alphabet;
+    const int8_t *mat = S.par->mat;
+    int mat_min = 0;
+    for (int i = 0; i < alphabet * alphabet; i++) mat_min = std::min<int>(mat_min, mat[i]);
+    std::vector<int> col_max(alphabet, -128);      // best score a query letter can meet
+    for (int x = 0; x < alphabet; x++)
+        for (int a = 0; a < alphabet; a++) col_max[a] = std::max<int>(col_max[a], mat[x * alphabet + a]);
+    S.qoff.assign(1, 0);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < S.nq; i++) {
+        const mmgpu_scan_query &Q = S.qs[i];
+        if (!Q.q || Q.qlen == 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: empty query");
+        if (Q.min_tlen > Q.max_tlen) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: min_tlen above max_tlen");
+        total += Q.qlen;
+        if (total > 0x7FFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: more than 2 GiB of query residues in one batch");
+        int cb_min = 0, p_max = -32768;
+        for (uint32_t k = 0; k < Q.qlen; k++) {
+            if (Q.q[k] >= alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: query letter outside the alphabet");
+            const int cb = Q.comp_bias ? Q.comp_bias[k] : 0;
+            cb_min = std::min(cb_min, cb);
+            p_max = std::max(p_max, col_max[Q.q[k]] + cb);
+        }
+        const int B = std::abs(mat_min) + std::abs(cb_min);
+        if (255 - B <= 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: the bias leaves no score range (255 - B <= 0)");
+        if (p_max + B > 255) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: a profile score plus the bias exceeds 255 (the reference's byte profile wraps)");
+        S.qres.insert(S.qres.end(), Q.q, Q.q + Q.qlen);
+        if (Q.comp_bias) S.qcb.insert(S.qcb.end(), Q.comp_bias, Q.comp_bias + Q.qlen);
+        else S.qcb.insert(S.qcb.end(), Q.qlen, 0);
+        S.qoff.push_back((uint32_t)total);
+        S.qcap.push_back(255 - B);
+        S.qident.push_back(Q.identity_id);
+        S.qwin.push_back(Q.min_tlen);
+        S.qwin.push_back(Q.max_tlen);
+    }
+    return MMGPU_OK;
+}
+
+// the resident ids by length, longest first (counting sort; ids ascend inside a length), and where each length starts
+void scan_order_targets(ScanPrepare &S) {
+    const std::vector<uint32_t> &len = S.c->h_len;
+    const uint32_t n = (uint32_t)len.size();
+    std::vector<uint32_t> start(65536 + 1, 0);      // after the prefix sum: start[k] = targets longer than 65535 - k = where length 65535 - k begins
+    for (uint32_t i = 0; i < n; i++) start[65535 - len[i] + 1]++;
+    for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
+    S.first_le.resize(65536);
+    for (uint32_t L = 0; L < 65536; L++) S.first_le[L] = start[65535 - L];
+    S.order.resize(n);
+    for (uint32_t i = 0; i < n; i++) S.order[start[65535 - len[i]]++] = i;
+}
+
+// jobs by class; one-tile classes: SCAN_JOB_TARGETS consecutive list positions of one query, multi-tile: one round.  Inside a class
+// the jobs with the longest targets come first (they run longest; the multi-tile slots are sized by their first job).
+void scan_cut_jobs(ScanPrepare &S, mmgpu_scan_batch_t *b) {
+    const uint32_t n = (uint32_t)S.order.size();
+    std::vector<ScanJob> by_class[SCAN_CLASSES];
+    for (uint32_t q = 0; q < S.nq; q++) {
+        const uint32_t qlen = S.qoff[q + 1] - S.qoff[q];
+        int cls = SCAN_MULTI;
+        for (int k = 0; k < SCAN_MULTI; k++)
+            if (qlen <= 16u * (uint32_t)scan_class_rows(k)) { cls = k; break; }
+        const uint32_t lo = S.qwin[2 * q], hi = S.qwin[2 * q + 1];
+        const uint32_t begin = hi >= 65535u ? 0u : S.first_le[hi];
+        const uint32_t end = lo == 0 ? n : (lo > 65535u ? 0u : S.first_le[lo - 1]);
+        const uint32_t step = cls == SCAN_MULTI ? (uint32_t)SCAN_ROUND : (uint32_t)SCAN_JOB_TARGETS;
+        for (uint32_t p = begin; p < end; p += std::min(step, end - p)) by_class[cls].push_back(ScanJob{q, p, std::min(end, p + step), 0});
+    }
+    b->class_begin[0] = 0;
+    for (int k = 0; k < SCAN_CLASSES; k++) {
+        std::stable_sort(by_class[k].begin(), by_class[k].end(), [](const ScanJob &a, const ScanJob &z) { return a.begin < z.begin; });
+        S.jobs.insert(S.jobs.end(), by_class[k].begin(), by_class[k].end());
+        b->class_begin[k + 1] = (uint32_t)S.jobs.size();
+    }
+    // persistent workgroups of the multi-tile launch and their boundary lines: workgroup w runs jobs w, w + grid, ..; the first is its
+    // longest (positions ascend = lengths descend)
+    const uint32_t n_multi = b->class_begin[SCAN_MULTI + 1] - b->class_begin[SCAN_MULTI];
+    b->multi_grid = std::min<uint32_t>(n_multi, 2u * (uint32_t)std::max(S.c->compute_units, 1));
+    uint64_t words = 0;
+    for (uint32_t w = 0; w < b->multi_grid; w++) {
+        const ScanJob &j = S.jobs[b->class_begin[SCAN_MULTI] + w];
+        S.park_off.push_back(words);
+        words += (uint64_t)(SCAN_ROUND / 2) * scan_park_row_words(S.c->h_len[S.order[j.begin]]);
+    }
+    b->park_words = words;
+}
+
+int scan_upload(ScanPrepare &S, mmgpu_scan_batch_t *b) {
+    mmgpu_ctx *c = S.c;
+    hipStream_t s = c->stream;
+    for (DevBuf *d : {&b->d_qres, &b->d_qcb, &b->d_qoff, &b->d_qcap, &b->d_qident, &b->d_qwin, &b->d_mat, &b->d_order, &b->d_jobs,
+                      &b->d_park_off, &b->d_hits, &b->d_counts})
+        d->bind(c->cache);
+    std::vector<int8_t> mat(S.par->mat, S.par->mat + (size_t)S.par->alphabet * S.par->alphabet);
+    HIP_TRY(upload(b->d_qres, S.qres, s));
+    HIP_TRY(upload(b->d_qcb, S.qcb, s));
+    HIP_TRY(upload(b->d_qoff, S.qoff, s));
+    HIP_TRY(upload(b->d_qcap, S.qcap, s));
+    HIP_TRY(upload(b->d_qident, S.qident, s));
+    HIP_TRY(upload(b->d_qwin, S.qwin, s));
+    HIP_TRY(upload(b->d_mat, mat, s));
+    HIP_TRY(upload(b->d_order, S.order, s));
+    HIP_TRY(upload(b->d_jobs, S.jobs, s));
+    HIP_TRY(upload(b->d_park_off, S.park_off, s));
+    HIP_TRY(b->d_hits.alloc((size_t)b->nq * b->stride * sizeof(mmgpu_pf_hit)));
+    HIP_TRY(b->d_counts.alloc((size_t)b->nq * sizeof(uint32_t)));
+    HIP_TRY(hipStreamSynchronize(s));      // the host vectors go with this call
+    return MMGPU_OK;
+}
+
+int scan_prepare_impl(mmgpu_ctx *c, const mmgpu_scan_params *par, const mmgpu_scan_query *qs, uint32_t nq, mmgpu_scan_batch_t **out) {
+    ScanPrepare S{c, par, qs, nq};
+    int rc = scan_check_call(S);
+    if (rc != MMGPU_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = scan_marshal_queries(S);
+    if (rc != MMGPU_OK) return rc;
+    std::unique_ptr<mmgpu_scan_batch_t> b(new mmgpu_scan_batch_t());
+    b->nq = nq;
+    b->n_targets = c->db.n;
+    b->max_hits = par->max_hits;
+    b->stride = std::min(par->max_hits, c->db.n);
+    b->min_score = par->min_score;
+    b->alphabet = par->alphabet;
+    b->db_res = c->db.res;
+    b->serial = ++g_scan_serial;
+    scan_order_targets(S);
+    scan_cut_jobs(S, b.get());
+    rc = scan_upload(S, b.get());
+    if (rc != MMGPU_OK) return rc;
+    HIP_TRY(hipEventCreate(&b->ev0));
+    HIP_TRY(hipEventCreate(&b->ev1));
+    *out = b.release();
+    return MMGPU_OK;
+}
+
+// the context's scratch: score bytes of the largest batch so far, boundary lines of the multi-tile workgroups
+int scan_reserve_scratch(mmgpu_ctx *c, const mmgpu_scan_batch_t *b) {
+    const size_t score_bytes = (size_t)b->nq * b->n_targets;
+    if (score_bytes > c->scan_scores.bytes || b->park_words * 4 > c->scan_park.bytes) HIP_TRY(hipStreamSynchronize(c->stream));   // a grown buffer frees the old one
+    HIP_TRY(c->scan_scores.reserve(score_bytes));
+    HIP_TRY(c->scan_park.reserve((size_t)b->park_words * 4));
+    return MMGPU_OK;
+}
+
+int scan_launch_classes(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
+    ScanLaunch L;
+    L.q_res = b->d_qres.as<uint8_t>();
+    L.q_cb = b->d_qcb.as<int8_t>();
+    L.q_off = b->d_qoff.as<uint32_t>();
+    L.q_cap = b->d_qcap.as<int32_t>();
+    L.t_res = c->db.res;
+    L.t_off4 = c->db.off4;
+    L.t_len = c->db.len;
+    L.order = b->d_order.as<uint32_t>();
+    L.n_targets = b->n_targets;
+    L.mat = b->d_mat.as<int8_t>();
+    L.alphabet = b->alphabet;
+    L.scores = c->scan_scores.as<uint8_t>();
+    L.park = c->scan_park.as<uint32_t>();
+    L.park_off = b->d_park_off.as<uint64_t>();
+    // targets outside a query's window are not scored: their bytes read 0
+    HIP_TRY(hipMemsetAsync(L.scores, 0, (size_t)b->nq * b->n_targets, c->stream));
+    for (int k = 0; k < SCAN_CLASSES; k++) {
+        L.jobs = b->d_jobs.as<ScanJob>() + b->class_begin[k];
+        L.n_jobs = b->class_begin[k + 1] - b->class_begin[k];
+        HIP_TRY(launch_scan(L, k, k == SCAN_MULTI ? b->multi_grid : L.n_jobs, c->stream));
+    }
+    return MMGPU_OK;
+}
+
+int scan_launch_select(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
+    ScanSelectArgs A;
+    A.scores = c->scan_scores.as<uint8_t>();
+    A.t_len = c->db.len;
+    A.n_targets = b->n_targets;
+    A.q_ident = b->d_qident.as<uint32_t>();
+    A.q_win = b->d_qwin.as<uint32_t>();
+    A.min_score = b->min_score;
+    A.max_hits = b->max_hits;
+    A.hits = b->d_hits.as<mmgpu_pf_hit>();
+    A.stride = b->stride;
+    A.counts = b->d_counts.as<uint32_t>();
+    HIP_TRY(launch_scan_select(A, b->nq, c->stream));
+    return MMGPU_OK;
+}
+
+int scan_check_batch(const char *who, const mmgpu_ctx *c, const mmgpu_scan_batch_t *b, bool must_have_run) {
+    if (!c || !b) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
+    if (b->db_res != c->db.res || b->n_targets != c->db.n) return fail(MMGPU_ERR_STATE, std::string(who) + ": the targets were reloaded since the batch was prepared");
+    if (must_have_run && !b->ran) return fail(MMGPU_ERR_STATE, std::string(who) + ": the batch has not been run");
+    return MMGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int mmgpu_scan_prepare(mmgpu_ctx *c, const mmgpu_scan_params *par, const mmgpu_scan_query *qs, uint32_t nq,
+                                  mmgpu_scan_batch_t **out) {
+    if (out) *out = nullptr;
+    if (!c || !out) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: NULL argument");
+    return scan_prepare_impl(c, par, qs, nq, out);
+}
+
+extern "C" int mmgpu_scan_run(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
+    int rc = scan_check_batch("mmgpu_scan_run", c, b, false);
+    if (rc != MMGPU_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = scan_reserve_scratch(c, b);
+    if (rc != MMGPU_OK) return rc;
+    c->scan_serial = b->serial;
+    HIP_TRY(hipEventRecord(b->ev0, c->stream));
+    rc = scan_launch_classes(c, b);
+    if (rc != MMGPU_OK) return rc;
+    rc = scan_launch_select(c, b);
+    if (rc != MMGPU_OK) return rc;
+    HIP_TRY(hipEventRecord(b->ev1, c->stream));
+    b->ran = true;
+    return MMGPU_OK;
+}
+
+extern "C" int mmgpu_scan_fetch(mmgpu_ctx *c, mmgpu_scan_batch_t *b, mmgpu_pf_hit *hits, uint32_t hit_stride, uint32_t *counts) {
+    int rc = scan_check_batch("mmgpu_scan_fetch", c, b, true);
+    if (rc != MMGPU_OK) return rc;
+    if (!hits || !counts) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch: NULL argument");
+    if (hit_stride < b->stride) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch: hit_stride below min(max_hits, resident targets)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy2DAsync(hits, (size_t)hit_stride * sizeof(mmgpu_pf_hit), b->d_hits.p, (size_t)b->stride * sizeof(mmgpu_pf_hit),
+                             (size_t)b->stride * sizeof(mmgpu_pf_hit), b->nq, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(counts, b->d_counts.p, (size_t)b->nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MMGPU_OK;
+}
+
+extern "C" int mmgpu_scan_fetch_device(mmgpu_ctx *c, mmgpu_scan_batch_t *b, void *d_hits, uint32_t hit_stride, void *d_counts) {
+    int rc = scan_check_batch("mmgpu_scan_fetch_device", c, b, true);
+    if (rc != MMGPU_OK) return rc;
+    if (!d_hits || !d_counts) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch_device: NULL argument");
+    if (hit_stride < b->stride) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch_device: hit_stride below min(max_hits, resident targets)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy2DAsync(d_hits, (size_t)hit_stride * sizeof(mmgpu_pf_hit), b->d_hits.p, (size_t)b->stride * sizeof(mmgpu_pf_hit),
+                             (size_t)b->stride * sizeof(mmgpu_pf_hit), b->nq, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_counts, b->d_counts.p, (size_t)b->nq * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    return MMGPU_OK;
+}
+
+extern "C" int mmgpu_scan_last_kernel_ms(mmgpu_ctx *c, mmgpu_scan_batch_t *b, float *ms) {
+    int rc = scan_check_batch("mmgpu_scan_last_kernel_ms", c, b, true);
+    if (rc != MMGPU_OK) return rc;
+    if (!ms) return fail(MMGPU_ERR_ARG, "mmgpu_scan_last_kernel_ms: NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(b->ev1));
+    HIP_TRY(hipEventElapsedTime(ms, b->ev0, b->ev1));
+    return MMGPU_OK;
+}
+
+extern "C" void mmgpu_scan_free(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
+    if (!b) return;
+    if (c) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+    }
+    delete b;
+}
+
+extern "C" int mmgpu_scan_batch(mmgpu_ctx *c, const mmgpu_scan_params *par, const mmgpu_scan_query *qs, uint32_t nq, mmgpu_pf_hit *hits,
+                                uint32_t hit_stride, uint32_t *counts) {
+    mmgpu_scan_batch_t *b = nullptr;
+    int rc = mmgpu_scan_prepare(c, par, qs, nq, &b);
+    if (rc != MMGPU_OK) return rc;
+    rc = mmgpu_scan_run(c, b);
+    if (rc == MMGPU_OK) rc = mmgpu_scan_fetch(c, b, hits, hit_stride, counts);
+    mmgpu_scan_free(c, b);
+    return rc;
+}
+
+extern "C" int mmgpu_scan_debug_scores(mmgpu_ctx *c, mmgpu_scan_batch_t *b, uint32_t query, uint8_t *out, size_t cap) {
+    int rc = scan_check_batch("mmgpu_scan_debug_scores", c, b, true);
+    if (rc != MMGPU_OK) return rc;
+    if (c->scan_serial != b->serial) return fail(MMGPU_ERR_STATE, "mmgpu_scan_debug_scores: another scan batch has run on the context since");
+    if (!out || query >= b->nq || cap < b->n_targets) return fail(MMGPU_ERR_ARG, "mmgpu_scan_debug_scores: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, c->scan_scores.as<uint8_t>() + (size_t)query * b->n_targets, b->n_targets, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MMGPU_OK;
+}

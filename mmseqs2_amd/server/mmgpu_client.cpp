@@ -177,6 +177,30 @@ int mmgpu_sw_debug_masked_target(mmgpu_ctx *, mmgpu_sw_batch_t *, uint32_t, uint
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_debug_masked_target: a test aid, not served through mmgpu_server");
 }
 
+// the exhaustive ungapped scan: the binary runs --prefilter-mode 1 on the host, nothing of it crosses the socket
+int mmgpu_scan_prepare(mmgpu_ctx *, const mmgpu_scan_params *, const mmgpu_scan_query *, uint32_t, mmgpu_scan_batch_t **batch) {
+    if (batch) *batch = nullptr;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: not served through mmgpu_server (the binary runs --prefilter-mode 1 on the host)");
+}
+int mmgpu_scan_run(mmgpu_ctx *, mmgpu_scan_batch_t *) { return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_run: not served through mmgpu_server"); }
+int mmgpu_scan_fetch(mmgpu_ctx *, mmgpu_scan_batch_t *, mmgpu_pf_hit *, uint32_t, uint32_t *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_fetch: not served through mmgpu_server");
+}
+int mmgpu_scan_fetch_device(mmgpu_ctx *, mmgpu_scan_batch_t *, void *, uint32_t, void *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_fetch_device: not served through mmgpu_server");
+}
+int mmgpu_scan_last_kernel_ms(mmgpu_ctx *, mmgpu_scan_batch_t *, float *ms) {
+    if (ms) *ms = 0.0f;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_last_kernel_ms: not served through mmgpu_server");
+}
+void mmgpu_scan_free(mmgpu_ctx *, mmgpu_scan_batch_t *) {}
+int mmgpu_scan_batch(mmgpu_ctx *, const mmgpu_scan_params *, const mmgpu_scan_query *, uint32_t, mmgpu_pf_hit *, uint32_t, uint32_t *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_batch: not served through mmgpu_server (the binary runs --prefilter-mode 1 on the host)");
+}
+int mmgpu_scan_debug_scores(mmgpu_ctx *, mmgpu_scan_batch_t *, uint32_t, uint8_t *, size_t) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_debug_scores: a test aid, not served through mmgpu_server");
+}
+
 int mmgpu_sw_block_tiers(const mmgpu_sw_batch_t *, uint32_t *first_tier, uint32_t *second_tier) {
     if (first_tier) *first_tier = 0;
     if (second_tier) *second_tier = 0;
