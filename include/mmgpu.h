@@ -701,16 +701,21 @@ void mmgpu_pf_free(mmgpu_ctx *ctx, mmgpu_pf_batch_t *batch);
  * `mmseqs ungappedprefilter` (--prefilter-mode 1): no k-mer index, no sensitivity - every query against every resident target,
  * scored with the best ungapped diagonal as SmithWaterman::ungapped_alignment computes it on the byte profile of ssw_init
  * (StripedSmithWaterman.cpp:1817-1876, :1364-1440):
- *     p(i, x) = mat[x * alphabet + q[i]] + comp_bias[i]
- *     B       = |min(mat)| + |min(0, min_i comp_bias[i])|           (profile->bias; the minimum over the whole table)
+ *     sequence query:  p(i, x) = mat[x * alphabet + q[i]] + comp_bias[i]
+ *                      B       = |min(mat)| + |min(0, min_i comp_bias[i])|    (profile->bias; the minimum over the whole table)
+ *     profile query:   p(i, x) = profile[x * qlen + i] for x < profile_letters, 0 for every other letter (the X state, :1389-1391)
+ *                      B       = |min(0, min profile[0 .. profile_letters * qlen))|   (neither the matrix nor comp_bias takes part,
+ *                                                                                       :1376-1385)
  *     S(i, j) = max(0, min(255 - B, S(i-1, j-1) + p(i, t[j]))),     score = max S, 0 for an empty target
  * A query's list holds the targets inside its length window whose score is > min_score, and the query's own target whatever it
  * scores, in the order of hit_t::compareHitsByScoreAndId (score descending, id ascending), cut at max_hits; diagonal is 0.
- * SEQUENCE queries over the resident PROTEIN database only: profile queries and nucleotide databases are not served (the
- * structs have no field for the former; an alphabet above 32 is MMGPU_ERR_UNSUPPORTED).
- * MMGPU_ERR_ARG: a letter outside the alphabet, 255 - B <= 0, max(p) + B > 255 (the reference's byte profile wraps there), an
- * empty query.  MMGPU_ERR_STATE: no targets loaded.  MMGPU_ERR_UNSUPPORTED: max_hits above MMGPU_PF_MAX_FUSED_HITS; more than
- * 4 GiB of scores (n_queries x resident targets bytes: send smaller batches); a context that holds a shard (mmgpu_pf_set_shard). */
+ * Sequence and profile queries (runFilterOnCpu hands qSeq.getAlignmentProfile() to ssw_init, ungappedprefilter.cpp:381-385) may
+ * share a batch.  The resident PROTEIN database only: nucleotide databases are not served (an alphabet above 32 is
+ * MMGPU_ERR_UNSUPPORTED).
+ * MMGPU_ERR_ARG: a letter of a sequence query outside the alphabet, a profile with profile_letters 0 or above alphabet,
+ * 255 - B <= 0, max(p) + B > 255 (the reference's byte profile wraps there), an empty query.  MMGPU_ERR_STATE: no targets loaded.
+ * MMGPU_ERR_UNSUPPORTED: max_hits above MMGPU_PF_MAX_FUSED_HITS; more than 4 GiB of scores (n_queries x resident targets bytes:
+ * send smaller batches); a context that holds a shard (mmgpu_pf_set_shard). */
 typedef struct {
     const int8_t *mat;   /* alphabet*alphabet, row-major: tinySubMat (ungappedprefilter.cpp:541-548) */
     int alphabet;        /* that of the resident targets */
@@ -718,13 +723,16 @@ typedef struct {
     uint32_t max_hits;   /* par.maxResListLen (--max-seqs), >= 1 */
 } mmgpu_scan_params;
 typedef struct {
-    const uint8_t *q;        /* Sequence::numSequence */
-    uint32_t qlen;
-    const int8_t *comp_bias; /* rounded as ssw_init rounds it (mmgpu_host_round_comp_bias); NULL = none (--comp-bias-corr 0) */
+    const uint8_t *q;        /* Sequence::numSequence; not read for a profile query (may be NULL there) */
+    uint32_t qlen;           /* a profile query: the profile's length (qSeq.L) */
+    const int8_t *comp_bias; /* rounded as ssw_init rounds it (mmgpu_host_round_comp_bias); NULL = none (--comp-bias-corr 0);
+                                ignored for a profile query */
     uint32_t identity_id;    /* the query's own target (same-database runs, ungappedprefilter.cpp:396), UINT32_MAX = none: as
                                 mmgpu_pf_query::identity_id */
     uint32_t min_tlen, max_tlen; /* inclusive window of target lengths Util::canBeCovered admits for this query (Util.cpp:542-559:
                                     monotone in the target length); 0 and UINT32_MAX = every length */
+    const int8_t *profile;   /* NULL = sequence query; else Sequence::getAlignmentProfile(): [profile_letters][qlen], letter-major */
+    uint32_t profile_letters;/* rows of `profile` (the reference: 20), 1 .. alphabet; 0 = sequence query */
 } mmgpu_scan_query;
 typedef struct mmgpu_scan_batch_t mmgpu_scan_batch_t;
 /* validates the inputs, computes B per query, cuts the jobs, H2D copies; *batch is NULL on failure */

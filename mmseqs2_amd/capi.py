@@ -134,7 +134,7 @@ class ScanParams(ctypes.Structure):      # mmgpu_scan_params
 
 class ScanQuery(ctypes.Structure):      # mmgpu_scan_query
     _fields_ = [("q", c_p), ("qlen", ctypes.c_uint32), ("comp_bias", c_p), ("identity_id", ctypes.c_uint32),
-                ("min_tlen", ctypes.c_uint32), ("max_tlen", ctypes.c_uint32)]
+                ("min_tlen", ctypes.c_uint32), ("max_tlen", ctypes.c_uint32), ("profile", c_p), ("profile_letters", ctypes.c_uint32)]
 
 
 class PfShard(ctypes.Structure):
@@ -303,7 +303,8 @@ PF_QUERY_DTYPE = np.dtype([("q", np.uint64), ("qlen", np.uint32), ("_p0", np.uin
                            ("_p2", np.uint32), ("profile", np.uint64)])
 assert SW_QUERY_DTYPE.itemsize == ctypes.sizeof(SwQuery) and PF_QUERY_DTYPE.itemsize == ctypes.sizeof(PfQuery)
 SCAN_QUERY_DTYPE = np.dtype([("q", np.uint64), ("qlen", np.uint32), ("_p0", np.uint32), ("comp_bias", np.uint64), ("identity_id", np.uint32),
-                             ("min_tlen", np.uint32), ("max_tlen", np.uint32), ("_p1", np.uint32)])
+                             ("min_tlen", np.uint32), ("max_tlen", np.uint32), ("_p1", np.uint32), ("profile", np.uint64),
+                             ("profile_letters", np.uint32), ("_p2", np.uint32)])
 assert SCAN_QUERY_DTYPE.itemsize == ctypes.sizeof(ScanQuery)
 
 
@@ -1000,24 +1001,34 @@ class MMGpu:
         return out
 
     def _scan_marshal(self, mat, queries, min_score, max_hits):
-        """queries: list of dicts {q: uint8[], comp_bias: int8[]|None (rounded), identity_id: int|None, window: (min_tlen, max_tlen)|None}"""
+        """queries: list of dicts {q: uint8[], comp_bias: int8[]|None (rounded), identity_id: int|None, window: (min_tlen, max_tlen)|None,
+        profile: int8[letters][qlen]|None (profile query: Sequence::getAlignmentProfile; q may then be absent, the library ignores comp_bias)}"""
         mat = np.ascontiguousarray(mat, np.int8)
         par = ScanParams(_ptr(mat), mat.shape[0], int(min_score), int(max_hits))
         arr = (ScanQuery * max(len(queries), 1))()
         keep = [mat]
         for i, qd in enumerate(queries):
-            q = np.ascontiguousarray(qd["q"], np.uint8)
+            prof = None if qd.get("profile") is None else np.ascontiguousarray(qd["profile"], np.int8)
+            if prof is not None and prof.ndim != 2:
+                raise ValueError("profile must be [letters][qlen]")
+            q = None if qd.get("q") is None else np.ascontiguousarray(qd["q"], np.uint8)
+            if q is None and prof is None:
+                raise ValueError("a query needs q or profile")
+            qlen = prof.shape[1] if prof is not None else len(q)
+            if q is not None and len(q) != qlen:
+                raise ValueError("profile must be [letters][qlen]")
             cb = None if qd.get("comp_bias") is None else np.ascontiguousarray(qd["comp_bias"], np.int8)
-            if cb is not None and len(cb) != len(q):
+            if cb is not None and len(cb) != qlen:
                 raise ValueError("comp_bias must have the query's length")
             ident = qd.get("identity_id")
             lo, hi = qd.get("window") or (0, 0xFFFFFFFF)
-            keep += [q, cb]
-            arr[i] = ScanQuery(_ptr(q), len(q), _ptr(cb), 0xFFFFFFFF if ident is None else int(ident), int(lo), int(hi))
+            keep += [q, cb, prof]
+            arr[i] = ScanQuery(_ptr(q), qlen, _ptr(cb), 0xFFFFFFFF if ident is None else int(ident), int(lo), int(hi), _ptr(prof),
+                               0 if prof is None else prof.shape[0])
         return par, arr, keep
 
     def scan_prepare(self, mat, queries, min_score=15, max_hits=300):
-        """mmgpu_scan_prepare: the exhaustive ungapped scan (`ungappedprefilter`) of sequence queries over the resident targets"""
+        """mmgpu_scan_prepare: the exhaustive ungapped scan (`ungappedprefilter`) of sequence and profile queries over the resident targets"""
         par, arr, keep = self._scan_marshal(mat, queries, min_score, max_hits)
         h = c_p()
         self._check(self.L.mmgpu_scan_prepare(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), ctypes.byref(h)))
@@ -1095,7 +1106,8 @@ class MMGpu:
 def exhaustive_search(gpu, scan_mat, sw_mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, mode=1):
     """Exhaustive search on one device without a list leaving it: scan_prepare + run, fetch_device into a device buffer,
     sw_prepare_from_lists over it, run, fetch.  queries: dicts with q, comp_bias (rounded int8 or None; the same bias serves both
-    stages, as ssw_init computes it once), identity_id, window, min_start_score.
+    stages, as ssw_init computes it once), identity_id, window, min_start_score; a profile query adds profile (int8 [letters][qlen],
+    read by both stages, which then ignore comp_bias) and keeps q = its consensus sequence, which the alignment stage needs.
     -> (hits[nq][stride], counts[nq], records[nq][stride] SW_HIT_DTYPE: slot k of a row = hit k of the query's list)"""
     import torch
     scan = gpu.scan_prepare(scan_mat, queries, min_score, max_hits)

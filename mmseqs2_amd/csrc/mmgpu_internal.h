@@ -211,6 +211,8 @@ __host__ __device__ constexpr uint32_t scan_cols(uint32_t len, int R) { return (
 // dwords of one DPP row's boundary line (multi-tile): two buffers of scan_cols + 1 entries, rounded to whole 64-byte lines
 __host__ __device__ constexpr uint32_t scan_park_row_words(uint32_t longest) { return 2u * ((scan_cols(longest, SCAN_MAX_R) + 1u + 15u) & ~15u); }
 
+constexpr uint64_t SCAN_NO_PROFILE = ~0ull;           // ScanLaunch::q_prof_off of a sequence query
+
 struct ScanJob {
     uint32_t query;
     uint32_t begin, end;      // positions in the length-sorted id list (longest first)
@@ -224,6 +226,11 @@ struct ScanLaunch {
     const int8_t *q_cb;       // concatenated rounded composition bias (zeros when absent)
     const uint32_t *q_off;    // [nq + 1]
     const int32_t *q_cap;     // [nq] 255 - B
+    // profile queries: q_prof + q_prof_off[query] is the query's int8 [q_prof_letters[query]][qlen], letter-major; a sequence query
+    // has SCAN_NO_PROFILE there (its rows come from mat, q_res and q_cb)
+    const int8_t *q_prof;
+    const uint64_t *q_prof_off;      // [nq]
+    const uint32_t *q_prof_letters;  // [nq]
     const uint8_t *t_res;
     const uint32_t *t_off4, *t_len;
     const uint32_t *order;    // [n_targets] ids by length, longest first

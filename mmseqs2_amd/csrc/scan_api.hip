@@ -1,5 +1,5 @@
-// Host side of the exhaustive ungapped scan (include/mmgpu.h, "exhaustive ungapped scan"): validation, the per-query bias,
-// the job lists, launches of scan_kernel.hip.  prepare and run are sequences of named steps over one record each, in the manner of
+// Host side of the exhaustive ungapped scan (include/mmgpu.h, "exhaustive ungapped scan"): validation, the per-query bias of sequence
+// and of profile queries, the job lists, launches of scan_kernel.hip.  prepare and run are sequences of named steps over one record each, in the manner of
 // sw_prepare_impl (mmgpu_api.hip).
 #include <algorithm>
 #include <cstring>
@@ -17,7 +17,8 @@ struct mmgpu_scan_batch_t {
     const uint8_t *db_res = nullptr;      // the resident database the batch was prepared against (a reload invalidates the batch)
     uint64_t serial = 0;                  // names this batch in mmgpu_ctx::scan_serial
     bool ran = false;
-    DevBuf d_qres, d_qcb, d_qoff, d_qcap, d_qident, d_qwin, d_mat, d_order, d_jobs, d_park_off, d_hits, d_counts;
+    DevBuf d_qres, d_qcb, d_qoff, d_qcap, d_qprof, d_qprof_off, d_qprof_letters, d_qident, d_qwin, d_mat, d_order, d_jobs, d_park_off,
+        d_hits, d_counts;
     uint32_t class_begin[SCAN_CLASSES + 1] = {};   // jobs of class k: d_jobs[class_begin[k] .. class_begin[k + 1])
     uint32_t multi_grid = 0;              // persistent workgroups of the multi-tile launch
     uint64_t park_words = 0;              // dwords of boundary lines they need
@@ -39,7 +40,9 @@ struct ScanPrepare {
     const mmgpu_scan_query *qs;
     uint32_t nq;
     std::vector<uint8_t> qres;
-    std::vector<int8_t> qcb;
+    std::vector<int8_t> qcb, qprof;      // qprof: the profile queries' tables, one after the other
+    std::vector<uint64_t> qprof_off;     // [nq] offset into qprof, SCAN_NO_PROFILE for a sequence query
+    std::vector<uint32_t> qprof_letters; // [nq]
     std::vector<uint32_t> qoff, qident, qwin, order, first_le;   // first_le[L]: position of the first target of length <= L in `order`
     std::vector<int32_t> qcap;
     std::vector<ScanJob> jobs;
@@ -59,38 +62,82 @@ int scan_check_call(const ScanPrepare &S) {
     return MMGPU_OK;
 }
 
-// residues, bias, window and identity of every query; B and 255 - B as ssw_init derives them (StripedSmithWaterman.cpp:1397-1406)
+// the two range checks of a query whose bias is B and whose highest profile score is p_max, and its cap (ssw_init, :1397-1406)
+int scan_cap_of(int B, int p_max, int32_t *cap) {
+    if (255 - B <= 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: the bias leaves no score range (255 - B <= 0)");
+    if (p_max + B > 255) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: a profile score plus the bias exceeds 255 (the reference's byte profile wraps)");
+    *cap = 255 - B;
+    return MMGPU_OK;
+}
+
+// a profile query: its table goes into the pool, B comes from the table alone (StripedSmithWaterman.cpp:1376-1385, :1397-1406);
+// q and comp_bias are not read, the residue pools get zeros so that q_off keeps giving every query's length
+int scan_marshal_profile(ScanPrepare &S, const mmgpu_scan_query &Q, int32_t *cap) {
+    if (Q.profile_letters == 0 || Q.profile_letters > (uint32_t)S.par->alphabet)
+        return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: profile_letters must be 1 .. alphabet for a profile query");
+    const size_t n = (size_t)Q.profile_letters * Q.qlen;
+    int p_min = 0, p_max = -128;
+    for (size_t k = 0; k < n; k++) {
+        p_min = std::min<int>(p_min, Q.profile[k]);
+        p_max = std::max<int>(p_max, Q.profile[k]);
+    }
+    const int rc = scan_cap_of(std::abs(p_min), std::max(p_max, 0), cap);      // (the letters without a row score 0)
+    if (rc != MMGPU_OK) return rc;
+    S.qprof_off.push_back(S.qprof.size());
+    S.qprof_letters.push_back(Q.profile_letters);
+    S.qprof.insert(S.qprof.end(), Q.profile, Q.profile + n);
+    S.qres.insert(S.qres.end(), Q.qlen, 0);
+    S.qcb.insert(S.qcb.end(), Q.qlen, 0);
+    return MMGPU_OK;
+}
+
+struct ScanMatRange {
+    int mat_min = 0;
+    std::vector<int> col_max;      // best score a query letter can meet
+};
+
+int scan_marshal_sequence(ScanPrepare &S, const mmgpu_scan_query &Q, const ScanMatRange &M, int32_t *cap) {
+    if (!Q.q) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: empty query");
+    int cb_min = 0, p_max = -32768;
+    for (uint32_t k = 0; k < Q.qlen; k++) {
+        if (Q.q[k] >= S.par->alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: query letter outside the alphabet");
+        const int cb = Q.comp_bias ? Q.comp_bias[k] : 0;
+        cb_min = std::min(cb_min, cb);
+        p_max = std::max(p_max, M.col_max[Q.q[k]] + cb);
+    }
+    const int rc = scan_cap_of(std::abs(M.mat_min) + std::abs(cb_min), p_max, cap);
+    if (rc != MMGPU_OK) return rc;
+    S.qprof_off.push_back(SCAN_NO_PROFILE);
+    S.qprof_letters.push_back(0);
+    S.qres.insert(S.qres.end(), Q.q, Q.q + Q.qlen);
+    if (Q.comp_bias) S.qcb.insert(S.qcb.end(), Q.comp_bias, Q.comp_bias + Q.qlen);
+    else S.qcb.insert(S.qcb.end(), Q.qlen, 0);
+    return MMGPU_OK;
+}
+
+// residues or profile, bias, window and identity of every query; B and 255 - B as ssw_init derives them
+// (StripedSmithWaterman.cpp:1397-1406)
 int scan_marshal_queries(ScanPrepare &S) {
     const int alphabet = S.par->alphabet;
     const int8_t *mat = S.par->mat;
-    int mat_min = 0;
-    for (int i = 0; i < alphabet * alphabet; i++) mat_min = std::min<int>(mat_min, mat[i]);
-    std::vector<int> col_max(alphabet, -128);      // best score a query letter can meet
+    ScanMatRange M;
+    for (int i = 0; i < alphabet * alphabet; i++) M.mat_min = std::min<int>(M.mat_min, mat[i]);
+    M.col_max.assign(alphabet, -128);
     for (int x = 0; x < alphabet; x++)
-        for (int a = 0; a < alphabet; a++) col_max[a] = std::max<int>(col_max[a], mat[x * alphabet + a]);
+        for (int a = 0; a < alphabet; a++) M.col_max[a] = std::max<int>(M.col_max[a], mat[x * alphabet + a]);
     S.qoff.assign(1, 0);
     uint64_t total = 0;
     for (uint32_t i = 0; i < S.nq; i++) {
         const mmgpu_scan_query &Q = S.qs[i];
-        if (!Q.q || Q.qlen == 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: empty query");
+        if (Q.qlen == 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: empty query");
         if (Q.min_tlen > Q.max_tlen) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: min_tlen above max_tlen");
         total += Q.qlen;
         if (total > 0x7FFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: more than 2 GiB of query residues in one batch");
-        int cb_min = 0, p_max = -32768;
-        for (uint32_t k = 0; k < Q.qlen; k++) {
-            if (Q.q[k] >= alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: query letter outside the alphabet");
-            const int cb = Q.comp_bias ? Q.comp_bias[k] : 0;
-            cb_min = std::min(cb_min, cb);
-            p_max = std::max(p_max, col_max[Q.q[k]] + cb);
-        }
-        const int B = std::abs(mat_min) + std::abs(cb_min);
-        if (255 - B <= 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: the bias leaves no score range (255 - B <= 0)");
-        if (p_max + B > 255) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: a profile score plus the bias exceeds 255 (the reference's byte profile wraps)");
-        S.qres.insert(S.qres.end(), Q.q, Q.q + Q.qlen);
-        if (Q.comp_bias) S.qcb.insert(S.qcb.end(), Q.comp_bias, Q.comp_bias + Q.qlen);
-        else S.qcb.insert(S.qcb.end(), Q.qlen, 0);
+        int32_t cap = 0;
+        const int rc = Q.profile ? scan_marshal_profile(S, Q, &cap) : scan_marshal_sequence(S, Q, M, &cap);
+        if (rc != MMGPU_OK) return rc;
         S.qoff.push_back((uint32_t)total);
-        S.qcap.push_back(255 - B);
+        S.qcap.push_back(cap);
         S.qident.push_back(Q.identity_id);
         S.qwin.push_back(Q.min_tlen);
         S.qwin.push_back(Q.max_tlen);
@@ -149,14 +196,17 @@ void scan_cut_jobs(ScanPrepare &S, mmgpu_scan_batch_t *b) {
 int scan_upload(ScanPrepare &S, mmgpu_scan_batch_t *b) {
     mmgpu_ctx *c = S.c;
     hipStream_t s = c->stream;
-    for (DevBuf *d : {&b->d_qres, &b->d_qcb, &b->d_qoff, &b->d_qcap, &b->d_qident, &b->d_qwin, &b->d_mat, &b->d_order, &b->d_jobs,
-                      &b->d_park_off, &b->d_hits, &b->d_counts})
+    for (DevBuf *d : {&b->d_qres, &b->d_qcb, &b->d_qoff, &b->d_qcap, &b->d_qprof, &b->d_qprof_off, &b->d_qprof_letters, &b->d_qident,
+                      &b->d_qwin, &b->d_mat, &b->d_order, &b->d_jobs, &b->d_park_off, &b->d_hits, &b->d_counts})
         d->bind(c->cache);
     std::vector<int8_t> mat(S.par->mat, S.par->mat + (size_t)S.par->alphabet * S.par->alphabet);
     HIP_TRY(upload(b->d_qres, S.qres, s));
     HIP_TRY(upload(b->d_qcb, S.qcb, s));
     HIP_TRY(upload(b->d_qoff, S.qoff, s));
     HIP_TRY(upload(b->d_qcap, S.qcap, s));
+    HIP_TRY(upload(b->d_qprof, S.qprof, s));
+    HIP_TRY(upload(b->d_qprof_off, S.qprof_off, s));
+    HIP_TRY(upload(b->d_qprof_letters, S.qprof_letters, s));
     HIP_TRY(upload(b->d_qident, S.qident, s));
     HIP_TRY(upload(b->d_qwin, S.qwin, s));
     HIP_TRY(upload(b->d_mat, mat, s));
@@ -210,6 +260,9 @@ int scan_launch_classes(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
     L.q_cb = b->d_qcb.as<int8_t>();
     L.q_off = b->d_qoff.as<uint32_t>();
     L.q_cap = b->d_qcap.as<int32_t>();
+    L.q_prof = b->d_qprof.as<int8_t>();
+    L.q_prof_off = b->d_qprof_off.as<uint64_t>();
+    L.q_prof_letters = b->d_qprof_letters.as<uint32_t>();
     L.t_res = c->db.res;
     L.t_off4 = c->db.off4;
     L.t_len = c->db.len;

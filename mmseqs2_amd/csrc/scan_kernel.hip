@@ -3,9 +3,10 @@
 // src/prefiltering/ungappedprefilter.cpp:346-482), and the selection of each query's list out of the score bytes.
 //
 // What it computes, per pair:   U(i, j) = max(0, sat16(U(i-1, j-1) + p(i, t[j]))),   score = min(255 - B, max U)
-// with p(i, x) = mat[x][q[i]] + comp_bias[i].  The reference clamps every cell at 255 - B (unsigned bytes, adds then subs of the
-// bias B); the capped and the uncapped recurrence agree until the cap first bites, and from there the capped maximum IS the cap,
-// so one min at the end gives the same number.
+// with p(i, x) = mat[x][q[i]] + comp_bias[i] for a sequence query and p(i, x) = prof[x][i] (x < profile_letters, else 0) for a
+// profile query (B then comes from the profile alone; scan_api.hip).  The reference clamps every cell at 255 - B (unsigned bytes,
+// adds then subs of the bias B); the capped and the uncapped recurrence agree until the cap first bites, and from there the capped
+// maximum IS the cap, so one min at the end gives the same number.
 //
 // How it is mapped (sw_kernel.hip's mapping where it serves):
 //  * packed 2 x int16: the low half of every register belongs to target A, the high half to target B of a pair taken from the
@@ -16,7 +17,8 @@
 //    and no register is ever moved.  Per row pair: v_perm_b32 (interleave the two letters' profile rows), v_pk_add_i16 clamp,
 //    v_pk_max_i16 with 0, v_pk_max_i16 into the running maximum.
 //  * the query profile P[letter][row] (int16, composition bias folded in, 0 for the rows past the query and for the pad letter)
-//    is built once per workgroup in LDS in sw_kernel.hip's layout (odd number of 16-byte slots per lane).
+//    is built once per workgroup in LDS in sw_kernel.hip's layout (odd number of 16-byte slots per lane).  A profile query's rows
+//    are copied from its own int8 table instead; from there on the two kinds of query run the same code.
 //  * four rows per wave64, four waves per workgroup: 32 targets per round, SCAN_JOB_TARGETS per job.  Target letters are read
 //    a chunk ahead, four per dword; words past a target's end read as the pad letter, whose profile row is 0.
 //  * queries longer than one tile (512 rows): the tile loop runs inside the kernel; the value leaving the last lane is parked in a
@@ -51,10 +53,32 @@ struct Tile {
     static constexpr int ROW_STRIDE = GROUP * LANE_STRIDE;   // bytes per letter
 };
 
-// P[letter][row] for rows [tile_base, tile_base + ROWS): 0 past the query's end and for the pad letter `alphabet`
+// where a job's profile rows come from: a sequence query (prof == nullptr) or a profile query's own table
+struct ScanSource {
+    const uint8_t *q;
+    const int8_t *cb;
+    const int8_t *prof;      // [prof_letters][qlen], letter-major
+    int prof_letters;
+    int qlen;
+};
+
+__device__ __forceinline__ ScanSource scan_source(const ScanLaunch &L, uint32_t query) {
+    const uint32_t qo = L.q_off[query];
+    const uint64_t po = L.q_prof_off[query];
+    ScanSource S;
+    S.q = L.q_res + qo;
+    S.cb = L.q_cb + qo;
+    S.prof = po == SCAN_NO_PROFILE ? nullptr : L.q_prof + po;
+    S.prof_letters = (int)L.q_prof_letters[query];
+    S.qlen = (int)(L.q_off[query + 1] - qo);
+    return S;
+}
+
+// P[letter][row] for rows [tile_base, tile_base + ROWS): 0 past the query's end and for the pad letter `alphabet`; for a profile
+// query also for the letters it has no row for.  Consecutive threads take consecutive rows of one letter, so a profile query's reads
+// are contiguous bytes; the source is the job's, hence uniform over the workgroup.
 template <int R>
-__device__ __forceinline__ void build_profile(unsigned char *lds, const uint8_t *q, const int8_t *cb, int qlen, int tile_base,
-                                              const int8_t *mat, int alphabet) {
+__device__ __forceinline__ void build_profile(unsigned char *lds, const ScanSource &S, int tile_base, const int8_t *mat, int alphabet) {
     using T = Tile<R>;
     const int total = (alphabet + 1) * T::ROWS;
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
@@ -62,7 +86,11 @@ __device__ __forceinline__ void build_profile(unsigned char *lds, const uint8_t 
         const int row = idx - letter * T::ROWS;
         const int rg = tile_base + row;
         short v = 0;
-        if (letter < alphabet && rg < qlen) v = (short)((int)mat[letter * alphabet + q[rg]] + (int)cb[rg]);
+        if (S.prof) {
+            if (letter < S.prof_letters && rg < S.qlen) v = (short)S.prof[(size_t)letter * (size_t)S.qlen + (size_t)rg];
+        } else if (letter < alphabet && rg < S.qlen) {
+            v = (short)((int)mat[letter * alphabet + S.q[rg]] + (int)S.cb[rg]);
+        }
         const int lane = row / R, r = row - lane * R;
         *reinterpret_cast<short *>(lds + letter * T::ROW_STRIDE + lane * T::LANE_STRIDE + r * 2) = v;
     }
@@ -133,13 +161,13 @@ __global__ __launch_bounds__(WAVES * 64) void scan_kernel(ScanLaunch L) {
 
     for (uint32_t job = blockIdx.x; job < L.n_jobs; job += gridDim.x) {
         const ScanJob J = L.jobs[job];
-        const uint32_t qo = L.q_off[J.query];
-        const int qlen = (int)(L.q_off[J.query + 1] - qo);
+        const ScanSource S = scan_source(L, J.query);
+        const int qlen = S.qlen;
         const int cap = L.q_cap[J.query];
         const int n_tiles = MULTI ? (qlen + T::ROWS - 1) / T::ROWS : 1;
         if (!MULTI) {
             __syncthreads();
-            build_profile<R>(scan_lds, L.q_res + qo, L.q_cb + qo, qlen, 0, L.mat, L.alphabet);
+            build_profile<R>(scan_lds, S, 0, L.mat, L.alphabet);
             __syncthreads();
         }
         // multi-tile: this DPP row's two boundary lines in the workgroup's slot (the slot was sized for its longest job)
@@ -167,7 +195,7 @@ __global__ __launch_bounds__(WAVES * 64) void scan_kernel(ScanLaunch L) {
             for (int tile = 0; tile < n_tiles; tile++) {
                 if (MULTI) {
                     __syncthreads();
-                    build_profile<R>(scan_lds, L.q_res + qo, L.q_cb + qo, qlen, tile * T::ROWS, L.mat, L.alphabet);
+                    build_profile<R>(scan_lds, S, tile * T::ROWS, L.mat, L.alphabet);
                     __syncthreads();
                 }
                 uint32_t *park_out = MULTI ? park + (uint32_t)(tile & 1) * park_half : nullptr;

@@ -5,7 +5,8 @@ Workload: --queries queries drawn by the generator of BASELINE.json configs[2] w
 (everything resident).  Warm-up, then --steps timed runs in this process: kernel time from mmgpu_scan_last_kernel_ms, wall time
 around run + synchronize.  Yardstick, in the same process: mmgpu_sw_prepare in MMGPU_SW_SCORE_END mode (the Gotoh forward scan)
 over the same queries against the first --slice targets, and the scan's own rate on that same slice.  Cells = query length x
-target length summed over the pairs a kernel scores."""
+target length summed over the pairs a kernel scores.  --profile: the same queries run as profile queries in the two scan runs (each
+query's [20][qlen] profile is its letters' substitution rows; the Gotoh yardstick keeps the sequence queries)."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +24,7 @@ ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=1)
 ap.add_argument("--max-hits", type=int, default=300)
 ap.add_argument("--min-score", type=int, default=15)
+ap.add_argument("--profile", action="store_true", help="run the scan's queries as profile queries (mmgpu_scan_query::profile)")
 ap.add_argument("--out", default="")
 args = ap.parse_args()
 
@@ -34,6 +36,8 @@ t_gen = time.time() - t0
 qs = wl.split(qres, qoff)[:args.queries]
 cbs = [capi.host_comp_bias(mat.astype(np.int16), m["blosum62_pback"], q)[1] for q in qs]
 queries = [dict(q=q, comp_bias=cb, identity_id=None) for q, cb in zip(qs, cbs)]
+if args.profile:
+    queries = [dict(profile=np.ascontiguousarray(mat[:20, q]), identity_id=None) for q in qs]
 qlen_sum = int(sum(len(q) for q in qs))
 gpu = mmseqs2_amd.MMGpu(0)
 
@@ -67,7 +71,7 @@ def scan_rate(res, off, tag):
 
 
 out = dict(workload="%d queries drawn as configs[2]'s are (families %d x members %d), all targets resident" % (len(qs), args.families, args.members),
-           queries=len(qs), query_residues=qlen_sum, steps=args.steps, warmup=args.warmup, t_gen_s=round(t_gen, 1))
+           queries=len(qs), query_kind="profile" if args.profile else "sequence", query_residues=qlen_sum, steps=args.steps, warmup=args.warmup, t_gen_s=round(t_gen, 1))
 out["scan_full"] = scan_rate(tres, toff, "scan, all targets:")
 n_slice = min(args.slice, len(toff) - 1)
 sres, soff = tres[:int(toff[n_slice])], toff[:n_slice + 1]
