@@ -1106,7 +1106,7 @@ int SwPrepare::enqueue_uploads() {
 // per job: a batch of long queries against one very long target would ask for 100+ GB), sized by the longest
 // target any list holds
 hipError_t SwPrepare::alloc_scratch(uint32_t longest) {
-    b->scratch_cols = longest + 16;
+    b->scratch_cols = ((longest + 15u) & ~15u) + 16;      // whole 16-column stretches: every line starts on a 128-byte boundary
     b->scratch_slots = std::min<uint32_t>(std::max<uint32_t>(std::max<uint32_t>(n_multi, (uint32_t)rev_jobs.size()), 1),
                                           sw_multi_resident_blocks(b->group_lds[SW_GROUPS - 1], mode >= MMGPU_SW_START, c->compute_units));
     hipError_t e = b->d_scratch.alloc((size_t)b->scratch_slots * 4 * 4 * 2 * (size_t)b->scratch_cols * sizeof(uint2));

@@ -18,7 +18,11 @@
 //    (R = 1,2,..,32 -> 16..512 rows per tile) whose H/E state lives in registers for the whole scan.
 //    Lanes run skewed by one column (anti-diagonal wavefront): at step s lane g works on column s - g.
 //    The hand-off lane g -> g+1 (H of the strip's last row, the F leaving it, and the two target
-//    letters) is three v_mov_b32_dpp row_shr:1 - no LDS, no bpermute.
+//    letters) is three v_mov_b32_dpp row_shr:1 - no LDS, no bpermute.  The head lane takes zeros for H and F
+//    (bound_ctrl) or the boundary row of the tile above, and its letters from a queue of four (a | b << 8) pairs
+//    that is made once per four columns (two v_perm_b32; the padding letter of columns past a target's end is put
+//    in there, under a scalar branch): what a column costs beside its rows is 11 VALU instructions single-tile,
+//    16 multi-tile (profiles/sw_isa_audit.txt).
 //  * the query profile P[letter][row] (int16, composition bias folded in) is built once per workgroup in
 //    LDS; per step a lane fetches its R scores for letter a (target A) and for letter b (target B) with
 //    ds_read_b128 and interleaves them with v_perm_b32.  The per-lane row stride is padded to an odd
@@ -30,7 +34,8 @@
 //    last raised and a snapshot of the strip's H values at that column (v_bfi under a rarely taken
 //    branch); a 16-lane DPP/shuffle reduction at the end applies the reference's tie rules.
 //  * queries longer than one tile loop over tiles inside the kernel; the H/F row leaving the last lane
-//    is parked in a double-buffered global scratch line and re-enters at the head lane of the next tile.
+//    is parked in a double-buffered global scratch line (lane 15 stores a column per step, under a scalar test) and
+//    re-enters at the head lane of the next tile, loaded 16 columns at a time and rotated one lane per step.
 //    Where the profiles of all tiles fit the workgroup's LDS (two tiles always, three up to R = 24 with 21 letters:
 //    sw_multi_resident, mmgpu_internal.h) they are built once per job and the tile loop only moves the LDS base;
 //    otherwise the one profile is rebuilt per tile, between two barriers.
@@ -76,6 +81,10 @@ __device__ __forceinline__ unsigned bfi(unsigned mask, unsigned a, unsigned b) {
 __device__ __forceinline__ unsigned from_lane_above(unsigned head, unsigned v) {
     return __builtin_amdgcn_update_dpp(head, v, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
 }
+// ... lane 0 of each row gets 0 (bound_ctrl): no register has to hold the zero
+__device__ __forceinline__ unsigned from_lane_above_or_zero(unsigned v) {
+    return __builtin_amdgcn_update_dpp(0u, v, 0x111 /*row_shr:1*/, 0xF, 0xF, true);
+}
 
 // Build knob for A/B measurements (no test builds with 0; the default is what the suite and the bench run):
 // MMGPU_SW_PREFETCH=0 fetches the profile rows in the column that uses them, as before the prefetch.
@@ -83,7 +92,7 @@ __device__ __forceinline__ unsigned from_lane_above(unsigned head, unsigned v) {
 #define MMGPU_SW_PREFETCH 1
 #endif
 // Empty asm that takes a value in and out of a VGPR: the instruction producing it has to stand where the source has it.
-// Used on the E update (and the multi-tile bodies' column maximum) in phase 2 of the column loop - see there.
+// Used on the E update in phase 2 of the column loop - see there.
 #define SW_KEEP_IN_ROW(x) asm volatile("" : "+v"(x))
 
 // (lane_stride_bytes and the size of a tile's profile: mmgpu_internal.h, shared with the host's LDS sizing)
@@ -269,11 +278,22 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
         ncols = max(ncols, __shfl_xor(ncols, 32));
         ncols = __builtin_amdgcn_readfirstlane(ncols);
         const int nsteps = ncols + GROUP - 1;
+        // the shortest target of the wavefront (a half without a pair counts as 0 columns): letter blocks that end at or
+        // before it hold no padding column in any group
+        int mincols = colsA < colsB ? colsA : colsB;
+        mincols = min(mincols, __shfl_xor(mincols, 16));
+        mincols = min(mincols, __shfl_xor(mincols, 32));
+        mincols = __builtin_amdgcn_readfirstlane(mincols);
 
         unsigned long long bestA = 0, bestB = 0;   // (score << 32) | (~col << 16) | ~row, maximised
 
+        // the scratch lines of this wavefront (a wave-uniform address) and where the group's two start in them
         uint2 *scr = nullptr;
-        if (MULTI) scr = L.scratch + ((size_t)((job.shape >> 8) * WAVES + wave) * GROUPS_PER_WAVE + grp) * 2 * L.scratch_cols;
+        unsigned scr_grp = 0;
+        if (MULTI) {
+            scr = L.scratch + (size_t)((job.shape >> 8) * WAVES + wave) * GROUPS_PER_WAVE * 2 * L.scratch_cols;
+            scr_grp = (unsigned)grp * 2u * L.scratch_cols;
+        }
 
         for (int tile = 0; tile < n_tiles; ++tile) {
             const int tile_base = tile * T::ROWS;
@@ -329,19 +349,21 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             };
             unsigned wA = letters4(pA, endA, 0), wB = letters4(pB, endB, 0);
             unsigned wA_next = letters4(pA, endA, 1), wB_next = letters4(pB, endB, 1);
-            // boundary row of the tile above: column s is needed at step s; the load of column s + UPD is issued at step s
-            // (UPD columns of ~300-400 instructions each cover the L2 round trip at two waves per SIMD)
-#ifndef MMGPU_SW_UP_DEPTH
-#define MMGPU_SW_UP_DEPTH 4
-#endif
-            constexpr int UPD = MMGPU_SW_UP_DEPTH;
-            uint2 up[UPD];
-#pragma unroll
-            for (int k = 0; k < UPD; ++k) up[k] = make_uint2(0, 0);
-            if (has_above) {
+            // Boundary row of the tile above, 16 columns (a stretch) at a time: the lanes of the group load one column each -
+            // one coalesced load per 16 steps, issued a stretch ahead - and the live stretch is rotated by one lane per step,
+            // so that the head lane holds column s at step s.  A stretch changes where a block of four steps begins (below):
+            // stretch 0 is the columns 0 .. 15, of which the steps 0 .. 14 use 15, stretch m >= 1 the columns 16 m - 1 .. 16 m + 14.
+            // The index is clamped to the last column of the wavefront: the steps past a group's (or the wavefront's) end read
+            // that column again, as harmless as it was.
+            // Boundary row for the tile below: lane 15 stores its hand-off in every step from its first column on (see there).
+            uint2 bnd = make_uint2(0, 0), bnd_next = make_uint2(0, 0);   // (H, F) of the live stretch and of the one after it
+            auto boundary16 = [&](int m) -> uint2 {   // m is wave-uniform
                 const int last = ncols - 1 < 0 ? 0 : ncols - 1;
-#pragma unroll
-                for (int k = 0; k < UPD; ++k) up[k] = scr_in[min(k, last)];
+                return scr_in[scr_grp + (unsigned)min(16 * m + g - (m > 0 ? 1 : 0), last)];
+            };
+            if (has_above) {
+                bnd = boundary16(0);
+                bnd_next = boundary16(1);
             }
 
             // R scores per target as ND = ceil(R / 2) packed dwords (odd R: the high half of the last one is row padding
@@ -369,46 +391,83 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                     pbv[ND - 1] = reinterpret_cast<const unsigned *>(rowB)[ND - 1];
                 }
             };
-            // PF: the profile rows of a column are fetched one column ahead.  The letters lane g needs in step s + 1 are the
-            // letters lane g - 1 holds in step s (the head lane's come from the letter words), so the hand-off of step s + 1
-            // and its ds_reads are issued in step s, behind the last use of the rows of step s (phase 1) and in front of the
+            // The letters lane g needs in step s + 1 are the letters lane g - 1 holds in step s (the head lane's come from the
+            // letter words): every body hands them on in step s, between the two phases, where the DPP move has the packed ops
+            // of the rows around it - at the top of a column it stood behind the instruction that made the head lane's letters,
+            // and short columns paid wait states for that.  `let` is carried from step to step; the prologue takes column 0.
+            // PF: the profile rows of a column are fetched one column ahead as well: the ds_reads of step s + 1 are issued in
+            // step s behind the hand-off, that is behind the last use of the rows of step s (phase 1) and in front of the
             // serial chain (phase 2): the LDS round trip is covered by the wavefront's own instructions instead of standing
-            // at the top of every column.  `let` / pav / pbv are carried from step to step; the prologue fetches column 0.
+            // at the top of every column.  pav / pbv are carried from step to step too; the prologue fetches column 0.
             // The step after the last one fetches the padding letter's row (s + 1 >= cols), which every tile has: nothing
             // is read past the profile.  The rows stay in the same registers (the reads stand behind their last use), but
             // the compiler moves some reads up, which costs 6 - 24 registers per kernel.
             unsigned let = pad_letter * 0x101u;   // what a lane holds before its first column
-            auto head_letters = [&](int c, int j) -> unsigned {   // column c of the head lane: byte j of the current letter words
-                const unsigned sh = (unsigned)(REV ? 3 - j : j) * 8u;   // wave-uniform
+            // The head lane's letters, prepared once per block of four columns: wA / wB are interleaved into the queue
+            // `lq` of four (a | b << 8) pairs in the order the columns consume them (two v_perm_b32), and a column shifts
+            // its pair out (the consumers read the low 16 bits of `let` only).  Columns past a target's end get the padding
+            // letter here, per block and only in the blocks that reach past the wavefront's shortest target (a scalar
+            // branch): the column loop holds no compare and no select for them.
+            // The single-tile bodies of R <= 6 have too few instructions per column to take this form without wait states they
+            // did not have (profiles/sw_isa_audit.txt): forward they select per column as before (LETTER_BLOCKS
+            // false), in reverse the column shifts the queue itself instead of indexing it (LETTER_QUEUE), one instruction more.
+            constexpr bool LETTER_BLOCKS = MULTI || REV || R >= 7;
+            constexpr bool LETTER_QUEUE = !MULTI && R < 7;
+            unsigned long long lq = 0;
+            auto letter_block = [&](int k) {   // block k = columns 4k .. 4k + 3, from wA / wB
+                if (!LETTER_BLOCKS) return;
+                unsigned a = wA, b = wB;
+                if (4 * k + 4 > mincols) {   // wave-uniform
+                    const unsigned pad4 = pad_letter * 0x01010101u;
+                    const int na = min(max(colsA - 4 * k, 0), 4), nb = min(max(colsB - 4 * k, 0), 4);   // live columns of the block
+                    // forward: column 4k + i is byte i; reverse: byte 3 - i
+                    const unsigned ma = REV ? ~(unsigned)(0xFFFFFFFFull >> (8 * na)) : (unsigned)((1ull << (8 * na)) - 1ull);
+                    const unsigned mb = REV ? ~(unsigned)(0xFFFFFFFFull >> (8 * nb)) : (unsigned)((1ull << (8 * nb)) - 1ull);
+                    a = bfi(ma, a, pad4);
+                    b = bfi(mb, b, pad4);
+                }
+                const unsigned lo = __builtin_amdgcn_perm(b, a, REV ? 0x06020703u : 0x05010400u);
+                const unsigned hi = __builtin_amdgcn_perm(b, a, REV ? 0x04000501u : 0x07030602u);
+                lq = ((unsigned long long)hi << 32) | lo;
+            };
+            auto head_letters = [&](int c, int j) -> unsigned {   // column c of the head lane = pair j of the block; j is wave-uniform
+                if (LETTER_BLOCKS && LETTER_QUEUE) { const unsigned v = (unsigned)lq; lq >>= 16; return v; }
+                if (LETTER_BLOCKS) return (unsigned)(lq >> (16 * j));   // (plus bits nobody reads)
+                const unsigned sh = (unsigned)(REV ? 3 - j : j) * 8u;
                 const unsigned la0 = __builtin_amdgcn_ubfe(wA, sh, 8u);
                 const unsigned lb0 = __builtin_amdgcn_ubfe(wB, sh, 8u);
                 return (c < colsA ? la0 : pad_letter) | ((c < colsB ? lb0 : pad_letter) << 8);
             };
-            if (PF) {
-                let = from_lane_above(head_letters(0, 0), let);
-                load_rows(let, pav_next, pbv_next);
-            }
+            letter_block(0);
+            let = from_lane_above(head_letters(0, 0), let);
+            if (PF) load_rows(let, pav_next, pbv_next);
 
-            // blocks of four steps, one dword of letters per target and block.  PF: step s hands on the letters of column
+            // blocks of four steps, one dword of letters per target and block.  Step s hands on the letters of column
             // s + 1, so a block is the steps 4k - 1 .. 4k + 2 (the first one the steps 0 .. 2).
-            // Invariant: in block s0 = 4k - 1 (PF) / 4k (not PF), wA / wB hold the k-th letter word, and step j of the block
+            // Invariant: in block s0 = 4k - 1, wA / wB hold the k-th letter word (lq its four pairs), and step j of the block
             // fetches column 4k + j = byte j of it (reverse: byte 3 - j).
-            for (int s0 = PF ? -1 : 0; s0 < nsteps; s0 += 4) {
+            for (int s0 = -1; s0 < nsteps; s0 += 4) {
+            if (MULTI && s0 > 0 && ((s0 + 1) & 15) == 0) {   // every fourth block (s0 = 16 m - 1): stretch m of the boundary row
+                bnd = bnd_next;
+                if (has_above) bnd_next = boundary16(((s0 + 1) >> 4) + 1);
+            }
             const int jn = min(4, nsteps - s0);
 #pragma nounroll
-            for (int j = PF && s0 < 0 ? 1 : 0; j < jn; ++j) {
+            for (int j = s0 < 0 ? 1 : 0; j < jn; ++j) {
                 const int s = s0 + j;
                 // ---- inputs of this step: from the lane above, or the tile boundary for the head lane ----
-                unsigned head_let = 0;
-                if (!PF) head_let = head_letters(s, j);
-                const unsigned Hup = from_lane_above(up[0].x, out_H);
-                unsigned f = from_lane_above(up[0].y, out_F);
-                if (!PF) let = from_lane_above(head_let, let);
-                if (has_above) {
-#pragma unroll
-                    for (int k = 0; k + 1 < UPD; ++k) up[k] = up[k + 1];
-                    int c = s + UPD; if (c > ncols - 1) c = ncols - 1; if (c < 0) c = 0;
-                    up[UPD - 1] = scr_in[c];
+                // Lane 15 works on column s - 15, which lies inside [0, ncols) from step 15 to the last one: what it handed off
+                // in the step before is stored here, under a scalar test - the lane mask is the same in every step, and the
+                // address is the line's (wave-uniform) plus a fixed lane offset.  (The last column: behind the loop.)
+                if (has_below && s >= GROUP) {
+                    if (g == GROUP - 1) (scr_out + (s - GROUP))[scr_grp] = make_uint2(out_H, out_F);
+                }
+                const unsigned Hup = MULTI ? from_lane_above(bnd.x, out_H) : from_lane_above_or_zero(out_H);
+                unsigned f = MULTI ? from_lane_above(bnd.y, out_F) : from_lane_above_or_zero(out_F);
+                if (MULTI) {
+                    // the live stretch moves up one lane (row_ror:15)
+                    bnd.x = __builtin_amdgcn_update_dpp(bnd.x, bnd.x, 0x12F, 0xF, 0xF, false);
+                    bnd.y = __builtin_amdgcn_update_dpp(bnd.y, bnd.y, 0x12F, 0xF, 0xF, false);
                 }
                 unsigned pav[ND], pbv[ND];
                 if (PF) {
@@ -431,14 +490,14 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                 // A packed op that reads the result of the packed op right in front of it costs a wait state (s_nop).  A row
                 // of phase 2 is six ops, three of them the chain h -> t -> f'; with the other three between the links
                 // (h, f - ge, t, cmax, f', E[r]) no op reads its predecessor.  Left alone, the compiler sinks all R updates of
-                // E (in the multi-tile bodies the cmax chain too) out of the rows, past the `nm != vmax` branch (past the
-                // boundary store), into a block of their own: five ops per row and a wait state in each, 1.75 R + 2 per
-                // column, one issue slot in seven.  SW_KEEP_IN_ROW is an EMPTY asm on the value: it emits nothing (so the
+                // E out of the rows, past the `nm != vmax` branch, into a block of their own: five ops per row and a wait state
+                // in each, 1.75 R + 2 per column, one issue slot in seven.  SW_KEEP_IN_ROW is an EMPTY asm on the value: it emits nothing (so the
                 // hazard recognizer still sees real neighbours), but the update has to be done where the row is.  What was
                 // tried and does not work on this toolchain: an asm per op or two-operand asms that chain the ops (the
                 // recognizer pads around every asm boundary: 44 -> 73 and -> 97 wait states at R = 24),
-                // __builtin_amdgcn_sched_barrier after each row (no effect: the sinking happens before scheduling), taking
-                // `nm` in front of the boundary store instead of the anchor on cmax (49 instead of 2).  If a later compiler
+                // __builtin_amdgcn_sched_barrier after each row (no effect: the sinking happens before scheduling), an
+                // anchor on cmax as well (the multi-tile bodies had one while their boundary store stood behind phase 2; with the
+                // store at the top of the step it puts `t` right in front of `f'` in every second row from R = 17 on).  If a later compiler
                 // stops honouring the anchor (tests/test_sw_isa_audit.py notices), the structural alternatives are: rotate
                 // the body so that the `nm != vmax` bookkeeping of column s runs at the top of step s + 1 (Hp[] and col are
                 // still there; the tail of the step is then straight-line code with no join block to sink into), or fold
@@ -456,17 +515,14 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                     pre[r] = pk_max_s(pk_add_sat(r == 0 ? hd : Hp[r - 1], P), E[r]);
                     es[r] = pk_sub_sat_u(E[r], ge2);
                 }
-                if (PF) {   // the next column's letters and profile rows
-                    let = from_lane_above(head_letters(s + 1, j), let);
-                    load_rows(let, pav_next, pbv_next);
-                }
+                let = from_lane_above(head_letters(s + 1, j), let);   // the next column's letters (PF: and profile rows)
+                if (PF) load_rows(let, pav_next, pbv_next);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const unsigned h = pk_max_s(pre[r], f);
                     const unsigned fs = pk_sub_sat_u(f, ge2);
                     const unsigned t = pk_sub_sat_u(h, go2);
                     cmax = pk_max_u(cmax, h);
-                    if (MULTI) SW_KEEP_IN_ROW(cmax);
                     f = pk_max_u(fs, t);
                     E[r] = pk_max_u(es[r], t);
                     SW_KEEP_IN_ROW(E[r]);
@@ -476,7 +532,6 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                 out_F = f;
 
                 const int col = s - g;
-                if (has_below && g == GROUP - 1 && col >= 0 && col < ncols) scr_out[col] = make_uint2(out_H, out_F);
 
                 // ---- running maximum / column / snapshot (rarely taken once the scores have grown) ----
                 const unsigned nm = pk_max_u(vmax, cmax);
@@ -511,10 +566,12 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             }
             {   // the next four columns' letters; the load after that is in flight for four steps
                 wA = wA_next; wB = wB_next;
-                const int k = ((s0 + (PF ? 1 : 0)) >> 2) + 2;
+                const int k = ((s0 + 1) >> 2) + 2;
                 wA_next = letters4(pA, endA, k); wB_next = letters4(pB, endB, k);
+                letter_block(k - 1);
             }
             }
+            if (has_below && ncols > 0 && g == GROUP - 1) (scr_out + (ncols - 1))[scr_grp] = make_uint2(out_H, out_F);
 
             // ---- fold this tile's lanes into the pair's running best (tie rules in the key order) ----
             unsigned rowA_first = rev_rowA, rowB_first = rev_rowB;

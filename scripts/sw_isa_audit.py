@@ -120,7 +120,8 @@ def walk_column(lines, labels, head):
             if kind == "s_cbranch_execz" and tl >= 0 and len(path) >= 3 and path[-2].startswith("s_and_saveexec"):
                 # the rare maximum branch: exec mask straight from the compare of the new maximum with the old
                 prev = [p for p in path[-5:-2] if not p.startswith("s_nop")]
-                if prev and prev[-1].startswith("v_cmp_ne_u32") and "vcc" in path[-2]:
+                mask = prev[-1].split()[1].rstrip(",") if prev and prev[-1].startswith("v_cmp_ne_u32") else None
+                if mask and path[-2].split()[-1] == mask:      # (vcc, or the SGPR pair the compare wrote)
                     k = i + 1   # size of the skipped block: up to the join label or the branch that leaves it
                     while k < len(lines) and k != tl and not lines[k].startswith(".Lfunc_end"):
                         if is_instr(lines[k]):
