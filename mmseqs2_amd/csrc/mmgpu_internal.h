@@ -164,6 +164,14 @@ constexpr int SW_GROUPS = MMGPU_SW_GROUPS;
 static_assert(SW_GROUPS == 3 || SW_GROUPS == 4, "three or four kernel groups");
 int sw_shape_group(uint32_t shape);
 hipError_t launch_sw(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream);
+// Build knob for A/B measurements: MMGPU_SW_HALF=0 keeps every batch on the int16 kernels of sw_kernel.hip.  1 (default): the
+// single-tile groups of an eligible batch run sw_half_kernel.hip's kernels, whose forward scan is packed f16 with an int16 re-run of
+// the pairs that score past SW_HALF_LIMIT (sw_body.h).  launch_sw_half launches the f16 twin of a group's kernel if there is one.
+#ifndef MMGPU_SW_HALF
+#define MMGPU_SW_HALF 1
+#endif
+bool launch_sw_half(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream);
+void warm_sw_half();
 
 // LDS of an alignment workgroup: a header (the reverse pass's packed live hits and the chunk counter) followed by query profiles,
 // one per tile held.  Host (the launch's LDS size) and kernel (which jobs keep all their tiles) use the functions below: both sides

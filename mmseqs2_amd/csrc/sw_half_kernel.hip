@@ -1,0 +1,105 @@
+// Single-tile Smith-Waterman with the forward scan in packed f16 (gfx950: v_pk_maximum3_f16), the twins of sw_kernel<0..2, BOTH>.
+//
+// The forward scan of a pair runs in f16 first: 8.5 packed ops per row of two cells instead of the 10 of the int16 scan
+// (sw_body.h, at SW_HALF_LIMIT, has the recurrence and the proof that a score of at most SW_HALF_LIMIT = 1792 is the int16
+// score, end position and all).  A pair whose f16 maximum exceeds the limit is marked in its result record; the workgroup that
+// found it then builds the int16 profile and runs the int16 forward scan over its marked pairs, packed to the front.  The
+// reverse scan follows as in sw_kernel.hip, in int16, over every pair that wants one.  One launch, no host round trip, the same
+// SwJob: which kernel a batch gets is launch_sw's decision (sw_kernel.hip, sw_half_eligible).
+//
+// Forward-only kernels (BOTH = false): the f16 body with its int16 re-run beside it needs more registers than the int16 body
+// alone, and these kernels sit at the edge of a wavefront each (profiles/sw_half_isa_audit.txt).  launch_sw_half serves a
+// forward-only group only where the f16 kernel keeps its twin's wavefronts without scratch - SW_HALF_FORWARD_ONLY below; the
+// other groups stay with sw_kernel<G, false>.
+#include "mmgpu_internal.h"
+#include "pf_device.h"
+#include "sw_body.h"
+
+namespace mmgpu {
+
+namespace {
+
+template <int R, bool BOTH>
+__device__ __forceinline__ void sw_half_passes(const SwLaunch &L, const SwJob &job) {
+    if constexpr (R <= SW_MAX_R) {
+        constexpr bool PF = MMGPU_SW_PREFETCH && (BOTH || R <= 24);   // as sw_passes
+        sw_body<R, false, false, PF, true, false>(L, job);
+        // the results and marks of this job, written by other waves of the workgroup; and every wave is done with the f16 profile
+        __threadfence_block();
+        __syncthreads();
+        if (sw_half_any_marked()) {   // workgroup-uniform
+            sw_body<R, false, false, PF, false, true>(L, job);
+            __threadfence_block();
+            __syncthreads();
+        }
+        if constexpr (BOTH) sw_body<R, false, true, PF>(L, job);
+    }
+}
+
+// which forward-only groups have an f16 kernel (the others: launch_sw_half declines, launch_sw stays with int16)
+constexpr bool SW_HALF_FORWARD_ONLY[3] = {false, false, false};
+
+template <int G, bool BOTH>
+__global__ __launch_bounds__(WAVES * 64)
+__attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_SW_WAVES_G0F)
+                                           : (G == 1 ? (BOTH ? MMGPU_SW_WAVES_G1B : MMGPU_SW_WAVES_G1F) : SW_MIN_WAVES),
+                                   G == 1 && BOTH ? MMGPU_SW_WAVES_G1B : 8))) void sw_half_kernel(SwLaunch L) {   // (sw_kernel's floors)
+    SwJob job = L.jobs[blockIdx.x];
+    if (L.q_hit_count) {   // fused prefilter -> align hand-over: the list length of the query is only known on the device
+        const uint32_t lim = job.query * L.hit_stride + L.q_hit_count[job.query];
+        job.hit_end = job.hit_end < lim ? job.hit_end : lim;
+        if (job.hit_end <= job.hit_begin) return;
+    }
+#define MMGPU_SW_SINGLE(R) case (R) - 1: sw_half_passes<R, BOTH>(L, job); break;
+    if constexpr (G == 0) {
+        switch (job.shape & 0xFFu) {   // workgroup-uniform
+            MMGPU_SW_SINGLE(1) MMGPU_SW_SINGLE(2) MMGPU_SW_SINGLE(3) MMGPU_SW_SINGLE(4) MMGPU_SW_SINGLE(5) MMGPU_SW_SINGLE(6)
+            MMGPU_SW_SINGLE(7) MMGPU_SW_SINGLE(8) MMGPU_SW_SINGLE(9) MMGPU_SW_SINGLE(10) MMGPU_SW_SINGLE(11) MMGPU_SW_SINGLE(12)
+            default: break;
+        }
+    } else if constexpr (G == 1) {
+        switch (job.shape & 0xFFu) {
+            MMGPU_SW_SINGLE(13) MMGPU_SW_SINGLE(14) MMGPU_SW_SINGLE(15) MMGPU_SW_SINGLE(16) MMGPU_SW_SINGLE(17) MMGPU_SW_SINGLE(18)
+            MMGPU_SW_SINGLE(19) MMGPU_SW_SINGLE(20) MMGPU_SW_SINGLE(21) MMGPU_SW_SINGLE(22) MMGPU_SW_SINGLE(23) MMGPU_SW_SINGLE(24)
+            default: break;
+        }
+    } else {
+        switch (job.shape & 0xFFu) {
+            MMGPU_SW_SINGLE(25) MMGPU_SW_SINGLE(26) MMGPU_SW_SINGLE(27) MMGPU_SW_SINGLE(28) MMGPU_SW_SINGLE(29) MMGPU_SW_SINGLE(30)
+            MMGPU_SW_SINGLE(31) MMGPU_SW_SINGLE(32)
+            default: break;
+        }
+    }
+#undef MMGPU_SW_SINGLE
+}
+
+// the forward-only kernels no launch uses, for the audit that decides SW_HALF_FORWARD_ONLY (scripts/sw_isa_audit.py -D ...)
+#ifdef MMGPU_SW_HALF_AUDIT_FORWARD
+template __global__ void sw_half_kernel<0, false>(SwLaunch);
+template __global__ void sw_half_kernel<1, false>(SwLaunch);
+template __global__ void sw_half_kernel<2, false>(SwLaunch);
+#endif
+
+}  // namespace
+
+// The f16 twin of launch_sw's kernel for this group, if there is one: false = the caller launches the int16 kernel.
+// Group 2 is single-tile only where the multi-tile jobs have a group of their own (SW_GROUPS == 4).
+bool launch_sw_half(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream) {
+    if (group < 0 || group > 2 || (group == 2 && SW_GROUPS != 4)) return false;
+    if (!both_passes && !SW_HALF_FORWARD_ONLY[group]) return false;
+    dim3 grid(L.n_jobs), block(WAVES * 64);
+    const size_t lds = lds_bytes + SW_LDS_HEADER;
+    switch (group) {
+        case 0: hipLaunchKernelGGL((sw_half_kernel<0, true>), grid, block, lds, stream, L); break;
+        case 1: hipLaunchKernelGGL((sw_half_kernel<1, true>), grid, block, lds, stream, L); break;
+        default: hipLaunchKernelGGL((sw_half_kernel<2, true>), grid, block, lds, stream, L); break;
+    }
+    return true;
+}
+
+void warm_sw_half() {
+    hipFuncAttributes a;
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_half_kernel<0, true>));
+}
+
+}  // namespace mmgpu

@@ -6,9 +6,11 @@
 //     H = max(sat16(Hdiag + P), E, F);  E' = max(E - ge, H - go);  F' = max(F - ge, H - go)   (E, F >= 0)
 //     t_end = first column in which the running maximum reaches its final value (:232-248, :414-425)
 //     q_end = smallest query index holding that maximum in that column           (:262-271, :438-447)
-// The reference runs a uint8 pass and re-runs in int16 on overflow; here everything is int16 (exact for
+// The reference runs a uint8 pass and re-runs in int16 on overflow; the kernels of this file compute in int16 (exact for
 // every score the uint8 pass can represent, and saturating at 32767 exactly like sw_sse2_word), and the
 // `word` flag reports which pass the reference would have ended in (score + bias >= 255, :238-242).
+// The single-tile groups have twins in sw_half_kernel.hip whose forward scan runs in packed f16 first and in int16 only for
+// the pairs that score past 1792 - same results; launch_sw (below) picks.  The body of both is sw_body.h.
 //
 // How it is mapped to CDNA4 (this is not the striped/lazy-F formulation of the CPU code):
 //  * integer DP => VALU, no MFMA.  All cell arithmetic is packed 2 x int16 (v_pk_add_i16 clamp,
@@ -44,639 +46,12 @@
 // is bound by VALU issue, not by HBM.
 #include "mmgpu_internal.h"
 #include "pf_device.h"
+#include "sw_body.h"   // sw_body, build_profile, sw_passes and the helpers: shared with sw_half_kernel.hip
 
 namespace mmgpu {
 
 namespace {
 
-constexpr int GROUP = 16;            // lanes per target pair (one DPP row)
-constexpr int WAVES = 4;             // waves per workgroup
-constexpr int GROUPS_PER_WAVE = 64 / GROUP;
-constexpr int HITS_PER_WAVE = 2 * GROUPS_PER_WAVE;   // two targets per group (lo/hi halves)
-constexpr unsigned NEG2 = 0x80008000u;               // packed (-32768, -32768)
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk_add_sat(unsigned a, unsigned b) {   // v_pk_add_i16 ... clamp
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_add_sat(__builtin_bit_cast(s16x2, a),
-                                                                      __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ unsigned pk_max_s(unsigned a, unsigned b) {     // v_pk_max_i16
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a),
-                                                                  __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ unsigned pk_max_u(unsigned a, unsigned b) {     // v_pk_max_u16
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a),
-                                                                  __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ unsigned pk_sub_sat_u(unsigned a, unsigned b) { // v_pk_sub_u16 ... clamp
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a),
-                                                                      __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ unsigned bfi(unsigned mask, unsigned a, unsigned b) {   // v_bfi_b32
-    return (a & mask) | (b & ~mask);
-}
-// value of the lane one below inside the 16-lane row; lane 0 of each row keeps `head`
-__device__ __forceinline__ unsigned from_lane_above(unsigned head, unsigned v) {
-    return __builtin_amdgcn_update_dpp(head, v, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
-}
-// ... lane 0 of each row gets 0 (bound_ctrl): no register has to hold the zero
-__device__ __forceinline__ unsigned from_lane_above_or_zero(unsigned v) {
-    return __builtin_amdgcn_update_dpp(0u, v, 0x111 /*row_shr:1*/, 0xF, 0xF, true);
-}
-
-// Build knob for A/B measurements (no test builds with 0; the default is what the suite and the bench run):
-// MMGPU_SW_PREFETCH=0 fetches the profile rows in the column that uses them, as before the prefetch.
-#ifndef MMGPU_SW_PREFETCH
-#define MMGPU_SW_PREFETCH 1
-#endif
-// Empty asm that takes a value in and out of a VGPR: the instruction producing it has to stand where the source has it.
-// Used on the E update in phase 2 of the column loop - see there.
-#define SW_KEEP_IN_ROW(x) asm volatile("" : "+v"(x))
-
-// (lane_stride_bytes and the size of a tile's profile: mmgpu_internal.h, shared with the host's LDS sizing)
-template <int R>
-struct Tile {
-    static constexpr int ROWS = GROUP * R;
-    static constexpr int LANE_STRIDE = lane_stride_bytes(R);
-    static constexpr int ROW_STRIDE = GROUP * LANE_STRIDE;   // bytes per letter
-};
-static_assert(GROUP == 16, "sw_profile_bytes and sw_tiles (mmgpu_internal.h) assume 16-lane groups");
-
-// Build P[letter][row] for rows [tile_base, tile_base + ROWS) of the query (or of the reversed query).
-// Rows past the query end and the extra letter `alphabet` (padding column of a finished target) are
-// -32768, which keeps H at max(E, F) there and can never raise a running maximum.
-template <int R, bool REV>
-__device__ __forceinline__ void build_profile(unsigned char *lds, const uint8_t *q, const int8_t *cb, int qlen,
-                                              int tile_base, const int8_t *mat, int alphabet, const int8_t *prof) {
-    using T = Tile<R>;
-    const int total = (alphabet + 1) * T::ROWS;
-    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
-        const int letter = idx / T::ROWS;
-        const int row = idx - letter * T::ROWS;
-        const int rg = tile_base + row;
-        short v = (short)-32768;
-        if (letter < alphabet && rg < qlen) {
-            const int qi = REV ? (qlen - 1 - rg) : rg;
-            // profile query: the score row of the letter (createQueryProfile<PROFILE>, StripedSmithWaterman.cpp:773-776)
-            v = prof ? (short)prof[letter * qlen + qi] : (short)((int)mat[letter * alphabet + q[qi]] + (int)cb[qi]);
-        }
-        const int lane = row / R, r = row - lane * R;
-        *reinterpret_cast<short *>(lds + letter * T::ROW_STRIDE + lane * T::LANE_STRIDE + r * 2) = v;
-    }
-}
-
-// Does the pair whose forward result sits in out[slot] get a reverse scan?  ssw_align_private scans backwards for the start
-// position when the score passes the E-value gate (StripedSmithWaterman.cpp:857-863) - and, in the reference's alignment modes with a
-// start position, only for hits of the uint8 pass: an int16-range hit (word == 1) takes its start from the block aligner (:865-882),
-// falling back to the reverse scan when that declines (rev_mode 2: the caller names those pairs afterwards).
-__device__ __forceinline__ bool sw_rev_wanted(const SwLaunch &L, uint32_t slot, int min_start) {
-    const mmgpu_sw_hit &f = L.out[slot];
-    const int s = f.score;
-    if (L.rev_mode == 2) return s > 0 && L.rev_force[slot] != 0;
-    return s > 0 && s >= min_start && !(L.rev_mode == 1 && f.word != 0);
-}
-
-constexpr int SW_REV_JOB_HITS = 1024;   // most hits a reverse-scan job may hold (mmgpu_internal.h: SW_REV_JOB_MAX)
-static_assert(SW_REV_JOB_HITS == SW_REV_JOB_MAX, "host and kernel disagree on the reverse job size");
-static_assert(SW_LDS_HEADER == SW_REV_JOB_HITS * 2 + 64, "the header holds the live hits and the scheduling words");
-
-// PF: the profile rows of a column are fetched one column ahead (see the column loop)
-template <int R, bool MULTI, bool REV, bool PF>
-__device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
-    using T = Tile<R>;
-    // dynamic LDS: a 1 KB header (job-local scheduling state, below) followed by the query profile of the tile
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-    uint16_t *live = reinterpret_cast<uint16_t *>(lds_all);                  // [SW_REV_JOB_HITS] packed live hits (reverse pass)
-    uint32_t *live_wave = reinterpret_cast<uint32_t *>(lds_all + SW_REV_JOB_HITS * 2);       // [WAVES]
-    uint32_t *next_chunk = reinterpret_cast<uint32_t *>(lds_all + SW_REV_JOB_HITS * 2 + 16); // next 8-hit chunk to hand to a wave
-    unsigned char *lds = lds_all + SW_LDS_HEADER;
-    // A multi-tile job is one long dependent chain (tiles x columns) however few targets it holds, and the batch ends
-    // with the longest of them: those waves take the issue slots first, the short jobs sharing the SIMD fill the gaps.
-    if (MULTI) __builtin_amdgcn_s_setprio(3);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = lane & (GROUP - 1);
-    const int grp = lane / GROUP;
-
-    const uint32_t qbeg = L.q_off[job.query];
-    const int qlen = (int)(L.q_off[job.query + 1] - qbeg);
-    const uint8_t *q = L.q_res + qbeg;
-    const int8_t *cb = L.q_cb + qbeg;
-    const int qbias = L.q_bias[job.query];
-    const int8_t *prof = nullptr;
-    if (L.q_prof_off) {
-        const uint32_t po = L.q_prof_off[job.query];
-        if (po != 0xFFFFFFFFu) prof = L.q_prof + po;
-    }
-    const int n_tiles = MULTI ? (int)sw_tiles((uint32_t)qlen, R) : 1;
-    // A multi-tile job whose tiles all fit the LDS the host granted by the same rule keeps every tile's profile: built once, in
-    // front of the chunk loop, which then runs without a barrier - its wavefronts take chunks as they finish, like the single-tile
-    // bodies.  The other jobs rebuild the one profile they have room for per tile and round.  (workgroup-uniform)
-    const uint32_t tile_bytes = sw_profile_bytes(R, L.alphabet);
-    const bool resident = MULTI && sw_multi_resident((uint32_t)n_tiles, R, L.alphabet, L.resident_lds);
-    const bool dynamic = !MULTI || resident;   // chunks handed out through next_chunk, no barrier in the loop
-    auto build_all_tiles = [&]() {
-        for (int tile = 0; tile < n_tiles; ++tile)
-            build_profile<R, REV>(lds + (uint32_t)tile * tile_bytes, q, cb, qlen, tile * T::ROWS, L.mat, L.alphabet, prof);
-        __syncthreads();
-    };
-
-    const unsigned go2 = (unsigned)L.gap_open * 0x10001u;
-    const unsigned ge2 = (unsigned)L.gap_extend * 0x10001u;
-    const unsigned pad_letter = (unsigned)L.alphabet;
-
-    if (threadIdx.x == 0) *next_chunk = 0;
-    if (!MULTI && !REV) {
-        build_profile<R, REV>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
-        __syncthreads();
-    }
-    if (MULTI && !REV && resident) build_all_tiles();
-
-    uint32_t n_hits = job.hit_end - job.hit_begin;
-    // Reverse pass: only the pairs whose forward score reaches the query's start-score threshold are scanned
-    // (ssw_align_private, StripedSmithWaterman.cpp:857-863) - typically one hit in six, scattered over the
-    // length-sorted list.  They are packed to the front (order kept), so that the waves run full instead of every
-    // wave waiting for its one or two live targets.
-    if (REV) {
-        const int min_start = L.q_minstart[job.query];
-        uint32_t total = 0;
-        for (uint32_t base = 0; base < n_hits; base += WAVES * 64) {   // a job of the BOTH kernels holds at most 256 hits: one round
-            const uint32_t idx = base + threadIdx.x;
-            bool pass = false;
-            if (idx < n_hits) pass = sw_rev_wanted(L, L.hit_out[job.hit_begin + idx], min_start);
-            const unsigned long long bal = __ballot(pass);
-            if (lane == 0) live_wave[wave] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            uint32_t before = 0, round_total = 0;
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) {
-                const uint32_t c = live_wave[w];
-                before += w < wave ? c : 0u;
-                round_total += c;
-            }
-            if (pass) live[total + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)idx;
-            total += round_total;
-            __syncthreads();
-        }
-        n_hits = total;
-        if (n_hits == 0) return;      // (workgroup-uniform) no pair of this job needs a start position: no profile either
-        if (!MULTI) {
-            build_profile<R, REV>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
-            __syncthreads();
-        }
-        if (MULTI && resident) build_all_tiles();
-    }
-    const uint32_t n_iter = (n_hits + WAVES * HITS_PER_WAVE - 1) / (WAVES * HITS_PER_WAVE);
-
-    for (uint32_t it = 0; dynamic || it < n_iter; ++it) {
-        // Single-tile and resident jobs: a wave takes the next chunk of 8 hits when it is done with its last one (the hits
-        // are sorted by length, so fixed wave <-> chunk striping would give wave 0 the longest chunk of every round).
-        // The other multi-tile jobs rebuild the profile per tile with all threads, so their waves stay in step.
-        uint32_t chunk = it * WAVES + wave;
-        if (dynamic) {
-            if (lane == 0) chunk = atomicAdd(next_chunk, 1u);
-            chunk = __builtin_amdgcn_readfirstlane(chunk);
-        }
-        const uint32_t slot0 = chunk * HITS_PER_WAVE;
-        if (dynamic && slot0 >= n_hits) break;   // wave-uniform; the jobs in step keep every wave in the barrier loop
-
-        // ---- the two targets of this group ------------------------------------------------------
-        const uint32_t sA = slot0 + grp * 2, sB = sA + 1;
-        const bool vA = sA < n_hits, vB = sB < n_hits;
-        const uint32_t hA = job.hit_begin + (REV ? (uint32_t)live[vA ? sA : 0] : sA);
-        const uint32_t hB = job.hit_begin + (REV ? (uint32_t)live[vB ? sB : 0] : sB);
-        const uint32_t tA = vA ? L.hit_target[hA] : 0u, tB = vB ? L.hit_target[hB] : 0u;
-        const uint8_t *pA = L.t_res + (size_t)L.t_off4[tA] * 4;
-        const uint8_t *pB = L.t_res + (size_t)L.t_off4[tB] * 4;
-        int colsA = vA ? (int)L.t_len[tA] : 0, colsB = vB ? (int)L.t_len[tB] : 0;
-        int r0A = 0, r0B = 0;       // REV: first live row of the reversed query
-        int endA = 0, endB = 0;     // REV: forward t_end
-        unsigned rev_target = 0xFFFFFFFFu;
-        if (REV) {
-            // reverse scan over q[0..q_end] x t[0..t_end], both walked backwards (:1143-1175)
-            // Lanes without a live pair must not take positions from a result slot: slot 0 may still be unwritten
-            // (another workgroup's forward pass), and an arbitrary t_end there becomes a wild target address below.
-            mmgpu_sw_hit fa, fb;
-            fa.score = 0; fa.q_end = 0; fa.t_end = 0;
-            fb = fa;
-            if (vA) fa = L.out[L.hit_out[hA]];
-            if (vB) fb = L.out[L.hit_out[hB]];
-            // (every packed hit passed sw_rev_wanted above)
-            colsA = vA ? fa.t_end + 1 : 0;
-            colsB = vB ? fb.t_end + 1 : 0;
-            endA = colsA > 0 ? fa.t_end : 0;
-            endB = colsB > 0 ? fb.t_end : 0;
-            r0A = colsA > 0 ? qlen - 1 - fa.q_end : 0;
-            r0B = colsB > 0 ? qlen - 1 - fb.q_end : 0;
-            // the score the reverse scan has to reach (terminate = r.score1, :1159-1175); 0xFFFF can never be reached
-            rev_target = (colsA > 0 ? (unsigned)fa.score & 0xFFFFu : 0xFFFFu) | ((colsB > 0 ? (unsigned)fb.score & 0xFFFFu : 0xFFFFu) << 16);
-        }
-        int ncols = colsA > colsB ? colsA : colsB;
-        ncols = max(ncols, __shfl_xor(ncols, 16));
-        ncols = max(ncols, __shfl_xor(ncols, 32));
-        ncols = __builtin_amdgcn_readfirstlane(ncols);
-        const int nsteps = ncols + GROUP - 1;
-        // the shortest target of the wavefront (a half without a pair counts as 0 columns): letter blocks that end at or
-        // before it hold no padding column in any group
-        int mincols = colsA < colsB ? colsA : colsB;
-        mincols = min(mincols, __shfl_xor(mincols, 16));
-        mincols = min(mincols, __shfl_xor(mincols, 32));
-        mincols = __builtin_amdgcn_readfirstlane(mincols);
-
-        unsigned long long bestA = 0, bestB = 0;   // (score << 32) | (~col << 16) | ~row, maximised
-
-        // the scratch lines of this wavefront (a wave-uniform address) and where the group's two start in them
-        uint2 *scr = nullptr;
-        unsigned scr_grp = 0;
-        if (MULTI) {
-            scr = L.scratch + (size_t)((job.shape >> 8) * WAVES + wave) * GROUPS_PER_WAVE * 2 * L.scratch_cols;
-            scr_grp = (unsigned)grp * 2u * L.scratch_cols;
-        }
-
-        for (int tile = 0; tile < n_tiles; ++tile) {
-            const int tile_base = tile * T::ROWS;
-            if (MULTI && !resident) {
-                __syncthreads();   // everyone is done reading the previous tile's profile
-                build_profile<R, REV>(lds, q, cb, qlen, tile_base, L.mat, L.alphabet, prof);
-                __syncthreads();
-            }
-            // the profile of this tile: the one there is, or this tile's of the resident ones (no barrier: nobody writes them).
-            // Without the barriers nothing but program order stands between tile t's stores to its scratch line (lane 15 of a
-            // group) and tile t + 1's loads from it (the group's head lane): the hand-over of the boundary row relies on both
-            // being lanes of ONE wavefront, whose vector memory operations on the same addresses complete in order.  A group
-            // spread over two wavefronts would need a fence and a barrier here again.
-            const unsigned char *const lds_tile = MULTI && resident ? lds + (uint32_t)tile * tile_bytes : lds;
-            const uint2 *scr_in = MULTI ? scr + (size_t)((tile + 1) & 1) * L.scratch_cols : nullptr;
-            uint2 *scr_out = MULTI ? scr + (size_t)(tile & 1) * L.scratch_cols : nullptr;
-            const bool has_above = MULTI && tile > 0;
-            const bool has_below = MULTI && tile + 1 < n_tiles;
-
-            // forward: snap[] = the strip's H values in the column where the running maximum last rose (q_end);
-            // reverse: rmask[] = rows of the reversed query that lie inside q[0..q_end] - the reverse scan needs no
-            // snapshot, it ends in the first column that reaches the forward score (see below), so the two bodies of a
-            // kernel need the same number of registers and the forward scan keeps its own occupancy
-            unsigned Hp[R], E[R], aux[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) { Hp[r] = 0; E[r] = 0; aux[r] = 0; }
-            if (REV) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int rg = tile_base + g * R + r;
-                    aux[r] = (rg >= r0A ? 0xFFFFu : 0u) | (rg >= r0B ? 0xFFFF0000u : 0u);
-                }
-            }
-            unsigned vmax = 0, bestcol = 0xFFFFFFFFu;
-            unsigned rev_rowA = 0, rev_rowB = 0;   // REV: first row holding the forward score in the column that reached it
-            unsigned Hup_prev = 0;
-            unsigned out_H = 0, out_F = 0;
-
-            // Four columns' letters per dword load (every lane of the group loads the same word).  Forward: targets
-            // start 4-byte aligned and the residue buffer ends with max_len + 64 bytes of slack (mmgpu_load_targets), so
-            // no clamping is needed: columns past a target's end are replaced by the padding letter below.  Reverse:
-            // column c is byte t[t_end - c], block k = the (unaligned) word at t_end - 3 - 4k read from its top byte down;
-            // words wholly before the target are clamped to offset -3 (the buffer starts with 64 bytes of padding).
-            // One v_bfe per target and column instead of an address computation and a byte load: 16-18 fewer
-            // instructions per column (R = 12: 194 -> 177).
-            auto letters4 = [&](const uint8_t *p, int end, int k) -> unsigned {
-                if (!REV) return reinterpret_cast<const unsigned *>(p)[k];
-                int o = end - 3 - 4 * k;
-                o = o < -3 ? -3 : o;
-                unsigned w;
-                __builtin_memcpy(&w, p + o, 4);
-                return w;
-            };
-            unsigned wA = letters4(pA, endA, 0), wB = letters4(pB, endB, 0);
-            unsigned wA_next = letters4(pA, endA, 1), wB_next = letters4(pB, endB, 1);
-            // Boundary row of the tile above, 16 columns (a stretch) at a time: the lanes of the group load one column each -
-            // one coalesced load per 16 steps, issued a stretch ahead - and the live stretch is rotated by one lane per step,
-            // so that the head lane holds column s at step s.  A stretch changes where a block of four steps begins (below):
-            // stretch 0 is the columns 0 .. 15, of which the steps 0 .. 14 use 15, stretch m >= 1 the columns 16 m - 1 .. 16 m + 14.
-            // The index is clamped to the last column of the wavefront: the steps past a group's (or the wavefront's) end read
-            // that column again, as harmless as it was.
-            // Boundary row for the tile below: lane 15 stores its hand-off in every step from its first column on (see there).
-            uint2 bnd = make_uint2(0, 0), bnd_next = make_uint2(0, 0);   // (H, F) of the live stretch and of the one after it
-            auto boundary16 = [&](int m) -> uint2 {   // m is wave-uniform
-                const int last = ncols - 1 < 0 ? 0 : ncols - 1;
-                return scr_in[scr_grp + (unsigned)min(16 * m + g - (m > 0 ? 1 : 0), last)];
-            };
-            if (has_above) {
-                bnd = boundary16(0);
-                bnd_next = boundary16(1);
-            }
-
-            // R scores per target as ND = ceil(R / 2) packed dwords (odd R: the high half of the last one is row padding
-            // nobody selects): ds_read_b128 for whole 16-byte slots, b64 / b32 for the tail
-            constexpr int ND = (R + 1) / 2;
-            unsigned pav_next[PF ? ND : 1], pbv_next[PF ? ND : 1];   // PF: the rows fetched for the next step
-            auto load_rows = [&](unsigned letters, unsigned *pav, unsigned *pbv) {
-                const unsigned a = letters & 0xFFu, b = (letters >> 8) & 0xFFu;
-                const uint4 *rowA = reinterpret_cast<const uint4 *>(lds_tile + a * T::ROW_STRIDE + g * T::LANE_STRIDE);
-                const uint4 *rowB = reinterpret_cast<const uint4 *>(lds_tile + b * T::ROW_STRIDE + g * T::LANE_STRIDE);
-#pragma unroll
-                for (int k = 0; k < ND / 4; ++k) {
-                    const uint4 pa = rowA[k], pb = rowB[k];
-                    pav[4 * k] = pa.x; pav[4 * k + 1] = pa.y; pav[4 * k + 2] = pa.z; pav[4 * k + 3] = pa.w;
-                    pbv[4 * k] = pb.x; pbv[4 * k + 1] = pb.y; pbv[4 * k + 2] = pb.z; pbv[4 * k + 3] = pb.w;
-                }
-                if constexpr (ND % 4 >= 2) {
-                    const uint2 pa = *reinterpret_cast<const uint2 *>(rowA + ND / 4);
-                    const uint2 pb = *reinterpret_cast<const uint2 *>(rowB + ND / 4);
-                    pav[(ND / 4) * 4] = pa.x; pav[(ND / 4) * 4 + 1] = pa.y;
-                    pbv[(ND / 4) * 4] = pb.x; pbv[(ND / 4) * 4 + 1] = pb.y;
-                }
-                if constexpr (ND % 2 == 1) {
-                    pav[ND - 1] = reinterpret_cast<const unsigned *>(rowA)[ND - 1];
-                    pbv[ND - 1] = reinterpret_cast<const unsigned *>(rowB)[ND - 1];
-                }
-            };
-            // The letters lane g needs in step s + 1 are the letters lane g - 1 holds in step s (the head lane's come from the
-            // letter words): every body hands them on in step s, between the two phases, where the DPP move has the packed ops
-            // of the rows around it - at the top of a column it stood behind the instruction that made the head lane's letters,
-            // and short columns paid wait states for that.  `let` is carried from step to step; the prologue takes column 0.
-            // PF: the profile rows of a column are fetched one column ahead as well: the ds_reads of step s + 1 are issued in
-            // step s behind the hand-off, that is behind the last use of the rows of step s (phase 1) and in front of the
-            // serial chain (phase 2): the LDS round trip is covered by the wavefront's own instructions instead of standing
-            // at the top of every column.  pav / pbv are carried from step to step too; the prologue fetches column 0.
-            // The step after the last one fetches the padding letter's row (s + 1 >= cols), which every tile has: nothing
-            // is read past the profile.  The rows stay in the same registers (the reads stand behind their last use), but
-            // the compiler moves some reads up, which costs 6 - 24 registers per kernel.
-            unsigned let = pad_letter * 0x101u;   // what a lane holds before its first column
-            // The head lane's letters, prepared once per block of four columns: wA / wB are interleaved into the queue
-            // `lq` of four (a | b << 8) pairs in the order the columns consume them (two v_perm_b32), and a column shifts
-            // its pair out (the consumers read the low 16 bits of `let` only).  Columns past a target's end get the padding
-            // letter here, per block and only in the blocks that reach past the wavefront's shortest target (a scalar
-            // branch): the column loop holds no compare and no select for them.
-            // The single-tile bodies of R <= 6 have too few instructions per column to take this form without wait states they
-            // did not have (profiles/sw_isa_audit.txt): forward they select per column as before (LETTER_BLOCKS
-            // false), in reverse the column shifts the queue itself instead of indexing it (LETTER_QUEUE), one instruction more.
-            constexpr bool LETTER_BLOCKS = MULTI || REV || R >= 7;
-            constexpr bool LETTER_QUEUE = !MULTI && R < 7;
-            unsigned long long lq = 0;
-            auto letter_block = [&](int k) {   // block k = columns 4k .. 4k + 3, from wA / wB
-                if (!LETTER_BLOCKS) return;
-                unsigned a = wA, b = wB;
-                if (4 * k + 4 > mincols) {   // wave-uniform
-                    const unsigned pad4 = pad_letter * 0x01010101u;
-                    const int na = min(max(colsA - 4 * k, 0), 4), nb = min(max(colsB - 4 * k, 0), 4);   // live columns of the block
-                    // forward: column 4k + i is byte i; reverse: byte 3 - i
-                    const unsigned ma = REV ? ~(unsigned)(0xFFFFFFFFull >> (8 * na)) : (unsigned)((1ull << (8 * na)) - 1ull);
-                    const unsigned mb = REV ? ~(unsigned)(0xFFFFFFFFull >> (8 * nb)) : (unsigned)((1ull << (8 * nb)) - 1ull);
-                    a = bfi(ma, a, pad4);
-                    b = bfi(mb, b, pad4);
-                }
-                const unsigned lo = __builtin_amdgcn_perm(b, a, REV ? 0x06020703u : 0x05010400u);
-                const unsigned hi = __builtin_amdgcn_perm(b, a, REV ? 0x04000501u : 0x07030602u);
-                lq = ((unsigned long long)hi << 32) | lo;
-            };
-            auto head_letters = [&](int c, int j) -> unsigned {   // column c of the head lane = pair j of the block; j is wave-uniform
-                if (LETTER_BLOCKS && LETTER_QUEUE) { const unsigned v = (unsigned)lq; lq >>= 16; return v; }
-                if (LETTER_BLOCKS) return (unsigned)(lq >> (16 * j));   // (plus bits nobody reads)
-                const unsigned sh = (unsigned)(REV ? 3 - j : j) * 8u;
-                const unsigned la0 = __builtin_amdgcn_ubfe(wA, sh, 8u);
-                const unsigned lb0 = __builtin_amdgcn_ubfe(wB, sh, 8u);
-                return (c < colsA ? la0 : pad_letter) | ((c < colsB ? lb0 : pad_letter) << 8);
-            };
-            letter_block(0);
-            let = from_lane_above(head_letters(0, 0), let);
-            if (PF) load_rows(let, pav_next, pbv_next);
-
-            // blocks of four steps, one dword of letters per target and block.  Step s hands on the letters of column
-            // s + 1, so a block is the steps 4k - 1 .. 4k + 2 (the first one the steps 0 .. 2).
-            // Invariant: in block s0 = 4k - 1, wA / wB hold the k-th letter word (lq its four pairs), and step j of the block
-            // fetches column 4k + j = byte j of it (reverse: byte 3 - j).
-            for (int s0 = -1; s0 < nsteps; s0 += 4) {
-            if (MULTI && s0 > 0 && ((s0 + 1) & 15) == 0) {   // every fourth block (s0 = 16 m - 1): stretch m of the boundary row
-                bnd = bnd_next;
-                if (has_above) bnd_next = boundary16(((s0 + 1) >> 4) + 1);
-            }
-            const int jn = min(4, nsteps - s0);
-#pragma nounroll
-            for (int j = s0 < 0 ? 1 : 0; j < jn; ++j) {
-                const int s = s0 + j;
-                // ---- inputs of this step: from the lane above, or the tile boundary for the head lane ----
-                // Lane 15 works on column s - 15, which lies inside [0, ncols) from step 15 to the last one: what it handed off
-                // in the step before is stored here, under a scalar test - the lane mask is the same in every step, and the
-                // address is the line's (wave-uniform) plus a fixed lane offset.  (The last column: behind the loop.)
-                if (has_below && s >= GROUP) {
-                    if (g == GROUP - 1) (scr_out + (s - GROUP))[scr_grp] = make_uint2(out_H, out_F);
-                }
-                const unsigned Hup = MULTI ? from_lane_above(bnd.x, out_H) : from_lane_above_or_zero(out_H);
-                unsigned f = MULTI ? from_lane_above(bnd.y, out_F) : from_lane_above_or_zero(out_F);
-                if (MULTI) {
-                    // the live stretch moves up one lane (row_ror:15)
-                    bnd.x = __builtin_amdgcn_update_dpp(bnd.x, bnd.x, 0x12F, 0xF, 0xF, false);
-                    bnd.y = __builtin_amdgcn_update_dpp(bnd.y, bnd.y, 0x12F, 0xF, 0xF, false);
-                }
-                unsigned pav[ND], pbv[ND];
-                if (PF) {
-#pragma unroll
-                    for (int k = 0; k < ND; ++k) { pav[k] = pav_next[k]; pbv[k] = pbv_next[k]; }
-                } else {
-                    load_rows(let, pav, pbv);
-                }
-
-                unsigned hd = Hup_prev;
-                Hup_prev = Hup;
-                unsigned cmax = 0;
-                // Phase 1 (no dependencies between rows): everything that only needs the previous column -
-                // diagonal + score, max with E, and E - ge.  Phase 2 is the serial F chain down the strip
-                // (max -> sub -> max per row) with the off-chain ops of the row (f - ge, column maximum, E
-                // update) available to sit behind each dependent VOP3P op.  Compared with the single-loop form
-                // the compiler needs 23 fewer register moves and 10 fewer wait states per column at R = 24
-                // (346 -> 313 instructions).
-                //
-                // A packed op that reads the result of the packed op right in front of it costs a wait state (s_nop).  A row
-                // of phase 2 is six ops, three of them the chain h -> t -> f'; with the other three between the links
-                // (h, f - ge, t, cmax, f', E[r]) no op reads its predecessor.  Left alone, the compiler sinks all R updates of
-                // E out of the rows, past the `nm != vmax` branch, into a block of their own: five ops per row and a wait state
-                // in each, 1.75 R + 2 per column, one issue slot in seven.  SW_KEEP_IN_ROW is an EMPTY asm on the value: it emits nothing (so the
-                // hazard recognizer still sees real neighbours), but the update has to be done where the row is.  What was
-                // tried and does not work on this toolchain: an asm per op or two-operand asms that chain the ops (the
-                // recognizer pads around every asm boundary: 44 -> 73 and -> 97 wait states at R = 24),
-                // __builtin_amdgcn_sched_barrier after each row (no effect: the sinking happens before scheduling), an
-                // anchor on cmax as well (the multi-tile bodies had one while their boundary store stood behind phase 2; with the
-                // store at the top of the step it puts `t` right in front of `f'` in every second row from R = 17 on).  If a later compiler
-                // stops honouring the anchor (tests/test_sw_isa_audit.py notices), the structural alternatives are: rotate
-                // the body so that the `nm != vmax` bookkeeping of column s runs at the top of step s + 1 (Hp[] and col are
-                // still there; the tail of the step is then straight-line code with no join block to sink into), or fold
-                // the E update into the chain's data flow.
-                // The schedule is sensitive to the shape of the source around it: with pav / pbv declared outside the column
-                // loop the multi-tile bodies get a wait state per row back (scripts/sw_isa_audit.py after every change here).
-                unsigned pre[R], es[R];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    // (score of target A's letter, score of target B's letter) for query row r
-                    unsigned P = __builtin_amdgcn_perm(pbv[r / 2], pav[r / 2], (r & 1) ? 0x07060302u : 0x05040100u);
-                    // v_bitop3 (a ? b : c, table 0xCA) as an intrinsic: written as and/or the compiler hoists NEG2 & ~mask
-                    // out of the column loop - R more live registers
-                    if (REV) P = __builtin_amdgcn_bitop3_b32(aux[r], P, NEG2, 0xCA);
-                    pre[r] = pk_max_s(pk_add_sat(r == 0 ? hd : Hp[r - 1], P), E[r]);
-                    es[r] = pk_sub_sat_u(E[r], ge2);
-                }
-                let = from_lane_above(head_letters(s + 1, j), let);   // the next column's letters (PF: and profile rows)
-                if (PF) load_rows(let, pav_next, pbv_next);
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const unsigned h = pk_max_s(pre[r], f);
-                    const unsigned fs = pk_sub_sat_u(f, ge2);
-                    const unsigned t = pk_sub_sat_u(h, go2);
-                    cmax = pk_max_u(cmax, h);
-                    f = pk_max_u(fs, t);
-                    E[r] = pk_max_u(es[r], t);
-                    SW_KEEP_IN_ROW(E[r]);
-                    Hp[r] = h;
-                }
-                out_H = Hp[R - 1];
-                out_F = f;
-
-                const int col = s - g;
-
-                // ---- running maximum / column / snapshot (rarely taken once the scores have grown) ----
-                const unsigned nm = pk_max_u(vmax, cmax);
-                if (nm != vmax) {
-                    const unsigned diff = nm ^ vmax;
-                    if (!REV) {
-                        const unsigned mask = ((diff & 0xFFFFu) ? 0xFFFFu : 0u) | ((diff >> 16) ? 0xFFFF0000u : 0u);
-                        bestcol = bfi(mask, ((unsigned)col & 0xFFFFu) * 0x10001u, bestcol);
-#pragma unroll
-                        for (int r = 0; r < R; ++r) aux[r] = bfi(mask, Hp[r], aux[r]);
-                    } else {
-                        // Reverse scan: nothing in q[0..q_end] x t[0..t_end] scores above the forward score, and the
-                        // reference stops in the first column whose maximum equals it (terminate, :232-248 / :414-425 with
-                        // :1159-1175): the column in which this strip's maximum rises TO that score is the strip's candidate,
-                        // its first row holding it the row - found once per pair, no snapshot of the strip is kept.
-                        const unsigned x = nm ^ rev_target;
-                        const bool hitA = (diff & 0xFFFFu) && !(x & 0xFFFFu), hitB = (diff >> 16) && !(x >> 16);
-                        if (hitA | hitB) {
-                            asm volatile("" ::: "memory");   // a real branch: if-converted, the row search below runs in every column
-                            unsigned ra = 0, rb = 0;
-#pragma unroll
-                            for (int r = R - 1; r >= 0; --r) {
-                                if ((Hp[r] & 0xFFFFu) == (rev_target & 0xFFFFu)) ra = (unsigned)r;
-                                if ((Hp[r] >> 16) == (rev_target >> 16)) rb = (unsigned)r;
-                            }
-                            if (hitA) { bestcol = (bestcol & 0xFFFF0000u) | ((unsigned)col & 0xFFFFu); rev_rowA = ra; }
-                            if (hitB) { bestcol = (bestcol & 0xFFFFu) | ((unsigned)col << 16); rev_rowB = rb; }
-                        }
-                    }
-                    vmax = nm;
-                }
-            }
-            {   // the next four columns' letters; the load after that is in flight for four steps
-                wA = wA_next; wB = wB_next;
-                const int k = ((s0 + 1) >> 2) + 2;
-                wA_next = letters4(pA, endA, k); wB_next = letters4(pB, endB, k);
-                letter_block(k - 1);
-            }
-            }
-            if (has_below && ncols > 0 && g == GROUP - 1) (scr_out + (ncols - 1))[scr_grp] = make_uint2(out_H, out_F);
-
-            // ---- fold this tile's lanes into the pair's running best (tie rules in the key order) ----
-            unsigned rowA_first = rev_rowA, rowB_first = rev_rowB;
-            unsigned sA = vmax & 0xFFFFu, sB = vmax >> 16;
-            if (!REV) {
-#pragma unroll
-                for (int r = R - 1; r >= 0; --r) {
-                    if ((aux[r] & 0xFFFFu) == sA) rowA_first = (unsigned)r;
-                    if ((aux[r] >> 16) == sB) rowB_first = (unsigned)r;
-                }
-            } else {   // a strip that never reached the forward score has no candidate
-                sA = sA == (rev_target & 0xFFFFu) ? sA : 0u;
-                sB = sB == (rev_target >> 16) ? sB : 0u;
-            }
-            const unsigned rgA = (unsigned)(tile_base + g * R) + rowA_first;
-            const unsigned rgB = (unsigned)(tile_base + g * R) + rowB_first;
-            unsigned long long keyA = sA ? ((unsigned long long)sA << 32) | ((0xFFFFu - (bestcol & 0xFFFFu)) << 16) | (0xFFFFu - rgA) : 0ull;
-            unsigned long long keyB = sB ? ((unsigned long long)sB << 32) | ((0xFFFFu - (bestcol >> 16)) << 16) | (0xFFFFu - rgB) : 0ull;
-#pragma unroll
-            for (int m = 1; m < GROUP; m <<= 1) {
-                const unsigned long long oa = __shfl_xor(keyA, m), ob = __shfl_xor(keyB, m);
-                keyA = oa > keyA ? oa : keyA;
-                keyB = ob > keyB ? ob : keyB;
-            }
-            bestA = keyA > bestA ? keyA : bestA;
-            bestB = keyB > bestB ? keyB : bestB;
-        }
-
-        // ---- write results -----------------------------------------------------------------------
-        if (g == 0) {
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const bool valid = half ? vB : vA;
-                if (!valid) continue;
-                const unsigned long long key = half ? bestB : bestA;
-                const uint32_t h = half ? hB : hA;
-                const int score = (int)(key >> 32);
-                const int col = 0xFFFF - (int)((key >> 16) & 0xFFFFu);
-                const int row = 0xFFFF - (int)(key & 0xFFFFu);
-                mmgpu_sw_hit *o = L.out + L.hit_out[h];
-                if (!REV) {
-                    mmgpu_sw_hit res;
-                    res.score = score;
-                    res.q_end = score ? row : 0;       // all-zero saved column matches at index 0 (:263-271)
-                    res.t_end = score ? col : -1;      // byte pass initialises end_db = -1 (:118)
-                    res.q_start = -1;
-                    res.t_start = -1;
-                    res.word = (score + qbias >= 255) ? 1 : 0;
-                    *o = res;
-                } else {
-                    const int end = half ? endB : endA;
-                    const int cols = half ? colsB : colsA;
-                    if (cols > 0) {
-                        // column index counts backwards from t_end; row is an index into the reversed query
-                        // score 0: no strip reached the forward score - "Score of forward/backward SW differ" (:1191-1201)
-                        o->t_start = (score == o->score) ? end - col : -2;
-                        o->q_start = (score == o->score) ? qlen - 1 - row : -2;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// Three launches per pass for the whole batch.  The tile shape (rows per lane R, single / multi tile) is a property
-// of the job: every shape is its own instantiation of sw_body, picked per workgroup.  A launch per shape (32 kernels
-// with grids from 50 to 3000 workgroups on side streams) left the chip underfilled - the runtime maps streams onto
-// four hardware queues, and the long multi-tile jobs of the few long queries ran nearly alone at the end.  Shapes
-// are grouped by register need instead (a kernel gets the registers of its largest body, which sets the occupancy of
-// all of them): S = R <= 12 (forward 80 / reverse 119 VGPRs), M = R 14..24 (140 / 212), L = R >= 26 and every
-// multi-tile shape (212 / 256).  Each group is one grid, longest job first; the three run concurrently.
-// BOTH = false: forward scan only (MMGPU_SW_SCORE_END).  BOTH = true: the workgroup runs the reverse scan of its own
-// pairs right after their forward scan - no grid-wide barrier between the passes, so the batch has one tail, not two.
-template <int R, bool MULTI, bool BOTH>
-__device__ __forceinline__ void sw_passes(const SwLaunch &L, const SwJob &job) {
-    if constexpr (R <= SW_MAX_R) {
-        // the prefetch goes where it costs no wavefront and no wait states: not into the forward-only kernel of R = 25 .. 28
-        // (183 registers, two wavefronts instead of three) and not into the multi-tile bodies (with it the compiler puts a
-        // wait state into every row of phase 2 again, profiles/sw_isa_audit.txt)
-        constexpr bool PF = MMGPU_SW_PREFETCH && !MULTI && (BOTH || R <= 24);
-        if (!(BOTH && L.rev_only)) sw_body<R, MULTI, false, PF>(L, job);
-        // multi-tile queries get their reverse scan from sw_rev_multi_kernel (below), per query instead of per job
-        if constexpr (BOTH && !MULTI) {
-            __threadfence_block();   // the forward results of this job, written by other waves of the workgroup
-            __syncthreads();
-            sw_body<R, MULTI, true, PF>(L, job);
-        }
-    }
-}
-
-// occupancy floor (waves per SIMD; 512 registers per lane and SIMD) per group and kernel kind: what the compiler is told to
-// fit.  Measured on the 10k x 1M lists (profiles/r03_exp_sw_occupancy_floors.txt): the floor changes the schedule even
-// where the register count already fits.
-#ifndef MMGPU_SW_WAVES_G0F
-#define MMGPU_SW_WAVES_G0F 4
-#endif
-#ifndef MMGPU_SW_WAVES_G0B
-#define MMGPU_SW_WAVES_G0B 2
-#endif
-#ifndef MMGPU_SW_WAVES_G1F
-#define MMGPU_SW_WAVES_G1F 3
-#endif
-#ifndef MMGPU_SW_WAVES_G1B
-#define MMGPU_SW_WAVES_G1B 2
-#endif
 // (a query cut into tiles gets at least ceil(SW_MAX_R / 2) rows per lane: R = 8 .. 32 covers every SW_MAX_R the header allows)
 #define MMGPU_SW_MULTI_ALL                                                                                                          \
     MMGPU_SW_MULTI(8) MMGPU_SW_MULTI(9) MMGPU_SW_MULTI(10) MMGPU_SW_MULTI(11) MMGPU_SW_MULTI(12) MMGPU_SW_MULTI(13) MMGPU_SW_MULTI(14) \
@@ -904,9 +279,19 @@ int sw_shape_group(uint32_t shape) {
     return R <= 12 ? 0 : (R <= 24 ? 1 : 2);
 }
 
+// May this batch's single-tile forward scans run in f16 (sw_half_kernel.hip)?  The exactness rule of sw_body.h (at SW_HALF_LIMIT)
+// assumes profile entries in [-256, 254] - true of every batch: they are sums of two int8, or int8 profile scores, whatever the
+// alphabet - and gap costs that f16 holds exactly and whose subtraction from a value in [0, 2046] stays within +-2048:
+// 0 <= gap_extend, gap_open <= 2048.  A launch that only runs reverse scans (rev_only) has no forward scan to gain from.
+static bool sw_half_eligible(const SwLaunch &L) {
+    return MMGPU_SW_HALF && !L.rev_only && L.gap_open >= 0 && L.gap_open <= SW_HALF_MAX_GAP && L.gap_extend >= 0 &&
+           L.gap_extend <= SW_HALF_MAX_GAP;
+}
+
 hipError_t launch_sw(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream) {
     static_assert(GROUP == 16, "the shape codes assume 16-lane groups");
     if (L.n_jobs == 0) return hipSuccess;
+    if (sw_half_eligible(L) && launch_sw_half(L, group, lds_bytes, both_passes, stream)) return hipGetLastError();
     dim3 grid(L.n_jobs), block(WAVES * 64);
     const size_t lds = lds_bytes + SW_LDS_HEADER;
     switch (group * 2 + (both_passes ? 1 : 0)) {
@@ -927,6 +312,7 @@ hipError_t launch_sw(const SwLaunch &L, int group, size_t lds_bytes, bool both_p
 void warm_sw() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sw_rev_multi_kernel));
+    if (MMGPU_SW_HALF) warm_sw_half();
 }
 
 }  // namespace mmgpu

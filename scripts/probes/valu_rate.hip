@@ -55,6 +55,18 @@ PROBE(k_pk_min_i16, OP8("v_pk_min_i16", ""))
 PROBE(k_max_i16, OP8("v_max_i16", ""))
 PROBE(k_sad_u16, "v_sad_u16 %0, %0, %8, %1\nv_sad_u16 %1, %1, %8, %2\nv_sad_u16 %2, %2, %8, %3\nv_sad_u16 %3, %3, %8, %4\n"
                  "v_sad_u16 %4, %4, %8, %5\nv_sad_u16 %5, %5, %8, %6\nv_sad_u16 %6, %6, %8, %7\nv_sad_u16 %7, %7, %8, %0")
+// packed f16: what a row of the f16 forward scan is made of (sw_half_kernel.hip) - add with and without the negate
+// modifiers, three-way maximum with three registers and with the inline constant 0.  main passes (3.0, 3.0) as the
+// shared operand of these.
+PROBE(k_pk_add_f16, OP8("v_pk_add_f16", ""))
+PROBE(k_pk_add_f16_neg, OP8("v_pk_add_f16", " neg_lo:[0,1] neg_hi:[0,1]"))
+PROBE(k_pk_max_f16, OP8("v_pk_max_f16", ""))
+PROBE(k_pk_maximum3_f16, "v_pk_maximum3_f16 %0, %0, %8, %1\nv_pk_maximum3_f16 %1, %1, %8, %2\nv_pk_maximum3_f16 %2, %2, %8, %3\n"
+                         "v_pk_maximum3_f16 %3, %3, %8, %4\nv_pk_maximum3_f16 %4, %4, %8, %5\nv_pk_maximum3_f16 %5, %5, %8, %6\n"
+                         "v_pk_maximum3_f16 %6, %6, %8, %7\nv_pk_maximum3_f16 %7, %7, %8, %0")
+PROBE(k_pk_maximum3_f16_zero, "v_pk_maximum3_f16 %0, %0, %8, 0\nv_pk_maximum3_f16 %1, %1, %8, 0\nv_pk_maximum3_f16 %2, %2, %8, 0\n"
+                              "v_pk_maximum3_f16 %3, %3, %8, 0\nv_pk_maximum3_f16 %4, %4, %8, 0\nv_pk_maximum3_f16 %5, %5, %8, 0\n"
+                              "v_pk_maximum3_f16 %6, %6, %8, 0\nv_pk_maximum3_f16 %7, %7, %8, 0")
 
 typedef void (*kern_t)(unsigned *, int, unsigned);
 
@@ -65,13 +77,16 @@ int main() {
     const int blocks = cus * 8, threads = 256, iters = 4000;
     unsigned *d;
     hipMalloc(&d, (size_t)blocks * threads * 4);
-    struct { const char *name; kern_t k; } ks[] = {
+    struct { const char *name; kern_t k; unsigned operand = 3u; } ks[] = {
         {"v_pk_add_i16 clamp", k_pk_add_i16}, {"v_pk_max_i16", k_pk_max_i16}, {"v_pk_max_u16", k_pk_max_u16},
         {"v_pk_sub_u16 clamp", k_pk_sub_u16}, {"v_pk_add_u16", k_pk_add_u16}, {"v_pk_min_i16", k_pk_min_i16},
         {"v_max_i16", k_max_i16}, {"v_max_i32", k_max_i32}, {"v_add_u32", k_add_u32}, {"v_sub_u32 clamp", k_sub_u32_clamp},
         {"v_and_b32", k_and_b32}, {"v_max3_i32", k_max3_i32}, {"v_add3_u32", k_add3_u32}, {"v_perm_b32", k_perm_b32},
         {"v_bfi_b32", k_bfi_b32}, {"v_mov_b32_dpp row_shr:1", k_mov_dpp}, {"v_sad_u16", k_sad_u16},
         {"v_fma_f32", k_fma_f32}, {"v_pk_fma_f16", k_pk_fma_f16},
+        {"v_pk_add_f16", k_pk_add_f16, 0x42004200u}, {"v_pk_add_f16 neg_lo neg_hi", k_pk_add_f16_neg, 0x42004200u},
+        {"v_pk_max_f16", k_pk_max_f16, 0x42004200u}, {"v_pk_maximum3_f16", k_pk_maximum3_f16, 0x42004200u},
+        {"v_pk_maximum3_f16 , 0", k_pk_maximum3_f16_zero, 0x42004200u},
     };
     printf("device: %s, %d CUs, clock %d MHz\n", prop.name, cus, prop.clockRate / 1000);
     printf("%-26s %12s %14s %16s\n", "instruction", "ms", "Tlane-op/s", "cyc/wave-instr@2.4GHz/SIMD");
@@ -79,10 +94,10 @@ int main() {
     hipEventCreate(&e0);
     hipEventCreate(&e1);
     for (auto &k : ks) {
-        hipLaunchKernelGGL(k.k, dim3(blocks), dim3(threads), 0, 0, d, 10, 3u);
+        hipLaunchKernelGGL(k.k, dim3(blocks), dim3(threads), 0, 0, d, 10, k.operand);
         hipDeviceSynchronize();
         hipEventRecord(e0);
-        hipLaunchKernelGGL(k.k, dim3(blocks), dim3(threads), 0, 0, d, iters, 3u);
+        hipLaunchKernelGGL(k.k, dim3(blocks), dim3(threads), 0, 0, d, iters, k.operand);
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         float ms;

@@ -14,6 +14,11 @@ the rarely taken `nm != vmax` branch (running maximum, snapshot / row search) is
     python scripts/sw_isa_audit.py -o FILE         # ... into a file (profiles/sw_isa_audit.txt)
     python scripts/sw_isa_audit.py --asm FILE.s    # audit an assembly file made earlier
     python scripts/sw_isa_audit.py -D MMGPU_SW_WAVES_G1B=3
+    python scripts/sw_isa_audit.py --src sw_half_kernel.hip --pk-per-row 7.5 -o profiles/sw_half_isa_audit.txt
+
+--src names another file of mmseqs2_amd/csrc that instantiates sw_body (sw_half_kernel.hip: the f16 forward scan).  Its f16
+loops - the ones that hold v_pk_maximum3_f16 - are listed as dir=half, and the tool's own check on them is
+pk <= PK_PER_ROW * R + 2 (--pk-per-row); the int16 loops are always held to pk = 9 R.
 
 The `LOOP` and `KERNEL` lines are `key=value` records: tests/test_sw_isa_audit.py reads them (parse_records).
 """
@@ -42,12 +47,12 @@ def makefile_flags():
     return m.group(1).split()
 
 
-def compile_asm(out_path, defines=()):
+def compile_asm(out_path, defines=(), src="sw_kernel.hip"):
     hipcc = find_hipcc()
     if not hipcc:
         raise RuntimeError("hipcc not found")
     cmd = [hipcc] + makefile_flags() + ["-D" + d for d in defines] + [
-        "--cuda-device-only", "-S", os.path.join(CSRC, "sw_kernel.hip"), "-o", out_path]
+        "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out_path]
     r = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed (exit %d): %s\n%s" % (r.returncode, " ".join(cmd), r.stderr[-4000:]))
@@ -56,9 +61,9 @@ def compile_asm(out_path, defines=()):
 def kernel_name(sym):
     if "sw_rev_multi_kernel" in sym:
         return "sw_rev_multi_kernel"
-    m = re.search(r"sw_kernelILi(\d+)ELb([01])E", sym)
+    m = re.search(r"(sw_kernel|sw_half_kernel)ILi(\d+)ELb([01])E", sym)
     if m:
-        return "sw_kernel<%s,%s>" % (m.group(1), "true" if m.group(2) == "1" else "false")
+        return "%s<%s,%s>" % (m.group(1), m.group(2), "true" if m.group(3) == "1" else "false")
     if "sw_from_pf_kernel" in sym:
         return "sw_from_pf_kernel"
     return sym
@@ -146,6 +151,8 @@ def audit_loop(path):
             c["pk"] += 1
         if m == "v_perm_b32":
             c["perm"] += 1
+        if m == "v_pk_maximum3_f16":
+            c["max3_f16"] += 1
         if m.startswith("ds_read"):
             c["ds_read"] += 1
         if m == "s_nop":
@@ -175,7 +182,7 @@ def audit(asm_path):
     kernels, loops = [], []
     for sym, a, b in split_functions(lines):
         name = kernel_name(sym)
-        if not name.startswith("sw_kernel") and name != "sw_rev_multi_kernel":
+        if not name.startswith(("sw_kernel", "sw_half_kernel")) and name != "sw_rev_multi_kernel":
             continue
         labels = {}
         for i in range(a, b):
@@ -207,7 +214,8 @@ def audit(asm_path):
                 continue
             c, pairs = audit_loop(path)
             R = c["perm"]
-            loops.append(dict(kernel=name, label=lab, dir="rev" if c["select"] >= R and R > 0 else "fwd", R=R,
+            direction = "rev" if c["select"] >= R and R > 0 else ("half" if c["max3_f16"] else "fwd")
+            loops.append(dict(kernel=name, label=lab, dir=direction, R=R,
                               counts=c, pairs=pairs, skipped=skipped))
     return kernels, loops
 
@@ -215,19 +223,22 @@ def audit(asm_path):
 FIELDS = ["instr", "valu", "pk", "perm", "ds_read", "s_nop", "v_mov", "s_waitcnt", "lgkm_wait_within2"]
 
 
-def report(kernels, loops, out):
+def report(kernels, loops, out, src="sw_kernel.hip", pk_per_row=9.0):
     w = out.write
-    w("# SW column loop audit (scripts/sw_isa_audit.py): gfx950 assembly of mmseqs2_amd/csrc/sw_kernel.hip, Makefile flags\n")
+    w("# SW column loop audit (scripts/sw_isa_audit.py): gfx950 assembly of mmseqs2_amd/csrc/%s, Makefile flags\n" % src)
     w("# Per loop: one column's straight path.  Skipped: the block under s_and_saveexec / s_cbranch_execz of the rare\n")
     w("# `nm != vmax` branch (its instruction count is given as skipped=).  R is the v_perm_b32 count of the loop.\n")
-    w("# pk must be 9 R (the tool's own check): pk_ok=1.\n\n")
+    w("# pk must be 9 R (the tool's own check): pk_ok=1.\n")
+    if any(lp["dir"] == "half" for lp in loops):
+        w("# dir=half: the f16 forward loops (they hold v_pk_maximum3_f16); their check is pk <= %g R + 2.\n" % pk_per_row)
+    w("\n")
     for k in kernels:
         w("KERNEL kernel=%s vgpr=%s occupancy=%s scratch=%s\n" % (k["kernel"], k["vgpr"], k["occupancy"], k["scratch"]))
     w("\n")
     bad = 0
     for lp in sorted(loops, key=lambda d: (d["kernel"], d["dir"], d["R"])):
         c = lp["counts"]
-        ok = int(c["pk"] == 9 * lp["R"])
+        ok = int(c["pk"] <= pk_per_row * lp["R"] + 2 if lp["dir"] == "half" else c["pk"] == 9 * lp["R"])
         bad += 1 - ok
         w("LOOP kernel=%s dir=%s R=%d %s skipped=%d pk_ok=%d label=%s\n" % (
             lp["kernel"], lp["dir"], lp["R"], " ".join("%s=%d" % (f, c[f]) for f in FIELDS), lp["skipped"], ok, lp["label"]))
@@ -259,18 +270,18 @@ def parse_records(text):
     return kernels, loops
 
 
-def run(defines=(), asm=None):
+def run(defines=(), asm=None, src="sw_kernel.hip", pk_per_row=9.0):
     """Audit text of the tree (or of an assembly file made earlier)."""
     import io
     if asm is None:
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "sw_kernel.s")
-            compile_asm(path, defines)
+            compile_asm(path, defines, src)
             kernels, loops = audit(path)
     else:
         kernels, loops = audit(asm)
     buf = io.StringIO()
-    bad = report(kernels, loops, buf)
+    bad = report(kernels, loops, buf, src, pk_per_row)
     return buf.getvalue(), bad
 
 
@@ -279,14 +290,16 @@ def main():
     ap.add_argument("--asm", help="audit this assembly file instead of compiling")
     ap.add_argument("-D", dest="defines", action="append", default=[], help="extra -D for the compile")
     ap.add_argument("-o", dest="out", help="write the audit here instead of stdout")
+    ap.add_argument("--src", default="sw_kernel.hip", help="file of mmseqs2_amd/csrc to audit (default sw_kernel.hip)")
+    ap.add_argument("--pk-per-row", type=float, default=9.0, help="v_pk_* per row the f16 loops may hold (dir=half); default 9")
     a = ap.parse_args()
-    text, bad = run(a.defines, a.asm)
+    text, bad = run(a.defines, a.asm, a.src, a.pk_per_row)
     if a.out:
         open(a.out, "w").write(text)
     else:
         sys.stdout.write(text)
     if bad:
-        sys.stderr.write("sw_isa_audit: %d loops whose v_pk_* count is not 9 R - the loop walk is wrong for them\n" % bad)
+        sys.stderr.write("sw_isa_audit: %d loops whose v_pk_* count is not what is expected - the loop walk is wrong for them\n" % bad)
     return 1 if bad else 0
 
 
