@@ -758,6 +758,61 @@ int mmgpu_scan_batch(mmgpu_ctx *ctx, const mmgpu_scan_params *params, const mmgp
  * scan batch has run on the context since (the scores live in the context's scratch).  Synchronises. */
 int mmgpu_scan_debug_scores(mmgpu_ctx *ctx, mmgpu_scan_batch_t *batch, uint32_t query, uint8_t *out, size_t cap);
 
+/* ---- exhaustive gapped scan (runFilterOnCpu with alignmentMode == 1, src/prefiltering/ungappedprefilter.cpp:346-482, :594) ------
+ * `mmseqs gappedprefilter`: every query against every resident target of its length window, scored with the Gotoh score of
+ * ssw_align(..., Matcher::SCORE_ONLY, ...) - mmgpu_sw_hit::score of a MMGPU_SW_SCORE_END batch, saturation at 32767 included; the
+ * forward kernels of mmgpu_sw_run compute it.  The query's own target (identity_id) is not aligned: it scores what
+ * SmithWaterman::scoreIdentical gives (StripedSmithWaterman.cpp:1770-1805), the sum over i of p(i, t[i]) accumulated in a short
+ * (it wraps as int16 and may be negative), with p as in the gapped alignment section: mat[t[i] * alphabet + q[i]] + comp_bias[i],
+ * or the profile query's row (0 for the letters from min(profile_letters, alphabet - 1) on).
+ * A query's list holds the targets inside its window with  score > min_score  and  score >= min_evalue_score  (the host's
+ * translation of computeEvalue(score, qlen) <= evalThr, which falls monotonically in the score), and its own target inside the
+ * window whatever it scores, by (score descending, id ascending), cut at max_hits; diagonal is 0.
+ * MMGPU_ERR_STATE: no targets loaded.  MMGPU_ERR_UNSUPPORTED: max_hits above MMGPU_PF_MAX_FUSED_HITS; a context that holds a shard;
+ * a batch with a query outside the acceptance rule of the gapped alignment section (the same check as mmgpu_sw_prepare's); more
+ * than 4 GiB of scores (n_queries x resident targets x 4 bytes).  MMGPU_ERR_ARG: NULL arguments, an empty query, a letter outside
+ * the alphabet, max_hits 0, min_tlen above max_tlen, an identity target (inside the window) whose length differs from qlen - the
+ * reference exits there. */
+typedef struct {
+    const int8_t *mat;    /* as mmgpu_sw_params */
+    int alphabet;
+    int gap_open;
+    int gap_extend;
+    int32_t min_score;    /* par.minDiagScoreThr (--min-ungapped-score): listed when score > min_score */
+    uint32_t max_hits;    /* par.maxResListLen (--max-seqs), 1 .. MMGPU_PF_MAX_FUSED_HITS */
+    uint64_t pair_budget; /* most (query, target) pairs scored at once: a batch with more runs as consecutive chunks of whole queries
+                             over one set of buffers (a query whose window alone exceeds it is a chunk of its own); 0 = the library's
+                             default.  The results do not depend on it. */
+} mmgpu_gscan_params;
+typedef struct {
+    const uint8_t *q;        /* as mmgpu_sw_query (a profile query: the consensus sequence) */
+    uint32_t qlen;
+    const int8_t *comp_bias; /* as mmgpu_sw_query */
+    const int8_t *profile;   /* as mmgpu_sw_query */
+    uint32_t profile_letters;
+    uint32_t identity_id;    /* the query's own target, UINT32_MAX = none */
+    uint32_t min_tlen, max_tlen; /* as mmgpu_scan_query */
+    int32_t min_evalue_score;/* listed only when score >= this: the smallest raw score whose E-value passes -e; <= 0 = every score */
+} mmgpu_gscan_query;
+typedef struct mmgpu_gscan_batch_t mmgpu_gscan_batch_t;
+/* the entry points mirror mmgpu_scan_*: the same contracts, lists of mmgpu_pf_hit with score = the int32 Gotoh or identity score */
+int mmgpu_gscan_prepare(mmgpu_ctx *ctx, const mmgpu_gscan_params *params, const mmgpu_gscan_query *queries, uint32_t n_queries,
+                        mmgpu_gscan_batch_t **batch);
+int mmgpu_gscan_run(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch);
+int mmgpu_gscan_fetch(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch, mmgpu_pf_hit *hits, uint32_t hit_stride, uint32_t *counts);
+int mmgpu_gscan_fetch_device(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch, void *d_hits, uint32_t hit_stride, void *d_counts);
+int mmgpu_gscan_last_kernel_ms(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch, float *ms);
+void mmgpu_gscan_free(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch);
+int mmgpu_gscan_batch(mmgpu_ctx *ctx, const mmgpu_gscan_params *params, const mmgpu_gscan_query *queries, uint32_t n_queries,
+                      mmgpu_pf_hit *hits, uint32_t hit_stride, uint32_t *counts);
+/* test aid: the raw score of every resident target for one query of a batch that has been run, one int32 per target in id order,
+ * before threshold, E-value rule or selection apply: targets outside the window read 0, the identity target reads its scoreIdentical
+ * value.  cap >= resident targets (in elements).  MMGPU_ERR_STATE as mmgpu_scan_debug_scores.  Synchronises. */
+int mmgpu_gscan_debug_scores(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch, uint32_t query, int32_t *out, size_t cap);
+/* milliseconds of the last run by stage: ms[0] planner, [1] Gotoh kernels, [2] identity, [3] selection, summed over the chunks; the
+ * chunks of the last run in *n_chunks (may be NULL).  Synchronises. */
+int mmgpu_gscan_stage_ms(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch, float ms[4], uint32_t *n_chunks);
+
 #ifdef __cplusplus
 }
 #endif

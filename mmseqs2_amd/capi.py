@@ -90,6 +90,8 @@ EXPORTED_SYMBOLS = [
     "mmgpu_sw_prepare_masked", "mmgpu_sw_debug_masked_target",
     "mmgpu_scan_prepare", "mmgpu_scan_run", "mmgpu_scan_fetch", "mmgpu_scan_fetch_device", "mmgpu_scan_last_kernel_ms", "mmgpu_scan_free",
     "mmgpu_scan_batch", "mmgpu_scan_debug_scores",
+    "mmgpu_gscan_prepare", "mmgpu_gscan_run", "mmgpu_gscan_fetch", "mmgpu_gscan_fetch_device", "mmgpu_gscan_last_kernel_ms", "mmgpu_gscan_free",
+    "mmgpu_gscan_batch", "mmgpu_gscan_debug_scores", "mmgpu_gscan_stage_ms",
 ]
 
 
@@ -135,6 +137,17 @@ class ScanParams(ctypes.Structure):      # mmgpu_scan_params
 class ScanQuery(ctypes.Structure):      # mmgpu_scan_query
     _fields_ = [("q", c_p), ("qlen", ctypes.c_uint32), ("comp_bias", c_p), ("identity_id", ctypes.c_uint32),
                 ("min_tlen", ctypes.c_uint32), ("max_tlen", ctypes.c_uint32), ("profile", c_p), ("profile_letters", ctypes.c_uint32)]
+
+
+class GscanParams(ctypes.Structure):      # mmgpu_gscan_params
+    _fields_ = [("mat", c_p), ("alphabet", ctypes.c_int), ("gap_open", ctypes.c_int), ("gap_extend", ctypes.c_int),
+                ("min_score", ctypes.c_int32), ("max_hits", ctypes.c_uint32), ("pair_budget", ctypes.c_uint64)]
+
+
+class GscanQuery(ctypes.Structure):      # mmgpu_gscan_query
+    _fields_ = [("q", c_p), ("qlen", ctypes.c_uint32), ("comp_bias", c_p), ("profile", c_p), ("profile_letters", ctypes.c_uint32),
+                ("identity_id", ctypes.c_uint32), ("min_tlen", ctypes.c_uint32), ("max_tlen", ctypes.c_uint32),
+                ("min_evalue_score", ctypes.c_int32)]
 
 
 class PfShard(ctypes.Structure):
@@ -255,6 +268,16 @@ def load_library():
     L.mmgpu_scan_free.restype = None
     L.mmgpu_scan_batch.argtypes = [c_p, ctypes.POINTER(ScanParams), c_p, ctypes.c_uint32, c_p, ctypes.c_uint32, c_p]
     L.mmgpu_scan_debug_scores.argtypes = [c_p, c_p, ctypes.c_uint32, c_p, ctypes.c_size_t]
+    L.mmgpu_gscan_prepare.argtypes = [c_p, ctypes.POINTER(GscanParams), c_p, ctypes.c_uint32, ctypes.POINTER(c_p)]
+    L.mmgpu_gscan_run.argtypes = [c_p, c_p]
+    L.mmgpu_gscan_fetch.argtypes = [c_p, c_p, c_p, ctypes.c_uint32, c_p]
+    L.mmgpu_gscan_fetch_device.argtypes = [c_p, c_p, c_p, ctypes.c_uint32, c_p]
+    L.mmgpu_gscan_last_kernel_ms.argtypes = [c_p, c_p, ctypes.POINTER(ctypes.c_float)]
+    L.mmgpu_gscan_stage_ms.argtypes = [c_p, c_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)]
+    L.mmgpu_gscan_free.argtypes = [c_p, c_p]
+    L.mmgpu_gscan_free.restype = None
+    L.mmgpu_gscan_batch.argtypes = [c_p, ctypes.POINTER(GscanParams), c_p, ctypes.c_uint32, c_p, ctypes.c_uint32, c_p]
+    L.mmgpu_gscan_debug_scores.argtypes = [c_p, c_p, ctypes.c_uint32, c_p, ctypes.c_size_t]
     return L
 
 
@@ -525,6 +548,56 @@ class ScanBatch:
     def free(self):
         if self.handle is not None:
             self.gpu.L.mmgpu_scan_free(self.gpu.ctx, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class GscanBatch:
+    """A prepared exhaustive gapped scan (mmgpu_gscan_*): queries resident in HBM."""
+
+    def __init__(self, gpu, handle, keep, nq, stride):
+        self.gpu, self.handle, self._keep, self.nq, self.stride = gpu, handle, keep, nq, stride
+
+    def run(self):
+        self.gpu._check(self.gpu.L.mmgpu_gscan_run(self.gpu.ctx, self.handle))
+
+    def fetch(self):
+        """-> (hits[nq][stride] PF_HIT_DTYPE, counts[nq])"""
+        hits = np.zeros((self.nq, max(self.stride, 1)), PF_HIT_DTYPE)
+        counts = np.zeros(self.nq, np.uint32)
+        self.gpu._check(self.gpu.L.mmgpu_gscan_fetch(self.gpu.ctx, self.handle, _ptr(hits), max(self.stride, 1), _ptr(counts)))
+        return hits, counts
+
+    def fetch_device(self, d_hits_ptr, stride, d_counts_ptr):
+        """D2D copy of the lists into caller-owned device memory (raw pointers): what sw_prepare_from_lists reads"""
+        self.gpu._check(self.gpu.L.mmgpu_gscan_fetch_device(self.gpu.ctx, self.handle, c_p(d_hits_ptr), stride, c_p(d_counts_ptr)))
+
+    def debug_scores(self, query):
+        """mmgpu_gscan_debug_scores (test aid): the raw int32 score of every resident target for one query of the last run"""
+        out = np.zeros(max(self.gpu.n_targets, 1), np.int32)
+        self.gpu._check(self.gpu.L.mmgpu_gscan_debug_scores(self.gpu.ctx, self.handle, int(query), _ptr(out), out.size))
+        return out[:self.gpu.n_targets]
+
+    def kernel_ms(self):
+        ms = ctypes.c_float()
+        self.gpu._check(self.gpu.L.mmgpu_gscan_last_kernel_ms(self.gpu.ctx, self.handle, ctypes.byref(ms)))
+        return ms.value
+
+    def stage_ms(self):
+        """-> (dict planner / sw / identity / select in ms, chunks) of the last run"""
+        ms = (ctypes.c_float * 4)()
+        n = ctypes.c_uint32()
+        self.gpu._check(self.gpu.L.mmgpu_gscan_stage_ms(self.gpu.ctx, self.handle, ms, ctypes.byref(n)))
+        return dict(planner=ms[0], sw=ms[1], identity=ms[2], select=ms[3]), n.value
+
+    def free(self):
+        if self.handle is not None:
+            self.gpu.L.mmgpu_gscan_free(self.gpu.ctx, self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1044,6 +1117,47 @@ class MMGpu:
         del keep
         return hits[:len(queries)], counts[:len(queries)]
 
+    def _gscan_marshal(self, mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget):
+        """queries: list of dicts {q: uint8[] (a profile query: the consensus), comp_bias: int8[]|None (rounded), identity_id: int|None,
+        window: (min_tlen, max_tlen)|None, profile: int8[letters][qlen]|None, min_evalue_score: int (default 0: every score passes)}"""
+        mat = np.ascontiguousarray(mat, np.int8)
+        par = GscanParams(_ptr(mat), mat.shape[0], int(gap_open), int(gap_extend), int(min_score), int(max_hits), int(pair_budget))
+        arr = (GscanQuery * max(len(queries), 1))()
+        keep = [mat]
+        for i, qd in enumerate(queries):
+            prof = None if qd.get("profile") is None else np.ascontiguousarray(qd["profile"], np.int8)
+            if prof is not None and prof.ndim != 2:
+                raise ValueError("profile must be [letters][qlen]")
+            q = np.ascontiguousarray(qd["q"], np.uint8)
+            if prof is not None and prof.shape[1] != len(q):
+                raise ValueError("profile must be [letters][qlen]")
+            cb = None if qd.get("comp_bias") is None else np.ascontiguousarray(qd["comp_bias"], np.int8)
+            if cb is not None and len(cb) != len(q):
+                raise ValueError("comp_bias must have the query's length")
+            ident = qd.get("identity_id")
+            lo, hi = qd.get("window") or (0, 0xFFFFFFFF)
+            keep += [q, cb, prof]
+            arr[i] = GscanQuery(_ptr(q), len(q), _ptr(cb), _ptr(prof), 0 if prof is None else prof.shape[0],
+                                0xFFFFFFFF if ident is None else int(ident), int(lo), int(hi), int(qd.get("min_evalue_score") or 0))
+        return par, arr, keep
+
+    def gscan_prepare(self, mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, pair_budget=0):
+        """mmgpu_gscan_prepare: the exhaustive gapped scan (`gappedprefilter`) of sequence and profile queries over the resident targets"""
+        par, arr, keep = self._gscan_marshal(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
+        h = c_p()
+        self._check(self.L.mmgpu_gscan_prepare(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), ctypes.byref(h)))
+        return GscanBatch(self, h, keep, len(queries), min(int(max_hits), self.n_targets))
+
+    def gscan_batch(self, mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, pair_budget=0):
+        """mmgpu_gscan_batch: -> (hits[nq][stride], counts[nq])"""
+        par, arr, keep = self._gscan_marshal(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
+        stride = max(min(int(max_hits), getattr(self, "n_targets", 0)), 1)
+        hits = np.zeros((max(len(queries), 1), stride), PF_HIT_DTYPE)
+        counts = np.zeros(max(len(queries), 1), np.uint32)
+        self._check(self.L.mmgpu_gscan_batch(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), _ptr(hits), stride, _ptr(counts)))
+        del keep
+        return hits[:len(queries)], counts[:len(queries)]
+
     def pf_set_shard(self, n_shards, shard, global_db_size, global_ids, shard_of, local_id):
         """this context holds shard `shard` of a database of global_db_size targets (None-like: pf_clear_shard)"""
         g = np.ascontiguousarray(global_ids, np.uint32)
@@ -1118,6 +1232,30 @@ def exhaustive_search(gpu, scan_mat, sw_mat, gap_open, gap_extend, queries, min_
     torch.cuda.synchronize()      # (the buffers are zeroed on torch's stream, filled on the context's)
     scan.fetch_device(d_hits.data_ptr(), stride, d_counts.data_ptr())
     sw = gpu.sw_prepare_from_lists(sw_mat, gap_open, gap_extend, queries, d_hits.data_ptr(), d_counts.data_ptr(), stride, mode=mode)
+    sw.run()
+    rec = sw.fetch().reshape(len(queries), stride)
+    hits, counts = scan.fetch()
+    sw.free()
+    scan.free()
+    gpu.synchronize()
+    del d_hits, d_counts
+    return hits, counts, rec
+
+
+def exhaustive_gapped_search(gpu, mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, mode=1, pair_budget=0):
+    """The gapped counterpart of exhaustive_search: gscan_prepare + run, fetch_device into a device buffer, sw_prepare_from_lists over
+    it (start positions with mode 1), run, fetch.  One matrix serves both stages (both are the Gotoh alignment).  queries: dicts with
+    q, comp_bias, identity_id, window, min_evalue_score, min_start_score, profile.
+    -> (hits[nq][stride], counts[nq], records[nq][stride] SW_HIT_DTYPE: slot k of a row = hit k of the query's list)"""
+    import torch
+    scan = gpu.gscan_prepare(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
+    scan.run()
+    stride = max(scan.stride, 1)
+    d_hits = torch.zeros(len(queries) * stride * PF_HIT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_counts = torch.zeros(len(queries), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()      # (the buffers are zeroed on torch's stream, filled on the context's)
+    scan.fetch_device(d_hits.data_ptr(), stride, d_counts.data_ptr())
+    sw = gpu.sw_prepare_from_lists(mat, gap_open, gap_extend, queries, d_hits.data_ptr(), d_counts.data_ptr(), stride, mode=mode)
     sw.run()
     rec = sw.fetch().reshape(len(queries), stride)
     hits, counts = scan.fetch()

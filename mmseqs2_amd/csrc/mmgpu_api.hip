@@ -241,6 +241,7 @@ extern "C" int mmgpu_warmup(mmgpu_ctx *c) {
     mmgpu::warm_block4();
     mmgpu::warm_bt();
     mmgpu::warm_scan();
+    mmgpu::warm_gscan();
     return MMGPU_OK;
 }
 
@@ -541,6 +542,10 @@ struct mmgpu_sw_batch_t {
     DevBuf m_res, m_off4, m_len;
     std::vector<uint32_t> m_h_len;
     uint32_t m_max_len = 0;
+    // sw_prepare_dense: lists and records live in arrays of the caller (the chunks of an exhaustive gapped scan share one set);
+    // d_hit_target / d_hit_out / d_out stay empty
+    uint32_t *x_hit_target = nullptr, *x_hit_out = nullptr;
+    mmgpu_sw_hit *x_out = nullptr;
 };
 
 // the targets a batch's kernels read: the resident database, or the batch's masked copies
@@ -614,6 +619,7 @@ struct SwPrepare {
     int mode;
     const DeviceLists *pf;        // null: the lists are the caller's (mmgpu_sw_query::target_ids)
     const mmgpu_sw_masks *masks;  // mmgpu_sw_prepare_masked: the batch aligns against masked copies of its targets (caller's lists only)
+    const SwDenseLists *dense;    // sw_prepare_dense: the lists are slices of the length-ordered id list, written on the device by the caller
     mmgpu_sw_batch_t *b = nullptr;
     TargetView tv;                // the targets the lists name: the resident database, or the batch's copies once plan_masked has run
 
@@ -656,6 +662,7 @@ struct SwPrepare {
     int copy_queries();
     void cut_list_jobs_of(size_t from, size_t to);
     void cut_list_jobs();
+    void cut_dense_jobs();
     int join_list_jobs();
     void order_jobs();
     int enqueue_uploads();
@@ -712,15 +719,15 @@ int SwPrepare::size_buffers() {
     qprof_off.assign(std::max<uint32_t>(nq, 1), 0xFFFFFFFFu);
     for (uint32_t i = 0; i < nq; i++) {
         // a query without targets may come without residues (Alignment::run never maps the query of an empty list, :322)
-        const bool empty_ok = !pf && qs[i].n_targets == 0 && qs[i].qlen == 0;
+        const bool empty_ok = !pf && !dense && qs[i].n_targets == 0 && qs[i].qlen == 0;
         if (!empty_ok && (qs[i].qlen == 0 || qs[i].qlen > 65535 || !qs[i].q)) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: bad query");
         qoff[i + 1] = qoff[i] + qs[i].qlen;
-        total_hits += pf ? pf_stride : qs[i].n_targets;
+        total_hits += pf ? pf_stride : dense ? dense->count[i] : qs[i].n_targets;
     }
     if (total_hits > 0xFFFFFFF0ull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_sw_prepare: more than 2^32 pairs in one batch");
     qres.resize(qoff[nq]);
     qcb.assign(qoff[nq], 0);
-    if (!pf) {
+    if (!pf && !dense) {
         hit_target.resize((size_t)total_hits);
         hit_out.resize((size_t)total_hits);
     }
@@ -919,7 +926,7 @@ int SwPrepare::copy_queries() {
         // jobs are cut at multiples of one workgroup round (4 waves x 8 targets); for queries of several tiles a
         // single wave's 8 targets already run for milliseconds, so those are cut per wave to shorten the tail
         const uint32_t round = (multi && Q.qlen >= LONG_QUERY) ? JOB_ROUND / 4 : JOB_ROUND;
-        const uint32_t n_slots = pf ? pf_stride : Q.n_targets;
+        const uint32_t n_slots = pf ? pf_stride : dense ? dense->count[i] : Q.n_targets;
         if (pf) add_slot_jobs(i, shape, round, multi);
         // caller-supplied list: the sort by target length and the job cuts are done for all queries in parallel (cut_list_jobs)
         else deferred.push_back(Deferred{i, hit_cursor, out_cursor, shape, round, multi});
@@ -1011,6 +1018,35 @@ void SwPrepare::cut_list_jobs() {
     for (std::thread &t : pool) t.join();
 }
 
+// dense lists: query i's list is positions [begin, begin + count) of the length-ordered id list, so it is sorted already and the
+// cells of any stretch of it come from the prefix sums - the same cuts as cut_list_jobs_of without touching a pair
+void SwPrepare::cut_dense_jobs() {
+    per_query.resize(deferred.size());
+    for (size_t d = 0; d < deferred.size(); d++) {
+        const Deferred &D = deferred[d];
+        const uint64_t qlen = qs[D.query].qlen;
+        const uint32_t beg = dense->begin[D.query], n = dense->count[D.query];
+        const uint64_t *pre = dense->len_prefix + beg;
+        PerQuery &P = per_query[d];
+        P.sum_cells = qlen * (pre[n] - pre[0]);
+        P.max_tlen = n ? tv.h_len[dense->order[beg]] : 0;
+        for (uint32_t k = 0; k < n;) {
+            uint64_t jc = 0;
+            uint32_t e = k;
+            while (e < n && e - k < JOB_HITS) {
+                const uint32_t stop = std::min<uint32_t>(e + D.round, n);
+                jc += qlen * (pre[stop] - pre[e]);
+                e = stop;
+                const uint32_t held = e - k;
+                if (jc >= JOB_CELLS && (held <= 16 || held % JOB_ROUND == 0)) break;
+            }
+            P.jobs.push_back(SwJob{D.query, D.hit_cursor + k, D.hit_cursor + e, D.shape});
+            P.cells.push_back(jc);
+            k = e;
+        }
+    }
+}
+
 int SwPrepare::join_list_jobs() {
     for (size_t d = 0; d < deferred.size(); d++) {
         const Deferred &D = deferred[d];
@@ -1024,7 +1060,7 @@ int SwPrepare::join_list_jobs() {
             jobs.push_back(j);
             job_cells.push_back(P.cells[z]);
         }
-        const uint32_t n_t = qs[D.query].n_targets;
+        const uint32_t n_t = dense ? 0u : qs[D.query].n_targets;      // (dense batches are SCORE_END)
         if (D.multi && mode >= MMGPU_SW_START && n_t)
             add_rev_jobs(D.query, D.hit_cursor, n_t, D.shape, (uint64_t)qs[D.query].qlen * (P.rev_mid_len + 1));
     }
@@ -1091,12 +1127,16 @@ int SwPrepare::enqueue_uploads() {
         HIP_TRY(hipMemsetAsync(b->d_stats.p, 0, SW_FROM_PF_STAT_SLOTS * 24, s));
         HIP_TRY(b->d_pf_counts.alloc(std::max<size_t>(nq, 1) * 4));
         HIP_TRY(b->d_slot_target.alloc(std::max<size_t>((size_t)total_hits, 1) * 4));
+    } else if (dense) {
+        b->x_hit_target = dense->d_hit_target;
+        b->x_hit_out = dense->d_hit_out;
+        b->x_out = dense->d_out;
     } else {
         HIP_TRY(upload(b->d_hit_target, hit_target, s));
         HIP_TRY(upload(b->d_hit_out, hit_out, s));
     }
     HIP_TRY(up(b->d_mat, mat));
-    HIP_TRY(b->d_out.alloc(std::max<size_t>((size_t)total_hits, 1) * sizeof(mmgpu_sw_hit)));
+    if (!dense) HIP_TRY(b->d_out.alloc(std::max<size_t>((size_t)total_hits, 1) * sizeof(mmgpu_sw_hit)));
     order_jobs();
     HIP_TRY(up(b->d_jobs, sorted));
     return MMGPU_OK;
@@ -1160,9 +1200,9 @@ int SwPrepare::order_device_lists() {
 }  // namespace
 
 static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, int mode,
-                           const DeviceLists *pf, const mmgpu_sw_masks *masks, mmgpu_sw_batch_t **out) {
+                           const DeviceLists *pf, const mmgpu_sw_masks *masks, mmgpu_sw_batch_t **out, const SwDenseLists *dense = nullptr) {
     if (!c || !par || !out || (!qs && nq)) return fail(MMGPU_ERR_ARG, "mmgpu_sw_prepare: NULL argument");
-    SwPrepare S{c, par, qs, nq, mode, pf, masks};
+    SwPrepare S{c, par, qs, nq, mode, pf, masks, dense};
     if (int e = S.check_params()) return e;
     S.tv = sw_targets(c, nullptr);
     HIP_TRY(hipSetDevice(c->device));
@@ -1175,7 +1215,8 @@ static int sw_prepare_impl(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu
     if (int e = S.copy_queries()) return e;
     S.lap("queries copied, buffers sized");
     if (!S.deferred.empty()) {
-        S.cut_list_jobs();
+        if (dense) S.cut_dense_jobs();
+        else S.cut_list_jobs();
         S.lap("lists sorted by target length, jobs cut (threads)");
         if (int e = S.join_list_jobs()) return e;
     }
@@ -1431,9 +1472,9 @@ static int sw_launch_groups(mmgpu_ctx *c, mmgpu_sw_batch_t *b, bool rev_only, co
             L.t_res = T.res;
             L.t_off4 = T.off4;
             L.t_len = T.len;
-            L.hit_target = b->d_hit_target.as<uint32_t>();
-            L.hit_out = b->d_hit_out.as<uint32_t>();
-            L.out = b->d_out.as<mmgpu_sw_hit>();
+            L.hit_target = b->x_hit_target ? b->x_hit_target : b->d_hit_target.as<uint32_t>();
+            L.hit_out = b->x_hit_out ? b->x_hit_out : b->d_hit_out.as<uint32_t>();
+            L.out = b->x_out ? b->x_out : b->d_out.as<mmgpu_sw_hit>();
             L.mat = b->d_mat.as<int8_t>();
             L.alphabet = b->alphabet;
             L.gap_open = b->gap_open;
@@ -1472,6 +1513,13 @@ static int sw_launch_groups(mmgpu_ctx *c, mmgpu_sw_batch_t *b, bool rev_only, co
     }
     return MMGPU_OK;
 }
+
+namespace mmgpu {
+int sw_prepare_dense(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, const SwDenseLists &lists, mmgpu_sw_batch_t **out) {
+    return sw_prepare_impl(c, par, qs, nq, MMGPU_SW_SCORE_END, nullptr, nullptr, out, &lists);
+}
+int sw_run_dense(mmgpu_ctx *c, mmgpu_sw_batch_t *b) { return sw_launch_groups(c, b, false, nullptr); }
+}  // namespace mmgpu
 
 extern "C" int mmgpu_sw_run(mmgpu_ctx *c, mmgpu_sw_batch_t *b) {
     if (!c || !b) return fail(MMGPU_ERR_ARG, "mmgpu_sw_run: NULL argument");

@@ -268,6 +268,68 @@ hipError_t launch_scan_select(const ScanSelectArgs &A, uint32_t nq, hipStream_t 
 void warm_scan();
 
 // ---------------------------------------------------------------------------------------------------------
+// exhaustive gapped scan (gscan_api.hip, gscan_kernel.hip): the Gotoh score of every query against every resident target of its
+// window.  The pairs of a chunk of queries are an ordinary MMGPU_SW_SCORE_END batch whose lists are slices of the length-ordered id
+// list: the planner kernel writes hit_target / hit_out on the device, the host cuts only the job ranges (sw_prepare_dense).
+constexpr uint64_t GSCAN_PAIR_BUDGET = 1ull << 24;    // pairs scored at once by default: 16 M x (24 + 8) bytes of records and lists
+constexpr int GSCAN_MAX_HITS = SCAN_MAX_HITS;
+
+// the lists of a dense alignment batch: query i of the call aligns against positions [begin[i], begin[i] + count[i]) of `order`; its
+// pairs take the slots [slot_base(i), + count[i]) of the three shared device arrays, slot_base = the running sum of the counts
+struct SwDenseLists {
+    const uint32_t *begin, *count;     // [nq]
+    const uint32_t *order;             // [n_targets] host: ids by length, longest first
+    const uint64_t *len_prefix;        // [n_targets + 1] host: residues of order[0 .. k)
+    uint32_t *d_hit_target, *d_hit_out;   // device, at least sum(count) entries each, owned by the caller
+    mmgpu_sw_hit *d_out;
+};
+
+struct GscanPlanArgs {
+    const uint32_t *order;             // [n_targets] device
+    const uint32_t *q_begin, *q_count; // [nq] window slice of every query
+    const uint32_t *q_slot;            // [nq] first slot of the query inside its chunk
+    uint32_t q_first, n_queries;       // the chunk
+    uint32_t *hit_target, *hit_out;
+};
+hipError_t launch_gscan_plan(const GscanPlanArgs &A, hipStream_t stream);
+
+struct GscanIdentArgs {
+    const uint8_t *q_res;
+    const int8_t *q_cb;
+    const uint32_t *q_off;             // [nq + 1]
+    const int8_t *q_prof;              // [alphabet][qlen] blocks as SwLaunch::q_prof, null = no profile query in the batch
+    const uint32_t *q_prof_off;        // [nq] 0xFFFFFFFF = sequence query
+    const uint32_t *q_ident;           // [nq] UINT32_MAX = none (also: outside the window)
+    const uint8_t *t_res;
+    const uint32_t *t_off4;
+    const int8_t *mat;
+    int alphabet;
+    int32_t *ident_score;              // [nq]
+};
+hipError_t launch_gscan_identity(const GscanIdentArgs &A, uint32_t nq, hipStream_t stream);
+
+struct GscanSelectArgs {
+    const mmgpu_sw_hit *out;           // the chunk's records
+    const uint32_t *order;
+    const uint32_t *q_begin, *q_count, *q_slot;
+    const uint32_t *q_ident;           // identity target inside the window, else UINT32_MAX
+    const int32_t *ident_score;
+    const int32_t *q_min_ev;           // [nq]
+    const uint32_t *t_len;
+    const uint32_t *q_win;             // [nq][2] inclusive window of target lengths
+    int32_t *scores;                   // [nq][n_targets] raw scores in id order (kept for mmgpu_gscan_debug_scores)
+    uint32_t n_targets;
+    uint32_t q_first;
+    int32_t min_score;
+    uint32_t max_hits;
+    mmgpu_pf_hit *hits;                // [nq][stride]
+    uint32_t stride;
+    uint32_t *counts;
+};
+hipError_t launch_gscan_select(const GscanSelectArgs &A, uint32_t n_queries, hipStream_t stream);
+void warm_gscan();
+
+// ---------------------------------------------------------------------------------------------------------
 // prefilter (pf_kernels.hip)
 constexpr int PF_T = 4096;             // arrival-ordered index entries per tile (2048: 22 % slower, more tiles)
 constexpr int PF_IDS_PER_BIN = 4096;   // targets per replay bin (one 16 KB LDS state table per wavefront)
@@ -729,6 +791,25 @@ hipError_t launch_block_scatter(const BlockScatterArgs &A, hipStream_t stream);
 hipError_t launch_sw_traceback(const BtLaunch &L, hipStream_t stream);
 hipError_t launch_sw_traceback_wave(const BtLaunch &L, hipStream_t stream);
 
+// the resident ids by length, longest first (counting sort; ids ascend inside a length), and where each length starts:
+// first_le[L] = position of the first target of length <= L in `order` (both scans cut their window slices out of it)
+inline void order_targets_by_length(const std::vector<uint32_t> &len, std::vector<uint32_t> &order, std::vector<uint32_t> &first_le) {
+    const uint32_t n = (uint32_t)len.size();
+    std::vector<uint32_t> start(65536 + 1, 0);      // after the prefix sum: start[k] = targets longer than 65535 - k = where length 65535 - k begins
+    for (uint32_t i = 0; i < n; i++) start[65535 - len[i] + 1]++;
+    for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
+    first_le.resize(65536);
+    for (uint32_t L = 0; L < 65536; L++) first_le[L] = start[65535 - L];
+    order.resize(n);
+    for (uint32_t i = 0; i < n; i++) order[start[65535 - len[i]]++] = i;
+}
+// positions [begin, end) of `order` whose targets have lengths in the inclusive window [lo, hi]
+inline void window_slice(const std::vector<uint32_t> &first_le, uint32_t n, uint32_t lo, uint32_t hi, uint32_t *begin, uint32_t *end) {
+    *begin = hi >= 65535u ? 0u : first_le[hi];
+    *end = lo == 0 ? n : (lo > 65535u ? 0u : first_le[lo - 1]);
+    if (*end < *begin) *end = *begin;
+}
+
 // host-side loops over targets / index entries / queries: plain std::thread chunks (the library carries no OpenMP runtime)
 inline unsigned host_threads() {
     unsigned n = std::thread::hardware_concurrency();
@@ -1010,6 +1091,9 @@ struct mmgpu_ctx {
     // largest batch and kept; scan_serial names the batch whose scores the scratch holds (mmgpu_scan_debug_scores)
     mmgpu::DevBuf scan_scores, scan_park;
     uint64_t scan_serial = 0;
+    // exhaustive gapped scan (gscan_api.hip): the [query][target] int32 scores of the last batch run, kept the same way
+    mmgpu::DevBuf gscan_scores;
+    uint64_t gscan_serial = 0;
 };
 
 // device memory for a context's long-lived buffers (targets, masked view): when the runtime is out of memory the blocks the
@@ -1062,5 +1146,9 @@ void pf_index_free(mmgpu_ctx *c);
 void db_release(mmgpu_ctx *c);      // mmgpu_api.hip: targets, masked view, index and shard description of a context
 // device-resident results of a prefilter batch that has been run (false if it has not)
 bool pf_batch_device_lists(mmgpu_pf_batch_t *b, const mmgpu_pf_hit **hits, const uint32_t **counts, uint32_t *stride, uint32_t *nq);
+// mmgpu_api.hip, for gscan_api.hip: a MMGPU_SW_SCORE_END batch over dense lists (mmgpu_sw_prepare's checks, queries, job rules and
+// kernels; target_ids / n_targets of the queries are not read), and its kernel launches without the batch's own timing events
+int sw_prepare_dense(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, const SwDenseLists &lists, mmgpu_sw_batch_t **out);
+int sw_run_dense(mmgpu_ctx *c, mmgpu_sw_batch_t *b);
 }
 #endif

@@ -145,18 +145,7 @@ int scan_marshal_queries(ScanPrepare &S) {
     return MMGPU_OK;
 }
 
-// the resident ids by length, longest first (counting sort; ids ascend inside a length), and where each length starts
-void scan_order_targets(ScanPrepare &S) {
-    const std::vector<uint32_t> &len = S.c->h_len;
-    const uint32_t n = (uint32_t)len.size();
-    std::vector<uint32_t> start(65536 + 1, 0);      // after the prefix sum: start[k] = targets longer than 65535 - k = where length 65535 - k begins
-    for (uint32_t i = 0; i < n; i++) start[65535 - len[i] + 1]++;
-    for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
-    S.first_le.resize(65536);
-    for (uint32_t L = 0; L < 65536; L++) S.first_le[L] = start[65535 - L];
-    S.order.resize(n);
-    for (uint32_t i = 0; i < n; i++) S.order[start[65535 - len[i]]++] = i;
-}
+void scan_order_targets(ScanPrepare &S) { order_targets_by_length(S.c->h_len, S.order, S.first_le); }
 
 // jobs by class; one-tile classes: SCAN_JOB_TARGETS consecutive list positions of one query, multi-tile: one round.  Inside a class
 // the jobs with the longest targets come first (they run longest; the multi-tile slots are sized by their first job).
@@ -169,8 +158,8 @@ void scan_cut_jobs(ScanPrepare &S, mmgpu_scan_batch_t *b) {
         for (int k = 0; k < SCAN_MULTI; k++)
             if (qlen <= 16u * (uint32_t)scan_class_rows(k)) { cls = k; break; }
         const uint32_t lo = S.qwin[2 * q], hi = S.qwin[2 * q + 1];
-        const uint32_t begin = hi >= 65535u ? 0u : S.first_le[hi];
-        const uint32_t end = lo == 0 ? n : (lo > 65535u ? 0u : S.first_le[lo - 1]);
+        uint32_t begin, end;
+        window_slice(S.first_le, n, lo, hi, &begin, &end);
         const uint32_t step = cls == SCAN_MULTI ? (uint32_t)SCAN_ROUND : (uint32_t)SCAN_JOB_TARGETS;
         for (uint32_t p = begin; p < end; p += std::min(step, end - p)) by_class[cls].push_back(ScanJob{q, p, std::min(end, p + step), 0});
     }

@@ -200,6 +200,32 @@ int mmgpu_scan_batch(mmgpu_ctx *, const mmgpu_scan_params *, const mmgpu_scan_qu
 int mmgpu_scan_debug_scores(mmgpu_ctx *, mmgpu_scan_batch_t *, uint32_t, uint8_t *, size_t) {
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_debug_scores: a test aid, not served through mmgpu_server");
 }
+// the exhaustive gapped scan: the binary runs gappedprefilter on the host, nothing of it crosses the socket
+int mmgpu_gscan_prepare(mmgpu_ctx *, const mmgpu_gscan_params *, const mmgpu_gscan_query *, uint32_t, mmgpu_gscan_batch_t **batch) {
+    if (batch) *batch = nullptr;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_prepare: not served through mmgpu_server (the binary runs gappedprefilter on the host)");
+}
+int mmgpu_gscan_run(mmgpu_ctx *, mmgpu_gscan_batch_t *) { return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_run: not served through mmgpu_server"); }
+int mmgpu_gscan_fetch(mmgpu_ctx *, mmgpu_gscan_batch_t *, mmgpu_pf_hit *, uint32_t, uint32_t *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_fetch: not served through mmgpu_server");
+}
+int mmgpu_gscan_fetch_device(mmgpu_ctx *, mmgpu_gscan_batch_t *, void *, uint32_t, void *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_fetch_device: not served through mmgpu_server");
+}
+int mmgpu_gscan_last_kernel_ms(mmgpu_ctx *, mmgpu_gscan_batch_t *, float *ms) {
+    if (ms) *ms = 0;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_last_kernel_ms: not served through mmgpu_server");
+}
+int mmgpu_gscan_stage_ms(mmgpu_ctx *, mmgpu_gscan_batch_t *, float *, uint32_t *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_stage_ms: not served through mmgpu_server");
+}
+void mmgpu_gscan_free(mmgpu_ctx *, mmgpu_gscan_batch_t *) {}
+int mmgpu_gscan_batch(mmgpu_ctx *, const mmgpu_gscan_params *, const mmgpu_gscan_query *, uint32_t, mmgpu_pf_hit *, uint32_t, uint32_t *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_batch: not served through mmgpu_server (the binary runs gappedprefilter on the host)");
+}
+int mmgpu_gscan_debug_scores(mmgpu_ctx *, mmgpu_gscan_batch_t *, uint32_t, int32_t *, size_t) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_debug_scores: a test aid, not served through mmgpu_server");
+}
 
 int mmgpu_sw_block_tiers(const mmgpu_sw_batch_t *, uint32_t *first_tier, uint32_t *second_tier) {
     if (first_tier) *first_tier = 0;
