@@ -514,40 +514,46 @@ class PfBatch:
             pass
 
 
-class ScanBatch:
-    """A prepared exhaustive ungapped scan (mmgpu_scan_*): queries resident in HBM."""
+class _ScanBatchBase:
+    """What the wrappers of the two exhaustive scans' batches share; a subclass names its C symbols' prefix and the dtype of a raw score."""
+    _prefix = None
+    _score_dtype = None
 
     def __init__(self, gpu, handle, keep, nq, stride):
         self.gpu, self.handle, self._keep, self.nq, self.stride = gpu, handle, keep, nq, stride
 
+    def _call(self, name, *args):
+        self.gpu._check(getattr(self.gpu.L, self._prefix + name)(self.gpu.ctx, self.handle, *args))
+
     def run(self):
-        self.gpu._check(self.gpu.L.mmgpu_scan_run(self.gpu.ctx, self.handle))
+        self._call("run")
 
     def fetch(self):
         """-> (hits[nq][stride] PF_HIT_DTYPE, counts[nq])"""
         hits = np.zeros((self.nq, max(self.stride, 1)), PF_HIT_DTYPE)
         counts = np.zeros(self.nq, np.uint32)
-        self.gpu._check(self.gpu.L.mmgpu_scan_fetch(self.gpu.ctx, self.handle, _ptr(hits), max(self.stride, 1), _ptr(counts)))
+        self._call("fetch", _ptr(hits), max(self.stride, 1), _ptr(counts))
         return hits, counts
 
     def fetch_device(self, d_hits_ptr, stride, d_counts_ptr):
         """D2D copy of the lists into caller-owned device memory (raw pointers): what sw_prepare_from_lists reads"""
-        self.gpu._check(self.gpu.L.mmgpu_scan_fetch_device(self.gpu.ctx, self.handle, c_p(d_hits_ptr), stride, c_p(d_counts_ptr)))
+        self._call("fetch_device", c_p(d_hits_ptr), stride, c_p(d_counts_ptr))
 
     def debug_scores(self, query):
-        """mmgpu_scan_debug_scores (test aid): the raw score byte of every resident target for one query of the last run"""
-        out = np.zeros(max(self.gpu.n_targets, 1), np.uint8)
-        self.gpu._check(self.gpu.L.mmgpu_scan_debug_scores(self.gpu.ctx, self.handle, int(query), _ptr(out), out.size))
+        """mmgpu_[g]scan_debug_scores (test aid): the raw score (a byte; the gapped scan's: an int32) of every resident target for one
+        query of the last run"""
+        out = np.zeros(max(self.gpu.n_targets, 1), self._score_dtype)
+        self._call("debug_scores", int(query), _ptr(out), out.size)
         return out[:self.gpu.n_targets]
 
     def kernel_ms(self):
         ms = ctypes.c_float()
-        self.gpu._check(self.gpu.L.mmgpu_scan_last_kernel_ms(self.gpu.ctx, self.handle, ctypes.byref(ms)))
+        self._call("last_kernel_ms", ctypes.byref(ms))
         return ms.value
 
     def free(self):
         if self.handle is not None:
-            self.gpu.L.mmgpu_scan_free(self.gpu.ctx, self.handle)
+            getattr(self.gpu.L, self._prefix + "free")(self.gpu.ctx, self.handle)
             self.handle = None
 
     def __del__(self):
@@ -557,54 +563,21 @@ class ScanBatch:
             pass
 
 
-class GscanBatch:
+class ScanBatch(_ScanBatchBase):
+    """A prepared exhaustive ungapped scan (mmgpu_scan_*): queries resident in HBM."""
+    _prefix, _score_dtype = "mmgpu_scan_", np.uint8
+
+
+class GscanBatch(_ScanBatchBase):
     """A prepared exhaustive gapped scan (mmgpu_gscan_*): queries resident in HBM."""
-
-    def __init__(self, gpu, handle, keep, nq, stride):
-        self.gpu, self.handle, self._keep, self.nq, self.stride = gpu, handle, keep, nq, stride
-
-    def run(self):
-        self.gpu._check(self.gpu.L.mmgpu_gscan_run(self.gpu.ctx, self.handle))
-
-    def fetch(self):
-        """-> (hits[nq][stride] PF_HIT_DTYPE, counts[nq])"""
-        hits = np.zeros((self.nq, max(self.stride, 1)), PF_HIT_DTYPE)
-        counts = np.zeros(self.nq, np.uint32)
-        self.gpu._check(self.gpu.L.mmgpu_gscan_fetch(self.gpu.ctx, self.handle, _ptr(hits), max(self.stride, 1), _ptr(counts)))
-        return hits, counts
-
-    def fetch_device(self, d_hits_ptr, stride, d_counts_ptr):
-        """D2D copy of the lists into caller-owned device memory (raw pointers): what sw_prepare_from_lists reads"""
-        self.gpu._check(self.gpu.L.mmgpu_gscan_fetch_device(self.gpu.ctx, self.handle, c_p(d_hits_ptr), stride, c_p(d_counts_ptr)))
-
-    def debug_scores(self, query):
-        """mmgpu_gscan_debug_scores (test aid): the raw int32 score of every resident target for one query of the last run"""
-        out = np.zeros(max(self.gpu.n_targets, 1), np.int32)
-        self.gpu._check(self.gpu.L.mmgpu_gscan_debug_scores(self.gpu.ctx, self.handle, int(query), _ptr(out), out.size))
-        return out[:self.gpu.n_targets]
-
-    def kernel_ms(self):
-        ms = ctypes.c_float()
-        self.gpu._check(self.gpu.L.mmgpu_gscan_last_kernel_ms(self.gpu.ctx, self.handle, ctypes.byref(ms)))
-        return ms.value
+    _prefix, _score_dtype = "mmgpu_gscan_", np.int32
 
     def stage_ms(self):
         """-> (dict planner / sw / identity / select in ms, chunks) of the last run"""
         ms = (ctypes.c_float * 4)()
         n = ctypes.c_uint32()
-        self.gpu._check(self.gpu.L.mmgpu_gscan_stage_ms(self.gpu.ctx, self.handle, ms, ctypes.byref(n)))
+        self._call("stage_ms", ms, ctypes.byref(n))
         return dict(planner=ms[0], sw=ms[1], identity=ms[2], select=ms[3]), n.value
-
-    def free(self):
-        if self.handle is not None:
-            self.gpu.L.mmgpu_gscan_free(self.gpu.ctx, self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 class SwBatch:
@@ -1073,6 +1046,26 @@ class MMGpu:
         b.free()
         return out
 
+    @staticmethod
+    def _scan_query_fields(qd, q_required):
+        """What the two scans' marshals check alike in one query dict -> (q, qlen, comp_bias, profile, identity_id, min_tlen, max_tlen);
+        q_required: the gapped scan needs q (a profile query's consensus), the ungapped one takes a profile query without it"""
+        prof = None if qd.get("profile") is None else np.ascontiguousarray(qd["profile"], np.int8)
+        if prof is not None and prof.ndim != 2:
+            raise ValueError("profile must be [letters][qlen]")
+        q = np.ascontiguousarray(qd["q"], np.uint8) if q_required or qd.get("q") is not None else None
+        if q is None and prof is None:
+            raise ValueError("a query needs q or profile")
+        qlen = prof.shape[1] if q is None else len(q)
+        if prof is not None and prof.shape[1] != qlen:
+            raise ValueError("profile must be [letters][qlen]")
+        cb = None if qd.get("comp_bias") is None else np.ascontiguousarray(qd["comp_bias"], np.int8)
+        if cb is not None and len(cb) != qlen:
+            raise ValueError("comp_bias must have the query's length")
+        ident = qd.get("identity_id")
+        lo, hi = qd.get("window") or (0, 0xFFFFFFFF)
+        return q, qlen, cb, prof, 0xFFFFFFFF if ident is None else int(ident), int(lo), int(hi)
+
     def _scan_marshal(self, mat, queries, min_score, max_hits):
         """queries: list of dicts {q: uint8[], comp_bias: int8[]|None (rounded), identity_id: int|None, window: (min_tlen, max_tlen)|None,
         profile: int8[letters][qlen]|None (profile query: Sequence::getAlignmentProfile; q may then be absent, the library ignores comp_bias)}"""
@@ -1081,41 +1074,33 @@ class MMGpu:
         arr = (ScanQuery * max(len(queries), 1))()
         keep = [mat]
         for i, qd in enumerate(queries):
-            prof = None if qd.get("profile") is None else np.ascontiguousarray(qd["profile"], np.int8)
-            if prof is not None and prof.ndim != 2:
-                raise ValueError("profile must be [letters][qlen]")
-            q = None if qd.get("q") is None else np.ascontiguousarray(qd["q"], np.uint8)
-            if q is None and prof is None:
-                raise ValueError("a query needs q or profile")
-            qlen = prof.shape[1] if prof is not None else len(q)
-            if q is not None and len(q) != qlen:
-                raise ValueError("profile must be [letters][qlen]")
-            cb = None if qd.get("comp_bias") is None else np.ascontiguousarray(qd["comp_bias"], np.int8)
-            if cb is not None and len(cb) != qlen:
-                raise ValueError("comp_bias must have the query's length")
-            ident = qd.get("identity_id")
-            lo, hi = qd.get("window") or (0, 0xFFFFFFFF)
+            q, qlen, cb, prof, ident, lo, hi = self._scan_query_fields(qd, q_required=False)
             keep += [q, cb, prof]
-            arr[i] = ScanQuery(_ptr(q), qlen, _ptr(cb), 0xFFFFFFFF if ident is None else int(ident), int(lo), int(hi), _ptr(prof),
-                               0 if prof is None else prof.shape[0])
+            arr[i] = ScanQuery(_ptr(q), qlen, _ptr(cb), ident, lo, hi, _ptr(prof), 0 if prof is None else prof.shape[0])
         return par, arr, keep
+
+    def _scan_prepare(self, batch_cls, marshalled, nq, max_hits):
+        par, arr, keep = marshalled
+        h = c_p()
+        self._check(getattr(self.L, batch_cls._prefix + "prepare")(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), nq, ctypes.byref(h)))
+        return batch_cls(self, h, keep, nq, min(int(max_hits), self.n_targets))
+
+    def _scan_batch(self, batch_cls, marshalled, nq, max_hits):
+        par, arr, keep = marshalled
+        stride = max(min(int(max_hits), getattr(self, "n_targets", 0)), 1)
+        hits = np.zeros((max(nq, 1), stride), PF_HIT_DTYPE)
+        counts = np.zeros(max(nq, 1), np.uint32)
+        self._check(getattr(self.L, batch_cls._prefix + "batch")(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), nq, _ptr(hits), stride, _ptr(counts)))
+        del keep
+        return hits[:nq], counts[:nq]
 
     def scan_prepare(self, mat, queries, min_score=15, max_hits=300):
         """mmgpu_scan_prepare: the exhaustive ungapped scan (`ungappedprefilter`) of sequence and profile queries over the resident targets"""
-        par, arr, keep = self._scan_marshal(mat, queries, min_score, max_hits)
-        h = c_p()
-        self._check(self.L.mmgpu_scan_prepare(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), ctypes.byref(h)))
-        return ScanBatch(self, h, keep, len(queries), min(int(max_hits), self.n_targets))
+        return self._scan_prepare(ScanBatch, self._scan_marshal(mat, queries, min_score, max_hits), len(queries), max_hits)
 
     def scan_batch(self, mat, queries, min_score=15, max_hits=300):
         """mmgpu_scan_batch: -> (hits[nq][stride], counts[nq])"""
-        par, arr, keep = self._scan_marshal(mat, queries, min_score, max_hits)
-        stride = max(min(int(max_hits), getattr(self, "n_targets", 0)), 1)
-        hits = np.zeros((max(len(queries), 1), stride), PF_HIT_DTYPE)
-        counts = np.zeros(max(len(queries), 1), np.uint32)
-        self._check(self.L.mmgpu_scan_batch(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), _ptr(hits), stride, _ptr(counts)))
-        del keep
-        return hits[:len(queries)], counts[:len(queries)]
+        return self._scan_batch(ScanBatch, self._scan_marshal(mat, queries, min_score, max_hits), len(queries), max_hits)
 
     def _gscan_marshal(self, mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget):
         """queries: list of dicts {q: uint8[] (a profile query: the consensus), comp_bias: int8[]|None (rounded), identity_id: int|None,
@@ -1125,38 +1110,21 @@ class MMGpu:
         arr = (GscanQuery * max(len(queries), 1))()
         keep = [mat]
         for i, qd in enumerate(queries):
-            prof = None if qd.get("profile") is None else np.ascontiguousarray(qd["profile"], np.int8)
-            if prof is not None and prof.ndim != 2:
-                raise ValueError("profile must be [letters][qlen]")
-            q = np.ascontiguousarray(qd["q"], np.uint8)
-            if prof is not None and prof.shape[1] != len(q):
-                raise ValueError("profile must be [letters][qlen]")
-            cb = None if qd.get("comp_bias") is None else np.ascontiguousarray(qd["comp_bias"], np.int8)
-            if cb is not None and len(cb) != len(q):
-                raise ValueError("comp_bias must have the query's length")
-            ident = qd.get("identity_id")
-            lo, hi = qd.get("window") or (0, 0xFFFFFFFF)
+            q, qlen, cb, prof, ident, lo, hi = self._scan_query_fields(qd, q_required=True)
             keep += [q, cb, prof]
-            arr[i] = GscanQuery(_ptr(q), len(q), _ptr(cb), _ptr(prof), 0 if prof is None else prof.shape[0],
-                                0xFFFFFFFF if ident is None else int(ident), int(lo), int(hi), int(qd.get("min_evalue_score") or 0))
+            arr[i] = GscanQuery(_ptr(q), qlen, _ptr(cb), _ptr(prof), 0 if prof is None else prof.shape[0], ident, lo, hi,
+                                int(qd.get("min_evalue_score") or 0))
         return par, arr, keep
 
     def gscan_prepare(self, mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, pair_budget=0):
         """mmgpu_gscan_prepare: the exhaustive gapped scan (`gappedprefilter`) of sequence and profile queries over the resident targets"""
-        par, arr, keep = self._gscan_marshal(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
-        h = c_p()
-        self._check(self.L.mmgpu_gscan_prepare(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), ctypes.byref(h)))
-        return GscanBatch(self, h, keep, len(queries), min(int(max_hits), self.n_targets))
+        m = self._gscan_marshal(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
+        return self._scan_prepare(GscanBatch, m, len(queries), max_hits)
 
     def gscan_batch(self, mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, pair_budget=0):
         """mmgpu_gscan_batch: -> (hits[nq][stride], counts[nq])"""
-        par, arr, keep = self._gscan_marshal(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
-        stride = max(min(int(max_hits), getattr(self, "n_targets", 0)), 1)
-        hits = np.zeros((max(len(queries), 1), stride), PF_HIT_DTYPE)
-        counts = np.zeros(max(len(queries), 1), np.uint32)
-        self._check(self.L.mmgpu_gscan_batch(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), _ptr(hits), stride, _ptr(counts)))
-        del keep
-        return hits[:len(queries)], counts[:len(queries)]
+        m = self._gscan_marshal(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
+        return self._scan_batch(GscanBatch, m, len(queries), max_hits)
 
     def pf_set_shard(self, n_shards, shard, global_db_size, global_ids, shard_of, local_id):
         """this context holds shard `shard` of a database of global_db_size targets (None-like: pf_clear_shard)"""
@@ -1217,14 +1185,9 @@ class MMGpu:
                                                  c_p(d_out_hits_ptr), c_p(d_out_counts_ptr)))
 
 
-def exhaustive_search(gpu, scan_mat, sw_mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, mode=1):
-    """Exhaustive search on one device without a list leaving it: scan_prepare + run, fetch_device into a device buffer,
-    sw_prepare_from_lists over it, run, fetch.  queries: dicts with q, comp_bias (rounded int8 or None; the same bias serves both
-    stages, as ssw_init computes it once), identity_id, window, min_start_score; a profile query adds profile (int8 [letters][qlen],
-    read by both stages, which then ignore comp_bias) and keeps q = its consensus sequence, which the alignment stage needs.
-    -> (hits[nq][stride], counts[nq], records[nq][stride] SW_HIT_DTYPE: slot k of a row = hit k of the query's list)"""
+def _search_over_lists(gpu, scan, sw_mat, gap_open, gap_extend, queries, mode):
+    """run a prepared scan, hand its lists over on the device to an alignment batch, run and fetch both; frees the scan"""
     import torch
-    scan = gpu.scan_prepare(scan_mat, queries, min_score, max_hits)
     scan.run()
     stride = max(scan.stride, 1)
     d_hits = torch.zeros(len(queries) * stride * PF_HIT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
@@ -1242,28 +1205,23 @@ def exhaustive_search(gpu, scan_mat, sw_mat, gap_open, gap_extend, queries, min_
     return hits, counts, rec
 
 
+def exhaustive_search(gpu, scan_mat, sw_mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, mode=1):
+    """Exhaustive search on one device without a list leaving it: scan_prepare + run, fetch_device into a device buffer,
+    sw_prepare_from_lists over it, run, fetch.  queries: dicts with q, comp_bias (rounded int8 or None; the same bias serves both
+    stages, as ssw_init computes it once), identity_id, window, min_start_score; a profile query adds profile (int8 [letters][qlen],
+    read by both stages, which then ignore comp_bias) and keeps q = its consensus sequence, which the alignment stage needs.
+    -> (hits[nq][stride], counts[nq], records[nq][stride] SW_HIT_DTYPE: slot k of a row = hit k of the query's list)"""
+    scan = gpu.scan_prepare(scan_mat, queries, min_score, max_hits)
+    return _search_over_lists(gpu, scan, sw_mat, gap_open, gap_extend, queries, mode)
+
+
 def exhaustive_gapped_search(gpu, mat, gap_open, gap_extend, queries, min_score=15, max_hits=300, mode=1, pair_budget=0):
     """The gapped counterpart of exhaustive_search: gscan_prepare + run, fetch_device into a device buffer, sw_prepare_from_lists over
     it (start positions with mode 1), run, fetch.  One matrix serves both stages (both are the Gotoh alignment).  queries: dicts with
     q, comp_bias, identity_id, window, min_evalue_score, min_start_score, profile.
     -> (hits[nq][stride], counts[nq], records[nq][stride] SW_HIT_DTYPE: slot k of a row = hit k of the query's list)"""
-    import torch
     scan = gpu.gscan_prepare(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
-    scan.run()
-    stride = max(scan.stride, 1)
-    d_hits = torch.zeros(len(queries) * stride * PF_HIT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-    d_counts = torch.zeros(len(queries), dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()      # (the buffers are zeroed on torch's stream, filled on the context's)
-    scan.fetch_device(d_hits.data_ptr(), stride, d_counts.data_ptr())
-    sw = gpu.sw_prepare_from_lists(mat, gap_open, gap_extend, queries, d_hits.data_ptr(), d_counts.data_ptr(), stride, mode=mode)
-    sw.run()
-    rec = sw.fetch().reshape(len(queries), stride)
-    hits, counts = scan.fetch()
-    sw.free()
-    scan.free()
-    gpu.synchronize()
-    del d_hits, d_counts
-    return hits, counts, rec
+    return _search_over_lists(gpu, scan, mat, gap_open, gap_extend, queries, mode)
 
 
 def alt_next_spans(spans, records, accepted):

@@ -1,6 +1,8 @@
-// Host side of the exhaustive gapped scan (include/mmgpu.h, "exhaustive gapped scan"): validation, the window slices and chunks, one
-// dense alignment batch per chunk (sw_prepare_dense: the checks, queries, job rules and kernels of mmgpu_sw_prepare), launches of
-// gscan_kernel.hip around them.  prepare and run are sequences of named steps over one record each, in the manner of scan_api.hip.
+// Host side of the exhaustive gapped scan (include/mmgpu.h, "exhaustive gapped scan"): the scan's own validation, the window slices and
+// chunks, one dense alignment batch per chunk (sw_prepare_dense: the checks, queries, job rules and kernels of mmgpu_sw_prepare), launches
+// of gscan_kernel.hip around them.  prepare and run are sequences of named steps over one record each, in the manner of scan_api.hip.
+// What a batch holds and does like the ungapped scan's is scan_common.hip's; the entry points here name themselves and call it.  Its
+// own: the alignment batches, which only release(ctx) can free.
 #include <algorithm>
 #include <array>
 #include <cstring>
@@ -11,14 +13,8 @@
 
 using namespace mmgpu;
 
-struct mmgpu_gscan_batch_t {
-    uint32_t nq = 0, n_targets = 0, max_hits = 0, stride = 0;
-    int32_t min_score = 0;
-    int alphabet = 0;
+struct mmgpu_gscan_batch_t : ScanBatchCommon {
     bool any_profile = false;
-    const uint8_t *db_res = nullptr;      // the resident database the batch was prepared against (a reload invalidates the batch)
-    uint64_t serial = 0;                  // names this batch in mmgpu_ctx::gscan_serial
-    bool ran = false;
     // a chunk: queries [q_first, q_first + nq) and their alignment batch over the shared lists and records
     struct Chunk {
         uint32_t q_first = 0, nq = 0;
@@ -27,11 +23,10 @@ struct mmgpu_gscan_batch_t {
         std::array<hipEvent_t, 4> ev = {};      // before the planner, before the alignment kernels, before the selection, after it
     };
     std::vector<Chunk> chunks;
-    DevBuf d_qres, d_qcb, d_qoff, d_qprof, d_qprof_off, d_mat, d_qident, d_qwin, d_qminev, d_order, d_qbegin, d_qcount, d_qslot, d_ident_score,
-        d_hits, d_counts;
+    DevBuf d_qres, d_qcb, d_qoff, d_qprof, d_qprof_off, d_qident, d_qwin, d_qminev, d_order, d_qbegin, d_qcount, d_qslot, d_ident_score;
     DevBuf d_hit_target, d_hit_out, d_out;      // the largest chunk's lists and records, reused by every chunk
-    hipEvent_t ev0 = nullptr, ev_ident = nullptr, ev1 = nullptr;
-    // the alignment batches and events go here, not in a destructor: freeing an alignment batch needs the context
+    hipEvent_t ev_ident = nullptr;      // behind the identity kernel
+    // the alignment batches and their events go here, not in a destructor: freeing an alignment batch needs the context
     void release(mmgpu_ctx *c) {
         for (Chunk &k : chunks) {
             if (k.sw) mmgpu_sw_free(c, k.sw);
@@ -39,10 +34,8 @@ struct mmgpu_gscan_batch_t {
                 if (e) (void)hipEventDestroy(e);
         }
         chunks.clear();
-        for (hipEvent_t *e : {&ev0, &ev_ident, &ev1}) {
-            if (*e) (void)hipEventDestroy(*e);
-            *e = nullptr;
-        }
+        if (ev_ident) (void)hipEventDestroy(ev_ident);
+        ev_ident = nullptr;
     }
 };
 
@@ -78,16 +71,10 @@ struct GscanPrepare {
 };
 
 int gscan_check_call(const GscanPrepare &S) {
-    const mmgpu_ctx *c = S.c;
-    if (!S.par || !S.qs || S.nq == 0 || !S.par->mat) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_prepare: NULL argument or no queries");
-    if (!c->db.res || c->db.n == 0) return fail(MMGPU_ERR_STATE, "mmgpu_gscan_prepare: no targets loaded");
-    if (c->shard.on) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_prepare: the context holds a shard of a multi-GPU run");
-    if (S.par->alphabet != c->db.alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_prepare: alphabet differs from the loaded targets");
-    if (S.par->max_hits == 0) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_prepare: max_hits must be >= 1");
-    if (S.par->max_hits > MMGPU_PF_MAX_FUSED_HITS) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_prepare: max_hits above MMGPU_PF_MAX_FUSED_HITS");
-    if ((uint64_t)S.nq * c->db.n > (1ull << 30))
-        return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_prepare: more than 4 GiB of scores (queries x resident targets x 4 bytes): send smaller batches");
-    return MMGPU_OK;
+    const char *who = "mmgpu_gscan_prepare";
+    const int rc = scan_check_db(who, S.c, S.par && S.qs && S.nq && S.par->mat, S.par ? S.par->alphabet : 0);
+    if (rc != MMGPU_OK) return rc;
+    return scan_check_size(who, S.c, S.nq, S.par->max_hits, sizeof(int32_t));
 }
 
 // every query's slice of the length-ordered id list and its identity target: inside the window it must have the query's length
@@ -204,16 +191,14 @@ int gscan_upload(GscanPrepare &S) {
     mmgpu_ctx *c = S.c;
     mmgpu_gscan_batch_t *b = S.b;
     hipStream_t s = c->stream;
-    for (DevBuf *d : {&b->d_qres, &b->d_qcb, &b->d_qoff, &b->d_qprof, &b->d_qprof_off, &b->d_mat, &b->d_qident, &b->d_qwin, &b->d_qminev,
-                      &b->d_order, &b->d_qbegin, &b->d_qcount, &b->d_qslot, &b->d_ident_score, &b->d_hits, &b->d_counts})
+    for (DevBuf *d : {&b->d_qres, &b->d_qcb, &b->d_qoff, &b->d_qprof, &b->d_qprof_off, &b->d_qident, &b->d_qwin, &b->d_qminev, &b->d_order,
+                      &b->d_qbegin, &b->d_qcount, &b->d_qslot, &b->d_ident_score})
         d->bind(c->cache);
-    std::vector<int8_t> mat(S.par->mat, S.par->mat + (size_t)S.par->alphabet * S.par->alphabet);
     HIP_TRY(upload(b->d_qres, S.qres, s));
     HIP_TRY(upload(b->d_qcb, S.qcb, s));
     HIP_TRY(upload(b->d_qoff, S.qoff, s));
     HIP_TRY(upload(b->d_qprof, S.qprof, s));
     HIP_TRY(upload(b->d_qprof_off, S.qprof_off, s));
-    HIP_TRY(upload(b->d_mat, mat, s));
     HIP_TRY(upload(b->d_qident, S.qident, s));
     HIP_TRY(upload(b->d_qwin, S.qwin, s));
     HIP_TRY(upload(b->d_qminev, S.qminev, s));
@@ -222,10 +207,7 @@ int gscan_upload(GscanPrepare &S) {
     HIP_TRY(upload(b->d_qcount, S.qcount, s));
     HIP_TRY(upload(b->d_qslot, S.qslot, s));
     HIP_TRY(b->d_ident_score.alloc((size_t)b->nq * sizeof(int32_t)));
-    HIP_TRY(b->d_hits.alloc((size_t)b->nq * b->stride * sizeof(mmgpu_pf_hit)));
-    HIP_TRY(b->d_counts.alloc((size_t)b->nq * sizeof(uint32_t)));
-    HIP_TRY(hipStreamSynchronize(s));      // the host vectors go with this call
-    return MMGPU_OK;
+    return scan_upload_common(c, b, S.par->mat);
 }
 
 int gscan_prepare_impl(mmgpu_ctx *c, const mmgpu_gscan_params *par, const mmgpu_gscan_query *qs, uint32_t nq, mmgpu_gscan_batch_t **out) {
@@ -235,14 +217,7 @@ int gscan_prepare_impl(mmgpu_ctx *c, const mmgpu_gscan_params *par, const mmgpu_
     HIP_TRY(hipSetDevice(c->device));
     std::unique_ptr<mmgpu_gscan_batch_t, GscanBatchFree> b(new mmgpu_gscan_batch_t(), GscanBatchFree{c});
     S.b = b.get();
-    b->nq = nq;
-    b->n_targets = c->db.n;
-    b->max_hits = par->max_hits;
-    b->stride = std::min(par->max_hits, c->db.n);
-    b->min_score = par->min_score;
-    b->alphabet = par->alphabet;
-    b->db_res = c->db.res;
-    b->serial = ++g_gscan_serial;
+    scan_fill_header(b.get(), c, nq, par->alphabet, par->min_score, par->max_hits, ++g_gscan_serial);
     rc = gscan_slices(S);
     if (rc != MMGPU_OK) return rc;
     gscan_cut_chunks(S);
@@ -318,13 +293,6 @@ int gscan_launch_chunk(mmgpu_ctx *c, mmgpu_gscan_batch_t *b, mmgpu_gscan_batch_t
     return MMGPU_OK;
 }
 
-int gscan_check_batch(const char *who, const mmgpu_ctx *c, const mmgpu_gscan_batch_t *b, bool must_have_run) {
-    if (!c || !b) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
-    if (b->db_res != c->db.res || b->n_targets != c->db.n) return fail(MMGPU_ERR_STATE, std::string(who) + ": the targets were reloaded since the batch was prepared");
-    if (must_have_run && !b->ran) return fail(MMGPU_ERR_STATE, std::string(who) + ": the batch has not been run");
-    return MMGPU_OK;
-}
-
 }  // namespace
 
 extern "C" int mmgpu_gscan_prepare(mmgpu_ctx *c, const mmgpu_gscan_params *par, const mmgpu_gscan_query *qs, uint32_t nq,
@@ -335,7 +303,7 @@ extern "C" int mmgpu_gscan_prepare(mmgpu_ctx *c, const mmgpu_gscan_params *par, 
 }
 
 extern "C" int mmgpu_gscan_run(mmgpu_ctx *c, mmgpu_gscan_batch_t *b) {
-    int rc = gscan_check_batch("mmgpu_gscan_run", c, b, false);
+    int rc = scan_check_batch("mmgpu_gscan_run", c, b, false);
     if (rc != MMGPU_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t score_bytes = (size_t)b->nq * b->n_targets * sizeof(int32_t);
@@ -356,42 +324,19 @@ extern "C" int mmgpu_gscan_run(mmgpu_ctx *c, mmgpu_gscan_batch_t *b) {
 }
 
 extern "C" int mmgpu_gscan_fetch(mmgpu_ctx *c, mmgpu_gscan_batch_t *b, mmgpu_pf_hit *hits, uint32_t hit_stride, uint32_t *counts) {
-    int rc = gscan_check_batch("mmgpu_gscan_fetch", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (!hits || !counts) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_fetch: NULL argument");
-    if (hit_stride < b->stride) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_fetch: hit_stride below min(max_hits, resident targets)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy2DAsync(hits, (size_t)hit_stride * sizeof(mmgpu_pf_hit), b->d_hits.p, (size_t)b->stride * sizeof(mmgpu_pf_hit),
-                             (size_t)b->stride * sizeof(mmgpu_pf_hit), b->nq, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(counts, b->d_counts.p, (size_t)b->nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MMGPU_OK;
+    return scan_fetch_lists("mmgpu_gscan_fetch", c, b, hits, hit_stride, counts, hipMemcpyDeviceToHost);
 }
 
 extern "C" int mmgpu_gscan_fetch_device(mmgpu_ctx *c, mmgpu_gscan_batch_t *b, void *d_hits, uint32_t hit_stride, void *d_counts) {
-    int rc = gscan_check_batch("mmgpu_gscan_fetch_device", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (!d_hits || !d_counts) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_fetch_device: NULL argument");
-    if (hit_stride < b->stride) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_fetch_device: hit_stride below min(max_hits, resident targets)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy2DAsync(d_hits, (size_t)hit_stride * sizeof(mmgpu_pf_hit), b->d_hits.p, (size_t)b->stride * sizeof(mmgpu_pf_hit),
-                             (size_t)b->stride * sizeof(mmgpu_pf_hit), b->nq, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_counts, b->d_counts.p, (size_t)b->nq * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    return MMGPU_OK;
+    return scan_fetch_lists("mmgpu_gscan_fetch_device", c, b, d_hits, hit_stride, d_counts, hipMemcpyDeviceToDevice);
 }
 
 extern "C" int mmgpu_gscan_last_kernel_ms(mmgpu_ctx *c, mmgpu_gscan_batch_t *b, float *ms) {
-    int rc = gscan_check_batch("mmgpu_gscan_last_kernel_ms", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (!ms) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_last_kernel_ms: NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(b->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, b->ev0, b->ev1));
-    return MMGPU_OK;
+    return scan_kernel_ms("mmgpu_gscan_last_kernel_ms", c, b, ms);
 }
 
 extern "C" int mmgpu_gscan_stage_ms(mmgpu_ctx *c, mmgpu_gscan_batch_t *b, float ms[4], uint32_t *n_chunks) {
-    int rc = gscan_check_batch("mmgpu_gscan_stage_ms", c, b, true);
+    int rc = scan_check_batch("mmgpu_gscan_stage_ms", c, b, true);
     if (rc != MMGPU_OK) return rc;
     if (!ms) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_stage_ms: NULL argument");
     HIP_TRY(hipSetDevice(c->device));
@@ -412,10 +357,7 @@ extern "C" int mmgpu_gscan_stage_ms(mmgpu_ctx *c, mmgpu_gscan_batch_t *b, float 
 
 extern "C" void mmgpu_gscan_free(mmgpu_ctx *c, mmgpu_gscan_batch_t *b) {
     if (!b) return;
-    if (c) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-    }
+    scan_sync_for_free(c);
     b->release(c);
     delete b;
 }
@@ -432,13 +374,6 @@ extern "C" int mmgpu_gscan_batch(mmgpu_ctx *c, const mmgpu_gscan_params *par, co
 }
 
 extern "C" int mmgpu_gscan_debug_scores(mmgpu_ctx *c, mmgpu_gscan_batch_t *b, uint32_t query, int32_t *out, size_t cap) {
-    int rc = gscan_check_batch("mmgpu_gscan_debug_scores", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (c->gscan_serial != b->serial) return fail(MMGPU_ERR_STATE, "mmgpu_gscan_debug_scores: another gapped scan batch has run on the context since");
-    if (!out || query >= b->nq || cap < b->n_targets) return fail(MMGPU_ERR_ARG, "mmgpu_gscan_debug_scores: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, c->gscan_scores.as<int32_t>() + (size_t)query * b->n_targets, (size_t)b->n_targets * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MMGPU_OK;
+    return scan_debug_scores("mmgpu_gscan_debug_scores", "gapped scan", c, b, &mmgpu_ctx::gscan_serial, &mmgpu_ctx::gscan_scores, sizeof(int32_t),
+                             query, out, cap);
 }

@@ -7,17 +7,16 @@
 //  * the selection kernel, one workgroup per query: it spreads the chunk's records into the query's row of the [query][target]
 //    score array (id order, 0 outside the window, the identity score over the aligned one), then builds the list out of the row:
 //    keys k = 32767 - score in [0, 65535]; a 256-bin histogram of k >> 8 finds the bin the cut falls into, one of k & 255 inside that
-//    bin the cut key; compaction in id order with ballot prefix sums takes every key below the cut and the first ids of the cut
-//    class; at most GSCAN_MAX_HITS keys (k << 32 | id) are sorted in LDS.  The histograms' atomics only count.
+//    bin the cut key; compaction, sort and the write of the list are select_device.h's, shared with scan_kernel.hip.  The
+//    histograms' atomics only count.
 #include "mmgpu_internal.h"
+#include "select_device.h"
 
 namespace mmgpu {
 
 namespace {
 
 constexpr int PLAN_THREADS = 256;
-constexpr int SELECT_THREADS = 1024;
-static_assert(GSCAN_MAX_HITS == MMGPU_PF_MAX_FUSED_HITS, "the selection kernel sorts every list the C-ABI admits");
 
 __global__ __launch_bounds__(PLAN_THREADS) void gscan_plan_kernel(GscanPlanArgs A) {
     for (uint32_t ql = blockIdx.y; ql < A.n_queries; ql += gridDim.y) {
@@ -54,12 +53,11 @@ __global__ __launch_bounds__(64) void gscan_identity_kernel(GscanIdentArgs A) {
 }
 
 __global__ __launch_bounds__(SELECT_THREADS) void gscan_select_kernel(GscanSelectArgs A) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned long long keys[GSCAN_MAX_HITS];
-    __shared__ unsigned wsum[2][2][SELECT_THREADS / 64];
+    __shared__ unsigned hist[SELECT_BINS];
+    __shared__ SelectLds lds;
     __shared__ unsigned s_bin, s_above, s_cut, s_need;
     const uint32_t q = A.q_first + blockIdx.x;
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const unsigned tid = threadIdx.x;
     const uint32_t n = A.n_targets;
     int32_t *row = A.scores + (size_t)q * n;
     const uint32_t ident = A.q_ident[q], lo = A.q_win[2 * q], hi = A.q_win[2 * q + 1];
@@ -74,7 +72,7 @@ __global__ __launch_bounds__(SELECT_THREADS) void gscan_select_kernel(GscanSelec
     for (uint32_t p = tid; p < count; p += SELECT_THREADS) row[A.order[begin + p]] = A.out[(size_t)slot + p].score;
     __syncthreads();
     if (tid == 0 && ident != 0xFFFFFFFFu) row[ident] = A.ident_score[q];
-    if (tid < 256) hist[tid] = 0;
+    if (tid < SELECT_BINS) hist[tid] = 0;
     __syncthreads();
 
     // admitted: inside the window, and the query's own target or past both thresholds
@@ -89,102 +87,37 @@ __global__ __launch_bounds__(SELECT_THREADS) void gscan_select_kernel(GscanSelec
     __syncthreads();
     if (tid == 0) {
         unsigned total = 0;
-        for (int b = 0; b < 256; b++) total += hist[b];
-        unsigned bin = 256, above = 0;
-        if (total > A.max_hits) {      // the high byte the cut falls into
-            for (unsigned b = 0; b < 256; b++) {
-                if (above + hist[b] >= A.max_hits) { bin = b; break; }
-                above += hist[b];
-            }
-        }
-        s_bin = bin;
-        s_above = above;
+        for (int b = 0; b < SELECT_BINS; b++) total += hist[b];
+        SelectCut c = {SELECT_BINS, 0};
+        if (total > A.max_hits) c = select_cut_walk(hist, 0, A.max_hits);      // the high byte the cut falls into
+        s_bin = c.bin;
+        s_above = c.above;
         s_cut = 65536u;      // no cut: every admitted key is below it
         s_need = 0;
     }
     __syncthreads();
     const unsigned bin = s_bin;
-    if (bin < 256u) {      // (uniform over the workgroup) the low byte inside that bin, and how many of the cut class's lowest ids are kept
-        if (tid < 256) hist[tid] = 0;
+    if (bin < (unsigned)SELECT_BINS) {      // (uniform over the workgroup) the low byte inside that bin, and how many of the cut class's lowest ids are kept
+        if (tid < SELECT_BINS) hist[tid] = 0;
         __syncthreads();
         for (uint64_t i = tid; i < n; i += SELECT_THREADS) {
             const int s = row[i];
             const unsigned k = (unsigned)(32767 - s);
-            if ((k >> 8) == bin && admitted(i, s)) atomicAdd(&hist[k & 255u], 1u);
+            if ((k >> 8) == bin && admitted(i, s)) atomicAdd(&hist[k & 255u], 1u);      // (the lengths are read for that bin's targets only)
         }
         __syncthreads();
         if (tid == 0) {
-            unsigned above = s_above;
-            for (unsigned b = 0; b < 256; b++) {
-                if (above + hist[b] >= A.max_hits) { s_cut = (bin << 8) | b; s_need = A.max_hits - above; break; }
-                above += hist[b];
-            }
+            const SelectCut c = select_cut_walk(hist, s_above, A.max_hits);
+            if (c.bin < (unsigned)SELECT_BINS) { s_cut = (bin << 8) | c.bin; s_need = A.max_hits - c.above; }
         }
         __syncthreads();
     }
-    const unsigned cut = s_cut, need = s_need;
-
-    // compaction in id order: everything below the cut key, the first `need` of the cut class
-    unsigned cbase = 0, obase = 0;
-    unsigned par = 0;
-    for (uint64_t start = 0; start < n; start += SELECT_THREADS, par ^= 1u) {
-        const uint64_t i = start + tid;
-        unsigned k = 0;
-        bool adm = false;
-        if (i < n) {
-            const int s = row[i];
-            k = (unsigned)(32767 - s);
-            adm = admitted(i, s);
-        }
-        const bool isA = adm && k < cut, isC = adm && k == cut;
-        const unsigned long long bA = __ballot(isA), bC = __ballot(isC);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (lane == 0) { wsum[par][0][wv] = (unsigned)__popcll(bA); wsum[par][1][wv] = (unsigned)__popcll(bC); }
-        __syncthreads();
-        unsigned a_before = (unsigned)__popcll(bA & below), c_before = (unsigned)__popcll(bC & below), a_tot = 0, c_tot = 0;
-        for (unsigned w = 0; w < SELECT_THREADS / 64; w++) {
-            const unsigned a = wsum[par][0][w], c = wsum[par][1][w];
-            if (w < wv) { a_before += a; c_before += c; }
-            a_tot += a; c_tot += c;
-        }
-        const unsigned taken0 = min(need, cbase);
-        const bool take = isA || (isC && cbase + c_before < need);
-        if (take) {
-            const unsigned pos = obase + a_before + (min(need, cbase + c_before) - taken0);
-            keys[pos] = ((unsigned long long)k << 32) | (unsigned long long)(uint32_t)i;
-        }
-        obase += a_tot + (min(need, cbase + c_tot) - taken0);
-        cbase += c_tot;
-    }
-    __syncthreads();
-    const unsigned total = obase;      // <= max_hits <= GSCAN_MAX_HITS by the choice of the cut
-    unsigned np2 = 1;
-    while (np2 < total) np2 <<= 1;
-    for (unsigned t = total + tid; t < np2; t += SELECT_THREADS) keys[t] = ~0ull;
-    __syncthreads();
-    for (unsigned kk = 2; kk <= np2; kk <<= 1) {
-        for (unsigned j = kk >> 1; j > 0; j >>= 1) {
-            for (unsigned t = tid; t < np2; t += SELECT_THREADS) {
-                const unsigned x = t ^ j;
-                if (x > t) {
-                    const unsigned long long a = keys[t], b = keys[x];
-                    if ((a > b) == ((t & kk) == 0)) { keys[t] = b; keys[x] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    mmgpu_pf_hit *out = A.hits + (size_t)q * A.stride;
-    for (unsigned t = tid; t < A.stride; t += SELECT_THREADS) {
-        mmgpu_pf_hit h = {0, 0, 0, 0};
-        if (t < total) {
-            const unsigned long long key = keys[t];
-            h.id = (uint32_t)key;
-            h.score = 32767 - (int32_t)(key >> 32);
-        }
-        out[t] = h;
-    }
-    if (tid == 0) A.counts[q] = total;
+    auto key_of = [&](uint64_t i, unsigned &k) {
+        const int s = row[i];
+        k = (unsigned)(32767 - s);
+        return admitted(i, s);
+    };
+    select_emit(n, key_of, s_cut, s_need, lds, 32767, A.hits + (size_t)q * A.stride, A.stride, &A.counts[q]);
 }
 
 }  // namespace
@@ -204,7 +137,7 @@ hipError_t launch_gscan_identity(const GscanIdentArgs &A, uint32_t nq, hipStream
 
 hipError_t launch_gscan_select(const GscanSelectArgs &A, uint32_t n_queries, hipStream_t stream) {
     if (n_queries == 0) return hipSuccess;
-    if (A.max_hits == 0 || A.max_hits > (uint32_t)GSCAN_MAX_HITS) return hipErrorInvalidValue;      // the key array must never be short
+    if (A.max_hits == 0 || A.max_hits > (uint32_t)SELECT_MAX_HITS) return hipErrorInvalidValue;      // the key array must never be short
     hipLaunchKernelGGL(gscan_select_kernel, dim3(n_queries), dim3(SELECT_THREADS), 0, stream, A);
     return hipGetLastError();
 }

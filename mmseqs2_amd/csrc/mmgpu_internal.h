@@ -212,7 +212,6 @@ constexpr int SCAN_MULTI = SCAN_CLASSES - 1;
 constexpr int SCAN_MAX_R = 32;                        // rows per lane of the largest tile: 16 lanes x 32 = 512 query rows
 constexpr int SCAN_ROUND = 32;                        // targets a workgroup scores at once: 4 waves x 4 DPP rows x 2 halves
 constexpr int SCAN_JOB_TARGETS = 16 * SCAN_ROUND;     // targets per job of a one-tile query (a multi-tile job is one round)
-constexpr int SCAN_MAX_HITS = 4096;                   // == MMGPU_PF_MAX_FUSED_HITS: keys the selection kernel sorts in LDS
 __host__ __device__ constexpr int scan_class_rows(int cls) { return cls == 0 ? 8 : cls == 1 ? 16 : cls == 2 ? 24 : 32; }
 // columns a pair's scan covers: the longer target's length, rounded up to whole chunks of R columns (the rest reads the pad letter)
 __host__ __device__ constexpr uint32_t scan_cols(uint32_t len, int R) { return (len + (uint32_t)R - 1u) / (uint32_t)R * (uint32_t)R; }
@@ -272,7 +271,6 @@ void warm_scan();
 // window.  The pairs of a chunk of queries are an ordinary MMGPU_SW_SCORE_END batch whose lists are slices of the length-ordered id
 // list: the planner kernel writes hit_target / hit_out on the device, the host cuts only the job ranges (sw_prepare_dense).
 constexpr uint64_t GSCAN_PAIR_BUDGET = 1ull << 24;    // pairs scored at once by default: 16 M x (24 + 8) bytes of records and lists
-constexpr int GSCAN_MAX_HITS = SCAN_MAX_HITS;
 
 // the lists of a dense alignment batch: query i of the call aligns against positions [begin[i], begin[i] + count[i]) of `order`; its
 // pairs take the slots [slot_base(i), + count[i]) of the three shared device arrays, slot_base = the running sum of the counts
@@ -1150,5 +1148,37 @@ bool pf_batch_device_lists(mmgpu_pf_batch_t *b, const mmgpu_pf_hit **hits, const
 // kernels; target_ids / n_targets of the queries are not read), and its kernel launches without the batch's own timing events
 int sw_prepare_dense(mmgpu_ctx *c, const mmgpu_sw_params *par, const mmgpu_sw_query *qs, uint32_t nq, const SwDenseLists &lists, mmgpu_sw_batch_t **out);
 int sw_run_dense(mmgpu_ctx *c, mmgpu_sw_batch_t *b);
+
+// scan_common.hip: what a batch of either exhaustive scan holds and does like the other's (mmgpu_scan_batch_t and
+// mmgpu_gscan_batch_t derive from the record).  `who` is the entry point's name, the head of every message.
+struct ScanBatchCommon {
+    uint32_t nq = 0, n_targets = 0, max_hits = 0, stride = 0;
+    int32_t min_score = 0;
+    int alphabet = 0;
+    const uint8_t *db_res = nullptr;      // the resident database the batch was prepared against (a reload invalidates the batch)
+    uint64_t serial = 0;                  // names this batch in mmgpu_ctx::scan_serial / gscan_serial
+    bool ran = false;
+    DevBuf d_mat, d_hits, d_counts;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;      // around the last run
+    ~ScanBatchCommon() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+// the checks of a prepare call before and after the scan's own; have_args: the parameters, their matrix and the queries are there;
+// score_size: bytes per entry of the [query][target] score scratch (4 GiB of it at most)
+int scan_check_db(const char *who, const mmgpu_ctx *c, bool have_args, int alphabet);
+int scan_check_size(const char *who, const mmgpu_ctx *c, uint32_t nq, uint32_t max_hits, size_t score_size);
+void scan_fill_header(ScanBatchCommon *b, const mmgpu_ctx *c, uint32_t nq, int alphabet, int32_t min_score, uint32_t max_hits, uint64_t serial);
+// the matrix, the list buffers, and the wait for the stream that ends a prepare call's uploads
+int scan_upload_common(mmgpu_ctx *c, ScanBatchCommon *b, const int8_t *matrix);
+int scan_check_batch(const char *who, const mmgpu_ctx *c, const ScanBatchCommon *b, bool must_have_run);
+int scan_fetch_lists(const char *who, mmgpu_ctx *c, ScanBatchCommon *b, void *hits, uint32_t hit_stride, void *counts, hipMemcpyKind kind);
+int scan_kernel_ms(const char *who, mmgpu_ctx *c, ScanBatchCommon *b, float *ms);
+// one query's row of the context's score scratch, if the scratch still holds this batch's (the two scans keep a serial and a
+// scratch each on the context); kind: "scan" / "gapped scan"
+int scan_debug_scores(const char *who, const char *kind, mmgpu_ctx *c, ScanBatchCommon *b, uint64_t mmgpu_ctx::*serial, DevBuf mmgpu_ctx::*scratch,
+                      size_t score_size, uint32_t query, void *out, size_t cap);
+void scan_sync_for_free(mmgpu_ctx *c);      // before a batch is deleted: nothing of it is in flight
 }
 #endif

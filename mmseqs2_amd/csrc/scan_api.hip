@@ -1,6 +1,7 @@
-// Host side of the exhaustive ungapped scan (include/mmgpu.h, "exhaustive ungapped scan"): validation, the per-query bias of sequence
-// and of profile queries, the job lists, launches of scan_kernel.hip.  prepare and run are sequences of named steps over one record each, in the manner of
-// sw_prepare_impl (mmgpu_api.hip).
+// Host side of the exhaustive ungapped scan (include/mmgpu.h, "exhaustive ungapped scan"): the scan's own validation, the per-query bias
+// of sequence and of profile queries, the job lists, launches of scan_kernel.hip.  prepare and run are sequences of named steps over one
+// record each, in the manner of sw_prepare_impl (mmgpu_api.hip).  What a batch holds and does like the gapped scan's - header, common
+// checks, list buffers, fetches, kernel time, score read-back - is scan_common.hip's; the entry points here name themselves and call it.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -10,23 +11,11 @@
 
 using namespace mmgpu;
 
-struct mmgpu_scan_batch_t {
-    uint32_t nq = 0, n_targets = 0, max_hits = 0, stride = 0;
-    int32_t min_score = 0;
-    int alphabet = 0;
-    const uint8_t *db_res = nullptr;      // the resident database the batch was prepared against (a reload invalidates the batch)
-    uint64_t serial = 0;                  // names this batch in mmgpu_ctx::scan_serial
-    bool ran = false;
-    DevBuf d_qres, d_qcb, d_qoff, d_qcap, d_qprof, d_qprof_off, d_qprof_letters, d_qident, d_qwin, d_mat, d_order, d_jobs, d_park_off,
-        d_hits, d_counts;
+struct mmgpu_scan_batch_t : ScanBatchCommon {
+    DevBuf d_qres, d_qcb, d_qoff, d_qcap, d_qprof, d_qprof_off, d_qprof_letters, d_qident, d_qwin, d_order, d_jobs, d_park_off;
     uint32_t class_begin[SCAN_CLASSES + 1] = {};   // jobs of class k: d_jobs[class_begin[k] .. class_begin[k + 1])
     uint32_t multi_grid = 0;              // persistent workgroups of the multi-tile launch
     uint64_t park_words = 0;              // dwords of boundary lines they need
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~mmgpu_scan_batch_t() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
 };
 
 namespace {
@@ -50,16 +39,11 @@ struct ScanPrepare {
 };
 
 int scan_check_call(const ScanPrepare &S) {
-    const mmgpu_ctx *c = S.c;
-    if (!S.par || !S.qs || S.nq == 0 || !S.par->mat) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: NULL argument or no queries");
-    if (!c->db.res || c->db.n == 0) return fail(MMGPU_ERR_STATE, "mmgpu_scan_prepare: no targets loaded");
-    if (c->shard.on) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: the context holds a shard of a multi-GPU run");
-    if (S.par->alphabet != c->db.alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: alphabet differs from the loaded targets");
+    const char *who = "mmgpu_scan_prepare";
+    int rc = scan_check_db(who, S.c, S.par && S.qs && S.nq && S.par->mat, S.par ? S.par->alphabet : 0);
+    if (rc != MMGPU_OK) return rc;
     if (S.par->alphabet > 32) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: sequence queries over a protein database only (alphabet <= 32)");
-    if (S.par->max_hits == 0) return fail(MMGPU_ERR_ARG, "mmgpu_scan_prepare: max_hits must be >= 1");
-    if (S.par->max_hits > MMGPU_PF_MAX_FUSED_HITS) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: max_hits above MMGPU_PF_MAX_FUSED_HITS");
-    if ((uint64_t)S.nq * c->db.n > (4ull << 30)) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_scan_prepare: more than 4 GiB of scores (queries x resident targets): send smaller batches");
-    return MMGPU_OK;
+    return scan_check_size(who, S.c, S.nq, S.par->max_hits, sizeof(uint8_t));
 }
 
 // the two range checks of a query whose bias is B and whose highest profile score is p_max, and its cap (ssw_init, :1397-1406)
@@ -186,9 +170,8 @@ int scan_upload(ScanPrepare &S, mmgpu_scan_batch_t *b) {
     mmgpu_ctx *c = S.c;
     hipStream_t s = c->stream;
     for (DevBuf *d : {&b->d_qres, &b->d_qcb, &b->d_qoff, &b->d_qcap, &b->d_qprof, &b->d_qprof_off, &b->d_qprof_letters, &b->d_qident,
-                      &b->d_qwin, &b->d_mat, &b->d_order, &b->d_jobs, &b->d_park_off, &b->d_hits, &b->d_counts})
+                      &b->d_qwin, &b->d_order, &b->d_jobs, &b->d_park_off})
         d->bind(c->cache);
-    std::vector<int8_t> mat(S.par->mat, S.par->mat + (size_t)S.par->alphabet * S.par->alphabet);
     HIP_TRY(upload(b->d_qres, S.qres, s));
     HIP_TRY(upload(b->d_qcb, S.qcb, s));
     HIP_TRY(upload(b->d_qoff, S.qoff, s));
@@ -198,14 +181,10 @@ int scan_upload(ScanPrepare &S, mmgpu_scan_batch_t *b) {
     HIP_TRY(upload(b->d_qprof_letters, S.qprof_letters, s));
     HIP_TRY(upload(b->d_qident, S.qident, s));
     HIP_TRY(upload(b->d_qwin, S.qwin, s));
-    HIP_TRY(upload(b->d_mat, mat, s));
     HIP_TRY(upload(b->d_order, S.order, s));
     HIP_TRY(upload(b->d_jobs, S.jobs, s));
     HIP_TRY(upload(b->d_park_off, S.park_off, s));
-    HIP_TRY(b->d_hits.alloc((size_t)b->nq * b->stride * sizeof(mmgpu_pf_hit)));
-    HIP_TRY(b->d_counts.alloc((size_t)b->nq * sizeof(uint32_t)));
-    HIP_TRY(hipStreamSynchronize(s));      // the host vectors go with this call
-    return MMGPU_OK;
+    return scan_upload_common(c, b, S.par->mat);
 }
 
 int scan_prepare_impl(mmgpu_ctx *c, const mmgpu_scan_params *par, const mmgpu_scan_query *qs, uint32_t nq, mmgpu_scan_batch_t **out) {
@@ -216,14 +195,7 @@ int scan_prepare_impl(mmgpu_ctx *c, const mmgpu_scan_params *par, const mmgpu_sc
     rc = scan_marshal_queries(S);
     if (rc != MMGPU_OK) return rc;
     std::unique_ptr<mmgpu_scan_batch_t> b(new mmgpu_scan_batch_t());
-    b->nq = nq;
-    b->n_targets = c->db.n;
-    b->max_hits = par->max_hits;
-    b->stride = std::min(par->max_hits, c->db.n);
-    b->min_score = par->min_score;
-    b->alphabet = par->alphabet;
-    b->db_res = c->db.res;
-    b->serial = ++g_scan_serial;
+    scan_fill_header(b.get(), c, nq, par->alphabet, par->min_score, par->max_hits, ++g_scan_serial);
     scan_order_targets(S);
     scan_cut_jobs(S, b.get());
     rc = scan_upload(S, b.get());
@@ -288,13 +260,6 @@ int scan_launch_select(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
     return MMGPU_OK;
 }
 
-int scan_check_batch(const char *who, const mmgpu_ctx *c, const mmgpu_scan_batch_t *b, bool must_have_run) {
-    if (!c || !b) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
-    if (b->db_res != c->db.res || b->n_targets != c->db.n) return fail(MMGPU_ERR_STATE, std::string(who) + ": the targets were reloaded since the batch was prepared");
-    if (must_have_run && !b->ran) return fail(MMGPU_ERR_STATE, std::string(who) + ": the batch has not been run");
-    return MMGPU_OK;
-}
-
 }  // namespace
 
 extern "C" int mmgpu_scan_prepare(mmgpu_ctx *c, const mmgpu_scan_params *par, const mmgpu_scan_query *qs, uint32_t nq,
@@ -322,46 +287,20 @@ extern "C" int mmgpu_scan_run(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
 }
 
 extern "C" int mmgpu_scan_fetch(mmgpu_ctx *c, mmgpu_scan_batch_t *b, mmgpu_pf_hit *hits, uint32_t hit_stride, uint32_t *counts) {
-    int rc = scan_check_batch("mmgpu_scan_fetch", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (!hits || !counts) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch: NULL argument");
-    if (hit_stride < b->stride) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch: hit_stride below min(max_hits, resident targets)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy2DAsync(hits, (size_t)hit_stride * sizeof(mmgpu_pf_hit), b->d_hits.p, (size_t)b->stride * sizeof(mmgpu_pf_hit),
-                             (size_t)b->stride * sizeof(mmgpu_pf_hit), b->nq, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(counts, b->d_counts.p, (size_t)b->nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MMGPU_OK;
+    return scan_fetch_lists("mmgpu_scan_fetch", c, b, hits, hit_stride, counts, hipMemcpyDeviceToHost);
 }
 
 extern "C" int mmgpu_scan_fetch_device(mmgpu_ctx *c, mmgpu_scan_batch_t *b, void *d_hits, uint32_t hit_stride, void *d_counts) {
-    int rc = scan_check_batch("mmgpu_scan_fetch_device", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (!d_hits || !d_counts) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch_device: NULL argument");
-    if (hit_stride < b->stride) return fail(MMGPU_ERR_ARG, "mmgpu_scan_fetch_device: hit_stride below min(max_hits, resident targets)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy2DAsync(d_hits, (size_t)hit_stride * sizeof(mmgpu_pf_hit), b->d_hits.p, (size_t)b->stride * sizeof(mmgpu_pf_hit),
-                             (size_t)b->stride * sizeof(mmgpu_pf_hit), b->nq, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_counts, b->d_counts.p, (size_t)b->nq * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    return MMGPU_OK;
+    return scan_fetch_lists("mmgpu_scan_fetch_device", c, b, d_hits, hit_stride, d_counts, hipMemcpyDeviceToDevice);
 }
 
 extern "C" int mmgpu_scan_last_kernel_ms(mmgpu_ctx *c, mmgpu_scan_batch_t *b, float *ms) {
-    int rc = scan_check_batch("mmgpu_scan_last_kernel_ms", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (!ms) return fail(MMGPU_ERR_ARG, "mmgpu_scan_last_kernel_ms: NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(b->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, b->ev0, b->ev1));
-    return MMGPU_OK;
+    return scan_kernel_ms("mmgpu_scan_last_kernel_ms", c, b, ms);
 }
 
 extern "C" void mmgpu_scan_free(mmgpu_ctx *c, mmgpu_scan_batch_t *b) {
     if (!b) return;
-    if (c) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-    }
+    scan_sync_for_free(c);
     delete b;
 }
 
@@ -377,12 +316,6 @@ extern "C" int mmgpu_scan_batch(mmgpu_ctx *c, const mmgpu_scan_params *par, cons
 }
 
 extern "C" int mmgpu_scan_debug_scores(mmgpu_ctx *c, mmgpu_scan_batch_t *b, uint32_t query, uint8_t *out, size_t cap) {
-    int rc = scan_check_batch("mmgpu_scan_debug_scores", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (c->scan_serial != b->serial) return fail(MMGPU_ERR_STATE, "mmgpu_scan_debug_scores: another scan batch has run on the context since");
-    if (!out || query >= b->nq || cap < b->n_targets) return fail(MMGPU_ERR_ARG, "mmgpu_scan_debug_scores: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, c->scan_scores.as<uint8_t>() + (size_t)query * b->n_targets, b->n_targets, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MMGPU_OK;
+    return scan_debug_scores("mmgpu_scan_debug_scores", "scan", c, b, &mmgpu_ctx::scan_serial, &mmgpu_ctx::scan_scores, sizeof(uint8_t),
+                             query, out, cap);
 }

@@ -24,9 +24,11 @@
 //  * queries longer than one tile (512 rows): the tile loop runs inside the kernel; the value leaving the last lane is parked in a
 //    double-buffered global line per DPP row and re-enters at lane 0 of the next tile.  The profile is rebuilt per tile.
 //  * the finished pair's score goes into the batch's [query][target] byte array with plain byte stores; the selection kernel
-//    (one workgroup per query) builds a 256-bin histogram of the admitted targets, finds the cut score, compacts the list in id order
-//    with ballot prefix sums and sorts at most SCAN_MAX_HITS keys (255 - score, id) in LDS.  The histogram's atomics only count.
+//    (one workgroup per query) builds a 256-bin histogram of the admitted targets' keys 255 - score and finds the cut key in it;
+//    compaction, sort and the write of the list are select_device.h's, shared with gscan_kernel.hip.  The histogram's atomics only
+//    count.
 #include "mmgpu_internal.h"
+#include "select_device.h"
 
 namespace mmgpu {
 
@@ -35,7 +37,6 @@ namespace {
 constexpr int GROUP = 16;            // lanes per target pair (one DPP row)
 constexpr int WAVES = 4;             // waves per workgroup
 static_assert(SCAN_ROUND == WAVES * (64 / GROUP) * 2, "targets per workgroup round");
-static_assert(SCAN_MAX_HITS == MMGPU_PF_MAX_FUSED_HITS, "the selection kernel sorts every list the C-ABI admits");
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
@@ -238,108 +239,44 @@ __global__ __launch_bounds__(WAVES * 64) void scan_kernel(ScanLaunch L) {
     }
 }
 
-constexpr int SELECT_THREADS = 1024;
-
-// One workgroup per query: the list out of the score bytes.
+// One workgroup per query: the list out of the score bytes.  Keys are 255 - score; one histogram level finds the cut.
 __global__ __launch_bounds__(SELECT_THREADS) void scan_select_kernel(ScanSelectArgs A) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned long long keys[SCAN_MAX_HITS];
-    __shared__ unsigned wsum[2][2][SELECT_THREADS / 64];
-    __shared__ int s_cut;
-    __shared__ unsigned s_need;
+    __shared__ unsigned hist[SELECT_BINS];
+    __shared__ SelectLds lds;
+    __shared__ unsigned s_cut, s_need;
     const uint32_t q = blockIdx.x;
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const unsigned tid = threadIdx.x;
     const uint32_t n = A.n_targets;
     const uint8_t *scores = A.scores + (size_t)q * n;
     const uint32_t ident = A.q_ident[q], lo = A.q_win[2 * q], hi = A.q_win[2 * q + 1];
-    if (tid < 256) hist[tid] = 0;
+    if (tid < SELECT_BINS) hist[tid] = 0;
     __syncthreads();
     // admitted: inside the window, and above the threshold or the query's own target
-    for (uint64_t i = tid; i < n; i += SELECT_THREADS) {
+    auto key_of = [&](uint64_t i, unsigned &k) {
         const int s = scores[i];
         const uint32_t len = A.t_len[i];
-        if (len >= lo && len <= hi && (s > A.min_score || (uint32_t)i == ident)) atomicAdd(&hist[s], 1u);
+        k = (unsigned)(255 - s);
+        return len >= lo && len <= hi && (s > A.min_score || (uint32_t)i == ident);
+    };
+    for (uint64_t i = tid; i < n; i += SELECT_THREADS) {
+        unsigned k;
+        if (key_of(i, k)) atomicAdd(&hist[k], 1u);
     }
     __syncthreads();
     if (tid == 0) {
         unsigned total = 0;
-        for (int s = 0; s < 256; s++) total += hist[s];
-        int cut = -1;
-        unsigned need = 0;
+        for (int b = 0; b < SELECT_BINS; b++) total += hist[b];
+        unsigned cut = SELECT_BINS, need = 0;      // no cut: every admitted key is below it
         if (total > A.max_hits) {      // the class the cut falls into, and how many of its lowest ids are kept
-            unsigned above = 0;
-            for (int s = 255; s >= 0; s--) {
-                if (above + hist[s] >= A.max_hits) { cut = s; need = A.max_hits - above; break; }
-                above += hist[s];
-            }
+            const SelectCut c = select_cut_walk(hist, 0, A.max_hits);
+            cut = c.bin;
+            need = A.max_hits - c.above;
         }
         s_cut = cut;
         s_need = need;
     }
     __syncthreads();
-    const int cut = s_cut;
-    const unsigned need = s_need;
-    // compaction in id order: everything above the cut, the first `need` of the cut class
-    unsigned cbase = 0, obase = 0;
-    unsigned par = 0;
-    for (uint64_t start = 0; start < n; start += SELECT_THREADS, par ^= 1u) {
-        const uint64_t i = start + tid;
-        int s = 0;
-        bool adm = false;
-        if (i < n) {
-            s = scores[i];
-            const uint32_t len = A.t_len[i];
-            adm = len >= lo && len <= hi && (s > A.min_score || (uint32_t)i == ident);
-        }
-        const bool isA = adm && s > cut, isC = adm && s == cut;
-        const unsigned long long bA = __ballot(isA), bC = __ballot(isC);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (lane == 0) { wsum[par][0][wv] = (unsigned)__popcll(bA); wsum[par][1][wv] = (unsigned)__popcll(bC); }
-        __syncthreads();
-        unsigned a_before = (unsigned)__popcll(bA & below), c_before = (unsigned)__popcll(bC & below), a_tot = 0, c_tot = 0;
-        for (unsigned w = 0; w < SELECT_THREADS / 64; w++) {
-            const unsigned a = wsum[par][0][w], c = wsum[par][1][w];
-            if (w < wv) { a_before += a; c_before += c; }
-            a_tot += a; c_tot += c;
-        }
-        const unsigned taken0 = min(need, cbase);
-        const bool take = isA || (isC && cbase + c_before < need);
-        if (take) {
-            const unsigned pos = obase + a_before + (min(need, cbase + c_before) - taken0);
-            keys[pos] = ((unsigned long long)(255 - s) << 32) | (unsigned long long)(uint32_t)i;
-        }
-        obase += a_tot + (min(need, cbase + c_tot) - taken0);
-        cbase += c_tot;
-    }
-    __syncthreads();
-    const unsigned total = obase;      // <= max_hits <= SCAN_MAX_HITS by the choice of the cut
-    unsigned np2 = 1;
-    while (np2 < total) np2 <<= 1;
-    for (unsigned t = total + tid; t < np2; t += SELECT_THREADS) keys[t] = ~0ull;
-    __syncthreads();
-    for (unsigned k = 2; k <= np2; k <<= 1) {
-        for (unsigned j = k >> 1; j > 0; j >>= 1) {
-            for (unsigned t = tid; t < np2; t += SELECT_THREADS) {
-                const unsigned x = t ^ j;
-                if (x > t) {
-                    const unsigned long long a = keys[t], b = keys[x];
-                    if ((a > b) == ((t & k) == 0)) { keys[t] = b; keys[x] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    mmgpu_pf_hit *out = A.hits + (size_t)q * A.stride;
-    for (unsigned t = tid; t < A.stride; t += SELECT_THREADS) {
-        mmgpu_pf_hit h = {0, 0, 0, 0};
-        if (t < total) {
-            const unsigned long long key = keys[t];
-            h.id = (uint32_t)key;
-            h.score = 255 - (int32_t)(key >> 32);
-        }
-        out[t] = h;
-    }
-    if (tid == 0) A.counts[q] = total;
+    select_emit(n, key_of, s_cut, s_need, lds, 255, A.hits + (size_t)q * A.stride, A.stride, &A.counts[q]);
 }
 
 }  // namespace
@@ -362,7 +299,7 @@ hipError_t launch_scan(const ScanLaunch &L, int cls, uint32_t grid, hipStream_t 
 
 hipError_t launch_scan_select(const ScanSelectArgs &A, uint32_t nq, hipStream_t stream) {
     if (nq == 0) return hipSuccess;
-    if (A.max_hits > (uint32_t)SCAN_MAX_HITS) return hipErrorInvalidValue;      // the key array must never be short
+    if (A.max_hits > (uint32_t)SELECT_MAX_HITS) return hipErrorInvalidValue;      // the key array must never be short
     hipLaunchKernelGGL(scan_select_kernel, dim3(nq), dim3(SELECT_THREADS), 0, stream, A);
     return hipGetLastError();
 }

@@ -186,3 +186,26 @@ def sw_job_constants():
         assert m, name
         out[name] = int(m.group(1))
     return out
+
+
+# ---- the selection over more ids than one round of the compaction holds, and over a full key array: uc's sequences, this scan's
+# scores and list rule ----
+CASE_GO, CASE_GE = 11, 1
+
+
+def _case(name, oracle, min_score, max_hits_of):
+    mat = Golden().g["mat_blosum62"]
+    C = uc.select_case(name, "gapped", lambda qd, ts: raw_scores(oracle, mat, CASE_GO, CASE_GE, qd, ts), min_score=min_score, min_ev=0)
+    C.setdefault("mat", mat)
+    if "max_hits" not in C:
+        C["max_hits"] = max_hits_of(C)
+    return C
+
+
+def rounds_case(oracle):
+    return _case("rounds", oracle, uc.ROUNDS_MIN_SCORE, lambda C: uc.rounds_max_hits(
+        *select_list(C["raw"][0], C["tlens"], FULL_WINDOW, uc.ROUNDS_MIN_SCORE, 0, len(C["tlens"]))))
+
+
+def full_case(oracle):
+    return _case("full", oracle, -1, lambda C: dict(full=uc.SELECT_KEYS))

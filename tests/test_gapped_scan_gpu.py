@@ -12,6 +12,7 @@ import pytest
 from mmseqs2_amd import capi
 from tests import gapped_scan_cases as gc
 from tests import ungapped_scan_cases as uc
+from tests.ungapped_scan_cases import assert_lists, lists_of
 from tests import ungapped_scan_profile_cases as upc
 
 pytestmark = pytest.mark.gpu
@@ -34,16 +35,6 @@ def blosum62():
 def the_oracle():
     from oracle.pyoracle import Oracle
     return Oracle()
-
-
-def lists_of(hits, counts):
-    return [(hits[k]["id"][:int(counts[k])].astype(np.int64), hits[k]["score"][:int(counts[k])].astype(np.int64)) for k in range(len(counts))]
-
-
-def assert_lists(got, want, tag=""):
-    assert len(got) == len(want)
-    for k, ((gi, gs), (wi, ws)) in enumerate(zip(got, want)):
-        assert np.array_equal(gi, wi) and np.array_equal(gs, ws), (tag, k, gi[:12], wi[:12], gs[:12], ws[:12])
 
 
 def expect_scores(queries, targets, go=GO, ge=GE):
@@ -350,3 +341,15 @@ def test_refusals_leave_the_handle_null(gpu):
     assert rc == 0 and h
     gpu.L.mmgpu_gscan_free(gpu.ctx, ctypes.c_void_p(h))
 
+
+# ---- the selection over several rounds of the compaction and over a full key array ----------------------------------------------
+@pytest.mark.parametrize("tag", ["a", "b", "c", "d", "all", "full"])
+def test_selection_over_rounds_and_a_full_key_array(gpu, tag):
+    """gc.rounds_case: 2100 targets, the cut inside a tie class whose last kept member is (a) before, (b) the last id of the first
+    round of 1024 ids, (c) the first of the second, (d) in the third, (all) no cut; gc.full_case: 4200 admitted targets, 4096 keys"""
+    C = gc.full_case(the_oracle()) if tag == "full" else gc.rounds_case(the_oracle())
+    m = C["max_hits"][tag]
+    gpu.load_targets(*uc.pack(C["targets"]), 21)
+    qs = [dict(qd, min_evalue_score=C["rule"]["min_ev"]) for qd in C["queries"]]
+    hits, counts = gpu.gscan_batch(C["mat"], gc.CASE_GO, gc.CASE_GE, qs, min_score=C["rule"]["min_score"], max_hits=m)
+    assert_lists(lists_of(hits, counts), uc.case_lists(C, gc.select_list, m), tag)

@@ -10,6 +10,7 @@ import pytest
 
 from mmseqs2_amd import capi
 from tests import ungapped_scan_cases as uc
+from tests.ungapped_scan_cases import assert_lists, lists_of
 
 pytestmark = pytest.mark.gpu
 
@@ -45,16 +46,6 @@ def assert_scores(gpu, mat, queries, targets):
     bad = np.argwhere(got != want)
     assert len(bad) == 0, [(int(q), int(t), int(got[q, t]), int(want[q, t]), len(queries[q]["q"]), len(targets[t])) for q, t in bad[:8]]
     return want
-
-
-def lists_of(hits, counts):
-    return [(hits[k]["id"][:int(counts[k])].astype(np.int64), hits[k]["score"][:int(counts[k])].astype(np.int64)) for k in range(len(counts))]
-
-
-def assert_lists(got, want, tag=""):
-    assert len(got) == len(want)
-    for k, ((gi, gs), (wi, ws)) in enumerate(zip(got, want)):
-        assert np.array_equal(gi, wi) and np.array_equal(gs, ws), (tag, k, gi[:12], wi[:12], gs[:12], ws[:12])
 
 
 # ---- 1. the recorded lists ---------------------------------------------------------------------------------------------------
@@ -271,3 +262,15 @@ def test_refusals_leave_the_handle_null(gpu):
     rc, h = raw_prepare(gpu, blosum62(), [q])
     assert rc == 0 and h
     gpu.L.mmgpu_scan_free(gpu.ctx, ctypes.c_void_p(h))
+
+
+# ---- the selection over several rounds of the compaction and over a full key array ----------------------------------------------
+@pytest.mark.parametrize("tag", ["a", "b", "c", "d", "all", "full"])
+def test_selection_over_rounds_and_a_full_key_array(gpu, tag):
+    """uc.rounds_case: 2100 targets, the cut inside a tie class whose last kept member is (a) before, (b) the last id of the first
+    round of 1024 ids, (c) the first of the second, (d) in the third, (all) no cut; uc.full_case: 4200 admitted targets, 4096 keys"""
+    C = uc.full_case() if tag == "full" else uc.rounds_case()
+    m = C["max_hits"][tag]
+    gpu.load_targets(*uc.pack(C["targets"]), 21)
+    hits, counts = gpu.scan_batch(C["mat"], C["queries"], min_score=C["rule"]["min_score"], max_hits=m)
+    assert_lists(lists_of(hits, counts), uc.case_lists(C, uc.select_list, m), tag)

@@ -10,6 +10,7 @@ import pytest
 
 from mmseqs2_amd import capi
 from tests import ungapped_scan_cases as uc
+from tests.ungapped_scan_cases import assert_lists, lists_of
 from tests import ungapped_scan_profile_cases as upc
 
 pytestmark = pytest.mark.gpu
@@ -50,16 +51,6 @@ def assert_scores(gpu, mat, queries, targets, alphabet=21):
     bad = np.argwhere(got != want)
     assert len(bad) == 0, [(int(q), int(t), int(got[q, t]), int(want[q, t]), len(targets[t])) for q, t in bad[:8]]
     return want
-
-
-def lists_of(hits, counts):
-    return [(hits[k]["id"][:int(counts[k])].astype(np.int64), hits[k]["score"][:int(counts[k])].astype(np.int64)) for k in range(len(counts))]
-
-
-def assert_lists(got, want, tag=""):
-    assert len(got) == len(want)
-    for k, ((gi, gs), (wi, ws)) in enumerate(zip(got, want)):
-        assert np.array_equal(gi, wi) and np.array_equal(gs, ws), (tag, k, gi[:12], wi[:12], gs[:12], ws[:12])
 
 
 # ---- 1. the recorded lists ---------------------------------------------------------------------------------------------------

@@ -204,3 +204,103 @@ def pack(seqs):
     off[1:] = np.cumsum([len(s) for s in seqs])
     res = np.concatenate([np.asarray(s, np.uint8) for s in seqs]) if seqs and off[-1] else np.zeros(0, np.uint8)
     return res, off
+
+
+# ---- lists of the device tests (both scans and the profile queries compare them the same way) ----
+def lists_of(hits, counts):
+    return [(hits[k]["id"][:int(counts[k])].astype(np.int64), hits[k]["score"][:int(counts[k])].astype(np.int64)) for k in range(len(counts))]
+
+
+def assert_lists(got, want, tag=""):
+    assert len(got) == len(want)
+    for k, ((gi, gs), (wi, ws)) in enumerate(zip(got, want)):
+        assert np.array_equal(gi, wi) and np.array_equal(gs, ws), (tag, k, gi[:12], wi[:12], gs[:12], ws[:12])
+
+
+# ---- the selection over more ids than one round of the compaction holds, and over a full key array ----
+SELECT_ROUND = 1024      # ids the selection kernels compact per round
+SELECT_KEYS = 4096       # keys they sort: the largest max_hits
+ROUNDS_TIE_IDS = np.concatenate([np.arange(1000, 1061), np.arange(2030, 2071)])      # on both sides of ids 1024 and 2048
+ROUNDS_BETTER_IDS = np.array([3, 500, 999, 1061, 1500, 2029, 2071, 2099])             # in every round, around the tie class
+ROUNDS_MIN_SCORE = 15
+
+
+def rounds_sequences():
+    """-> (queries, targets): 2100 targets of length 5 .. 40; a class of identical targets at ROUNDS_TIE_IDS that query 0 contains, a
+    few targets that hold more of query 0 and so score above the class, and an unrelated query 1"""
+    rng = np.random.default_rng(31)
+    ts = [random_seq(rng, int(n)) for n in rng.integers(5, 41, 2100)]
+    q0 = random_seq(rng, 64)
+    tied = q0[20:46].copy()
+    for i in ROUNDS_TIE_IDS:
+        ts[i] = tied.copy()
+    for k, i in enumerate(ROUNDS_BETTER_IDS):
+        ts[i] = q0[17 - k:47 + k // 2].copy()      # (distinct lengths of 30 .. 40: distinct scores above the class's)
+    return [dict(q=q0), dict(q=random_seq(rng, 50))], ts
+
+
+def rounds_max_hits(ids, scores):
+    """the values of max_hits of the rounds case, from query 0's whole list (ids, scores as select_list gives them for a max_hits
+    above the admitted count): the cut falls inside the tie class so that the last member kept is (a) before id 1023, (b) id 1023,
+    the last of the first round, (c) id 1024, the first of the second, (d) in 2048 .. 2069, in the third; (all) above the count"""
+    member = np.isin(ids, ROUNDS_TIE_IDS)
+    first = int(np.flatnonzero(member)[0])      # the class is contiguous in the list and in id order
+    assert member[first:first + len(ROUNDS_TIE_IDS)].all() and np.array_equal(ids[first:first + len(ROUNDS_TIE_IDS)], ROUNDS_TIE_IDS)
+
+    def upto(last_id):
+        return first + int(np.flatnonzero(ROUNDS_TIE_IDS == last_id)[0]) + 1
+    return dict(a=upto(1009), b=upto(1023), c=upto(1024), d=upto(2052), all=len(ids) + 7)
+
+
+def last_tie_member(ids):
+    """the highest id of the tie class in a list, and how many of the class the list holds"""
+    kept = ids[np.isin(ids, ROUNDS_TIE_IDS)]
+    return int(kept.max()), len(kept)
+
+
+def full_sequences():
+    """-> (queries, targets): 4200 short targets, all of which a scan with min_score = -1 admits: a list of SELECT_KEYS entries.  300 of
+    them are made of X (letter 20: -1 against everything) and score 0, so the lowest class is the one the cut falls into"""
+    rng = np.random.default_rng(32)
+    ts = [random_seq(rng, int(n)) for n in rng.integers(5, 21, 4200)]
+    for i in rng.choice(4200, 300, replace=False):
+        ts[i] = np.full(len(ts[i]), 20, np.uint8)
+    return [dict(q=random_seq(rng, 24)), dict(q=random_seq(rng, 9))], ts
+
+
+_select_cases = {}
+
+
+def select_case(name, scan, score_fn, **rule):
+    """the rounds / the full case of one scan ("ungapped", "gapped"): score_fn(qd, targets) -> raw scores of one query; rule: what the
+    scan's select_list takes besides scores, lengths, window and max_hits.  -> dict(queries, targets, tlens, raw [query][target], rule);
+    computed once and left unchanged"""
+    key = (name, scan)
+    if key not in _select_cases:
+        qs, ts = rounds_sequences() if name == "rounds" else full_sequences()
+        tl = np.array([len(t) for t in ts], np.int64)
+        raw = np.stack([np.asarray(score_fn(qd, ts), np.int64) for qd in qs])
+        raw.setflags(write=False)
+        _select_cases[key] = dict(queries=qs, targets=ts, tlens=tl, raw=raw, rule=rule)
+    return _select_cases[key]
+
+
+def rounds_case():
+    mat = Golden().g["mat_blosum62"]
+    C = select_case("rounds", "ungapped", lambda qd, ts: scores_one_query(mat, qd["q"], None, ts), min_score=ROUNDS_MIN_SCORE)
+    C.setdefault("mat", mat)
+    C.setdefault("max_hits", rounds_max_hits(*select_list(C["raw"][0], C["tlens"], FULL_WINDOW, ROUNDS_MIN_SCORE, len(C["tlens"]))))
+    return C
+
+
+def full_case():
+    mat = Golden().g["mat_blosum62"]
+    C = select_case("full", "ungapped", lambda qd, ts: scores_one_query(mat, qd["q"], None, ts), min_score=-1)
+    C.setdefault("mat", mat)
+    C.setdefault("max_hits", dict(full=SELECT_KEYS))
+    return C
+
+
+def case_lists(C, select, max_hits):
+    """the expected lists of a case for one max_hits, by the scan's select_list"""
+    return [select(C["raw"][k], C["tlens"], FULL_WINDOW, max_hits=max_hits, **C["rule"]) for k in range(len(C["queries"]))]
