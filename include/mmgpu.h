@@ -813,6 +813,94 @@ int mmgpu_gscan_debug_scores(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch, uint32_
  * chunks of the last run in *n_chunks (may be NULL).  Synchronises. */
 int mmgpu_gscan_stage_ms(mmgpu_ctx *ctx, mmgpu_gscan_batch_t *batch, float ms[4], uint32_t *n_chunks);
 
+/* ---- ungapped diagonal rescoring (`mmseqs rescorediagonal`, src/alignment/rescorediagonal.cpp:243-250) ------------------------
+ * Every hit of a prefilter result list is rescored along the diagonal the hit records, as
+ * DistanceCalculator::computeUngappedAlignment does (DistanceCalculator.h:93-200), against the resident PROTEIN targets
+ * (alphabet 21), without composition bias.  The stored diagonal d is a uint16; the candidates are tried in the reference's order,
+ *     D = d - 65536 k,  k = 1 .. 1 + tlen / 32768      then      D = d + 65536 k,  k = 0 .. qlen / 65536,
+ * a candidate D >= 0 is valid when D < qlen (query from D, target from 0, len = min(tlen, qlen - D)), a candidate D < 0 when
+ * -D < tlen (target from -D, len = min(tlen + D, qlen)), an invalid one scores 0, and a candidate replaces the best so far only
+ * with a strictly greater score.  The best starts as {score 0, diagonal 0, diag_len 0, start -1, end -1, ident 0}: a hit none of
+ * whose candidates scores above 0 gives exactly that record, valid diagonal or not.
+ *   MMGPU_RESCORE_HAMMING       score = ident = equal residues over the whole diagonal; start = end = -1
+ *   MMGPU_RESCORE_SUBSTITUTION  c[i] = mat[q[qs+i]][t[ts+i]], P[i] = c[0] + .. + c[i], P[-1] = 0, score = max_i P[i] - min(P[-1..i]);
+ *                               start = end = -1, ident = 0
+ *   MMGPU_RESCORE_ALIGNMENT     the same score; end = the EARLIEST i that attains it, start = 1 + the LATEST j in -1..end that attains
+ *                               min(P[-1..end]) (computeSubstitutionStartEndDistance resets on score <= 0 and updates on a strictly
+ *                               greater score); ident = equal residues in [start, end].  start / end are offsets along the diagonal.
+ * Residues are compared as numbers.  The reference counts identities on the ASCII letters of the database: the two agree for
+ * sequences of the 20 amino acids and X in upper case, which is what the recorded parity covers; ambiguity codes (B, Z, J, ...)
+ * that share a number with another letter, and lower-case letters, would count differently.
+ * Not served: modes 3 and 4 (end-to-end, window quality: both trim a leading or trailing `*`, which numeric residues cannot tell
+ * from X), nucleotide and reverse-strand results, --wrapped-scoring, profile databases.
+ * MMGPU_ERR_STATE: no targets loaded.  MMGPU_ERR_UNSUPPORTED: an alphabet other than 21, a context that holds a shard, mode 3 or 4,
+ * 2^31 hits or more.  MMGPU_ERR_ARG: NULL arguments, a mode outside 0 .. 4, an empty query, a query letter outside the alphabet,
+ * a target id outside the database, offsets that do not ascend. */
+#define MMGPU_RESCORE_HAMMING 0
+#define MMGPU_RESCORE_SUBSTITUTION 1
+#define MMGPU_RESCORE_ALIGNMENT 2
+typedef struct {
+    const int8_t *mat;   /* alphabet*alphabet, row-major: SubstitutionMatrix(file, 2.0, 0.0) (rescorediagonal.cpp:88); read in every mode */
+    int alphabet;        /* 21 */
+    int mode;            /* par.rescoreMode */
+} mmgpu_rescore_params;
+typedef struct {
+    const uint8_t *q;    /* numeric residues */
+    uint32_t qlen;
+} mmgpu_rescore_query;
+typedef struct {
+    uint32_t target;     /* resident id */
+    uint16_t diagonal;   /* as the prefilter result line carries it (hit_t::diagonal) */
+    uint16_t reserved;
+} mmgpu_rescore_pair;
+typedef struct {
+    int32_t score;
+    int32_t diagonal;    /* the winning candidate D */
+    uint32_t diag_len;
+    int32_t start, end;  /* offsets along the diagonal (LocalAlignment::startPos / endPos), -1 where the mode leaves them */
+    uint32_t ident;
+} mmgpu_rescore_hit;
+typedef struct mmgpu_rescore_batch_t mmgpu_rescore_batch_t;
+/* hit_off [n_queries + 1]: the hits of query i are pairs[hit_off[i] .. hit_off[i + 1]); validates, H2D copies; *batch is NULL on
+ * failure */
+int mmgpu_rescore_prepare(mmgpu_ctx *ctx, const mmgpu_rescore_params *params, const mmgpu_rescore_query *queries, uint32_t n_queries,
+                          const uint64_t *hit_off, const mmgpu_rescore_pair *pairs, mmgpu_rescore_batch_t **batch);
+/* the kernel launch only, asynchronous on the context's stream */
+int mmgpu_rescore_run(mmgpu_ctx *ctx, mmgpu_rescore_batch_t *batch);
+/* one record per hit, in input order (no compaction): out [hit_off[n_queries]].  Synchronises. */
+int mmgpu_rescore_fetch(mmgpu_ctx *ctx, mmgpu_rescore_batch_t *batch, mmgpu_rescore_hit *out);
+/* the same records into caller-owned DEVICE memory.  Asynchronous on the context's stream. */
+int mmgpu_rescore_fetch_device(mmgpu_ctx *ctx, mmgpu_rescore_batch_t *batch, void *d_out);
+int mmgpu_rescore_last_kernel_ms(mmgpu_ctx *ctx, mmgpu_rescore_batch_t *batch, float *ms);
+void mmgpu_rescore_free(mmgpu_ctx *ctx, mmgpu_rescore_batch_t *batch);
+/* one-shot form: prepare, run, fetch, free */
+int mmgpu_rescore_batch(mmgpu_ctx *ctx, const mmgpu_rescore_params *params, const mmgpu_rescore_query *queries, uint32_t n_queries,
+                        const uint64_t *hit_off, const mmgpu_rescore_pair *pairs, mmgpu_rescore_hit *out);
+
+/* The acceptance rule of rescorediagonal.cpp:255-330 for one record, on the host (no device, no context), in the reference's own
+ * float arithmetic.  evalue: EvalueComputation::computeEvalue(score, qlen) of the caller's (ungapped) parameter set; read in modes
+ * 1 and 2 only (mode 0 passes the E-value test with 0.0, as the reference does). */
+typedef struct {
+    int mode;                /* MMGPU_RESCORE_* after --filter-hits has turned 0 into 1 */
+    int seq_id_mode;         /* --seq-id-mode: 0 alignment length, 1 shorter, 2 longer sequence */
+    float seq_id_thr;        /* --min-seq-id */
+    float cov_thr;           /* -c */
+    int cov_mode;            /* --cov-mode */
+    double evalue_thr;       /* -e */
+    int min_aln_len;         /* --min-aln-len */
+    int filter_hits;         /* --filter-hits */
+    float score_per_col_thr; /* parsePrecisionLib's threshold (read with --filter-hits only) */
+} mmgpu_rescore_accept_params;
+typedef struct {
+    int32_t accepted;        /* isIdentity || hasToFilter || (hasAlnLen && hasCov && hasSeqId && hasEvalue) */
+    int32_t aln_len;
+    float seq_id;            /* mode 2: computed only when the E-value passes or the hit is the identity, else 0 */
+    float q_cov, t_cov;
+    int32_t q_start, q_end, t_start, t_end;   /* mode 2: the alignment in sequence coordinates; else 0 */
+} mmgpu_rescore_verdict;
+int mmgpu_host_rescore_accept(const mmgpu_rescore_hit *rec, uint32_t qlen, uint32_t tlen, int is_identity, double evalue,
+                              const mmgpu_rescore_accept_params *params, mmgpu_rescore_verdict *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,8 @@ EXPORTED_SYMBOLS = [
     "mmgpu_scan_batch", "mmgpu_scan_debug_scores",
     "mmgpu_gscan_prepare", "mmgpu_gscan_run", "mmgpu_gscan_fetch", "mmgpu_gscan_fetch_device", "mmgpu_gscan_last_kernel_ms", "mmgpu_gscan_free",
     "mmgpu_gscan_batch", "mmgpu_gscan_debug_scores", "mmgpu_gscan_stage_ms",
+    "mmgpu_rescore_prepare", "mmgpu_rescore_run", "mmgpu_rescore_fetch", "mmgpu_rescore_fetch_device", "mmgpu_rescore_last_kernel_ms",
+    "mmgpu_rescore_free", "mmgpu_rescore_batch", "mmgpu_host_rescore_accept",
 ]
 
 
@@ -148,6 +150,32 @@ class GscanQuery(ctypes.Structure):      # mmgpu_gscan_query
     _fields_ = [("q", c_p), ("qlen", ctypes.c_uint32), ("comp_bias", c_p), ("profile", c_p), ("profile_letters", ctypes.c_uint32),
                 ("identity_id", ctypes.c_uint32), ("min_tlen", ctypes.c_uint32), ("max_tlen", ctypes.c_uint32),
                 ("min_evalue_score", ctypes.c_int32)]
+
+
+class RescoreParams(ctypes.Structure):      # mmgpu_rescore_params
+    _fields_ = [("mat", c_p), ("alphabet", ctypes.c_int), ("mode", ctypes.c_int)]
+
+
+class RescoreQuery(ctypes.Structure):      # mmgpu_rescore_query
+    _fields_ = [("q", c_p), ("qlen", ctypes.c_uint32)]
+
+
+class RescoreAcceptParams(ctypes.Structure):      # mmgpu_rescore_accept_params
+    _fields_ = [("mode", ctypes.c_int), ("seq_id_mode", ctypes.c_int), ("seq_id_thr", ctypes.c_float), ("cov_thr", ctypes.c_float),
+                ("cov_mode", ctypes.c_int), ("evalue_thr", ctypes.c_double), ("min_aln_len", ctypes.c_int), ("filter_hits", ctypes.c_int),
+                ("score_per_col_thr", ctypes.c_float)]
+
+
+class RescoreVerdict(ctypes.Structure):      # mmgpu_rescore_verdict
+    _fields_ = [("accepted", ctypes.c_int32), ("aln_len", ctypes.c_int32), ("seq_id", ctypes.c_float), ("q_cov", ctypes.c_float),
+                ("t_cov", ctypes.c_float), ("q_start", ctypes.c_int32), ("q_end", ctypes.c_int32), ("t_start", ctypes.c_int32),
+                ("t_end", ctypes.c_int32)]
+
+
+RESCORE_HAMMING, RESCORE_SUBSTITUTION, RESCORE_ALIGNMENT = 0, 1, 2      # mmgpu_rescore_params::mode
+RESCORE_PAIR_DTYPE = np.dtype([("target", np.uint32), ("diagonal", np.uint16), ("reserved", np.uint16)])      # mmgpu_rescore_pair
+RESCORE_HIT_DTYPE = np.dtype([("score", np.int32), ("diagonal", np.int32), ("diag_len", np.uint32), ("start", np.int32), ("end", np.int32),
+                              ("ident", np.uint32)])      # mmgpu_rescore_hit
 
 
 class PfShard(ctypes.Structure):
@@ -278,6 +306,16 @@ def load_library():
     L.mmgpu_gscan_free.restype = None
     L.mmgpu_gscan_batch.argtypes = [c_p, ctypes.POINTER(GscanParams), c_p, ctypes.c_uint32, c_p, ctypes.c_uint32, c_p]
     L.mmgpu_gscan_debug_scores.argtypes = [c_p, c_p, ctypes.c_uint32, c_p, ctypes.c_size_t]
+    L.mmgpu_rescore_prepare.argtypes = [c_p, ctypes.POINTER(RescoreParams), c_p, ctypes.c_uint32, c_p, c_p, ctypes.POINTER(c_p)]
+    L.mmgpu_rescore_run.argtypes = [c_p, c_p]
+    L.mmgpu_rescore_fetch.argtypes = [c_p, c_p, c_p]
+    L.mmgpu_rescore_fetch_device.argtypes = [c_p, c_p, c_p]
+    L.mmgpu_rescore_last_kernel_ms.argtypes = [c_p, c_p, ctypes.POINTER(ctypes.c_float)]
+    L.mmgpu_rescore_free.argtypes = [c_p, c_p]
+    L.mmgpu_rescore_free.restype = None
+    L.mmgpu_rescore_batch.argtypes = [c_p, ctypes.POINTER(RescoreParams), c_p, ctypes.c_uint32, c_p, c_p, c_p]
+    L.mmgpu_host_rescore_accept.argtypes = [c_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_double,
+                                            ctypes.POINTER(RescoreAcceptParams), ctypes.POINTER(RescoreVerdict)]
     return L
 
 
@@ -578,6 +616,42 @@ class GscanBatch(_ScanBatchBase):
         n = ctypes.c_uint32()
         self._call("stage_ms", ms, ctypes.byref(n))
         return dict(planner=ms[0], sw=ms[1], identity=ms[2], select=ms[3]), n.value
+
+
+class RescoreBatch:
+    """A prepared ungapped diagonal rescoring (mmgpu_rescore_*): queries and hit list resident in HBM."""
+
+    def __init__(self, gpu, handle, keep, n_hits):
+        self.gpu, self.handle, self._keep, self.n_hits = gpu, handle, keep, n_hits
+
+    def run(self):
+        self.gpu._check(self.gpu.L.mmgpu_rescore_run(self.gpu.ctx, self.handle))
+
+    def fetch(self):
+        """-> records[n_hits] RESCORE_HIT_DTYPE, in the order of the input list"""
+        out = np.zeros(max(self.n_hits, 1), RESCORE_HIT_DTYPE)
+        self.gpu._check(self.gpu.L.mmgpu_rescore_fetch(self.gpu.ctx, self.handle, _ptr(out)))
+        return out[:self.n_hits]
+
+    def fetch_device(self, d_out_ptr):
+        """D2D copy of the records into caller-owned device memory (raw pointer), on the context's stream"""
+        self.gpu._check(self.gpu.L.mmgpu_rescore_fetch_device(self.gpu.ctx, self.handle, c_p(d_out_ptr)))
+
+    def kernel_ms(self):
+        ms = ctypes.c_float()
+        self.gpu._check(self.gpu.L.mmgpu_rescore_last_kernel_ms(self.gpu.ctx, self.handle, ctypes.byref(ms)))
+        return ms.value
+
+    def free(self):
+        if self.handle is not None:
+            self.gpu.L.mmgpu_rescore_free(self.gpu.ctx, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class SwBatch:
@@ -1126,6 +1200,51 @@ class MMGpu:
         m = self._gscan_marshal(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
         return self._scan_batch(GscanBatch, m, len(queries), max_hits)
 
+    def _rescore_marshal(self, mat, queries, hits, mode):
+        """queries: list of uint8[] (numeric residues); hits: per query a sequence of (target id, diagonal) pairs, or an array with
+        the fields `target` (or `id`) and `diagonal` - the diagonal as the prefilter result line carries it (taken modulo 65536)"""
+        mat = np.ascontiguousarray(mat, np.int8)
+        par = RescoreParams(_ptr(mat), mat.shape[0], int(mode))
+        arr = (RescoreQuery * max(len(queries), 1))()
+        keep = [mat]
+        for i, q in enumerate(queries):
+            q = np.ascontiguousarray(q, np.uint8)
+            keep.append(q)
+            arr[i] = RescoreQuery(_ptr(q), len(q))
+        if len(hits) != len(queries):
+            raise ValueError("hits must hold one list per query")
+        off = np.zeros(len(queries) + 1, np.uint64)
+        off[1:] = np.cumsum([len(h) for h in hits])
+        pairs = np.zeros(max(int(off[-1]), 1), RESCORE_PAIR_DTYPE)
+        for i, h in enumerate(hits):
+            if not len(h):
+                continue
+            a, b = int(off[i]), int(off[i + 1])
+            if isinstance(h, np.ndarray) and h.dtype.names:
+                pairs["target"][a:b] = h["target" if "target" in h.dtype.names else "id"]
+                pairs["diagonal"][a:b] = h["diagonal"].astype(np.int64) & 0xFFFF
+            else:
+                h = np.asarray(h, np.int64).reshape(-1, 2)
+                pairs["target"][a:b] = h[:, 0]
+                pairs["diagonal"][a:b] = h[:, 1] & 0xFFFF
+        keep += [off, pairs]
+        return par, arr, off, pairs, keep
+
+    def rescore_prepare(self, mat, queries, hits, mode):
+        """mmgpu_rescore_prepare: ungapped rescoring (`rescorediagonal`) of every hit along its recorded diagonal -> RescoreBatch"""
+        par, arr, off, pairs, keep = self._rescore_marshal(mat, queries, hits, mode)
+        h = c_p()
+        self._check(self.L.mmgpu_rescore_prepare(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), _ptr(off), _ptr(pairs), ctypes.byref(h)))
+        return RescoreBatch(self, h, keep, int(off[-1]))
+
+    def rescore_batch(self, mat, queries, hits, mode):
+        """mmgpu_rescore_batch: -> records[total hits] RESCORE_HIT_DTYPE in input order"""
+        par, arr, off, pairs, keep = self._rescore_marshal(mat, queries, hits, mode)
+        out = np.zeros(max(int(off[-1]), 1), RESCORE_HIT_DTYPE)
+        self._check(self.L.mmgpu_rescore_batch(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(queries), _ptr(off), _ptr(pairs), _ptr(out)))
+        del keep
+        return out[:int(off[-1])]
+
     def pf_set_shard(self, n_shards, shard, global_db_size, global_ids, shard_of, local_id):
         """this context holds shard `shard` of a database of global_db_size targets (None-like: pf_clear_shard)"""
         g = np.ascontiguousarray(global_ids, np.uint32)
@@ -1222,6 +1341,94 @@ def exhaustive_gapped_search(gpu, mat, gap_open, gap_extend, queries, min_score=
     -> (hits[nq][stride], counts[nq], records[nq][stride] SW_HIT_DTYPE: slot k of a row = hit k of the query's list)"""
     scan = gpu.gscan_prepare(mat, gap_open, gap_extend, queries, min_score, max_hits, pair_budget)
     return _search_over_lists(gpu, scan, mat, gap_open, gap_extend, queries, mode)
+
+
+def host_rescore_accept(rec, qlen, tlen, is_identity, evalue_of_score, mode, seq_id_mode=0, min_seq_id=0.0, cov=0.0, cov_mode=0, e=0.001,
+                        min_aln_len=0, filter_hits=False, score_per_col_thr=0.0, lib=None):
+    """mmgpu_host_rescore_accept: the acceptance rule of rescorediagonal.cpp:255-330 for one record (a RESCORE_HIT_DTYPE element), in
+    the reference's float arithmetic; no device.  -> dict of mmgpu_rescore_verdict's fields"""
+    L = lib or load_library()
+    r = np.zeros(1, RESCORE_HIT_DTYPE)
+    for f in RESCORE_HIT_DTYPE.names:
+        r[0][f] = rec[f]
+    par = RescoreAcceptParams(int(mode), int(seq_id_mode), float(min_seq_id), float(cov), int(cov_mode), float(e), int(min_aln_len),
+                              int(bool(filter_hits)), float(score_per_col_thr))
+    v = RescoreVerdict()
+    if L.mmgpu_host_rescore_accept(_ptr(r), int(qlen), int(tlen), int(bool(is_identity)), float(evalue_of_score), ctypes.byref(par), ctypes.byref(v)) != 0:
+        raise MMGpuError(L.mmgpu_last_error().decode())
+    return {k: getattr(v, k) for k, _ in RescoreVerdict._fields_}
+
+
+def rescore_effective_mode(mode, filter_hits):
+    """--filter-hits cannot use the Hamming distance: rescorediagonal.cpp:96-99 turns mode 0 into mode 1"""
+    return RESCORE_SUBSTITUTION if filter_hits and int(mode) == RESCORE_HAMMING else int(mode)
+
+
+def rescore_coverable_hits(hits, qlen, target_lengths, cov=0.0, cov_mode=0):
+    """the (target, diagonal) pairs of one query that Util::canBeCovered admits: the others are dropped before anything is scored
+    (rescorediagonal.cpp:219-221)"""
+    h = np.asarray(hits, np.int64).reshape(-1, 2)
+    if not len(h):
+        return h
+    return h[_can_be_covered(cov, int(cov_mode), int(qlen), np.asarray(target_lengths, np.int64)[h[:, 0]])]
+
+
+def rescore_lists(records, qlens, hits, target_lengths, db_residues, mode, e=0.001, min_seq_id=0.0, seq_id_mode=0, cov=0.0, cov_mode=0,
+                  min_aln_len=0, filter_hits=False, score_per_col_thr=0.0, sort_results=False, backtrace=False, identity=None,
+                  evalue_par=None, lib=None):
+    """What `rescorediagonal` writes, built from the device's records.  records: RESCORE_HIT_DTYPE, one per hit, query-major in the
+    order of `hits` (per query the (target, diagonal) pairs that rescore_coverable_hits left); mode: the effective one; identity:
+    per query its own target id or None (a same-database run, --add-self-matches); score_per_col_thr: the threshold --filter-hits
+    reads from the reference's precision table for (--min-seq-id, -c, --cov-mode).  -> per query the list of
+        mode 0: (target, int(100 * seqId), diagonal as a short)          mode 1: (target, bit score, diagonal as a short)
+        mode 2: (target, bit score, seqId, E-value, qStart, qEnd, qLen, tStart, tEnd, tLen, alnLen, backtrace or None)
+    E-value and bit score: evalue.py with the ungapped parameter set (BLOSUM62_UNGAPPED unless evalue_par names another)."""
+    from . import evalue as ev
+    par = evalue_par or ev.BLOSUM62_UNGAPPED
+    tl = np.asarray(target_lengths, np.int64)
+    out, at = [], 0
+    for qi, qlen in enumerate(qlens):
+        own = None if identity is None else identity[qi]
+        lines = []
+        for target, _ in np.asarray(hits[qi], np.int64).reshape(-1, 2):
+            r = records[at]
+            at += 1
+            score, tlen = int(r["score"]), int(tl[target])
+            evalue = ev.evalue(score, qlen, db_residues, par) if mode != RESCORE_HAMMING else 0.0
+            v = host_rescore_accept(r, qlen, tlen, own is not None and int(own) == int(target), evalue, mode, seq_id_mode, min_seq_id, cov,
+                                    cov_mode, e, min_aln_len, filter_hits, score_per_col_thr, lib)
+            if not v["accepted"]:
+                continue
+            short_diag = ((int(r["diagonal"]) & 0xFFFF) ^ 0x8000) - 0x8000      # hit_t::diagonal is an unsigned short, printed as a short
+            if mode == RESCORE_HAMMING:
+                lines.append((int(target), int(100 * float(v["seq_id"])), short_diag))
+                continue
+            bits = int(ev.bit_score(score, par) + 0.5)
+            if mode == RESCORE_SUBSTITUTION:
+                lines.append((int(target), bits, short_diag))
+            else:
+                lines.append((int(target), bits, float(v["seq_id"]), evalue, v["q_start"], v["q_end"], int(qlen), v["t_start"], v["t_end"], tlen,
+                              v["aln_len"], "%dM" % v["aln_len"] if backtrace else None))
+        if sort_results and mode == RESCORE_ALIGNMENT:      # Matcher::compareHits
+            lines.sort(key=lambda x: (x[3], -x[1], x[9], x[0]))
+        elif sort_results:                                  # hit_t::compareHitsByScoreAndId
+            lines.sort(key=lambda x: (-abs(x[1]), x[0]))
+        out.append(lines)
+    return out
+
+
+def rescore_diagonal(gpu, mat, queries, hits, mode, e=0.001, min_seq_id=0.0, seq_id_mode=0, cov=0.0, cov_mode=0, min_aln_len=0,
+                     filter_hits=False, score_per_col_thr=0.0, sort_results=False, backtrace=False, identity=None, evalue_par=None):
+    """`rescorediagonal` over the resident targets: queries = list of uint8[], hits = per query the (target, diagonal) pairs of its
+    prefilter result; the options as rescore_lists names them (-e, --min-seq-id, --seq-id-mode, -c, --cov-mode, --min-aln-len,
+    --filter-hits with its score-per-column threshold as a number, --sort-results, -a).  canBeCovered drops hits before the
+    device sees them; --filter-hits turns mode 0 into mode 1.  -> per query what the module would write (rescore_lists)."""
+    mode = rescore_effective_mode(mode, filter_hits)
+    tl = gpu._target_lens
+    kept = [rescore_coverable_hits(h, len(q), tl, cov, cov_mode) for q, h in zip(queries, hits)]
+    rec = gpu.rescore_batch(mat, queries, kept, mode)
+    return rescore_lists(rec, [len(q) for q in queries], kept, tl, int(tl.sum()), mode, e, min_seq_id, seq_id_mode, cov, cov_mode, min_aln_len,
+                         filter_hits, score_per_col_thr, sort_results, backtrace, identity, evalue_par, gpu.L)
 
 
 def alt_next_spans(spans, records, accepted):

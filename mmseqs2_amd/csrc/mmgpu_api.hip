@@ -242,6 +242,7 @@ extern "C" int mmgpu_warmup(mmgpu_ctx *c) {
     mmgpu::warm_bt();
     mmgpu::warm_scan();
     mmgpu::warm_gscan();
+    mmgpu::warm_rescore();
     return MMGPU_OK;
 }
 

@@ -328,6 +328,30 @@ hipError_t launch_gscan_select(const GscanSelectArgs &A, uint32_t n_queries, hip
 void warm_gscan();
 
 // ---------------------------------------------------------------------------------------------------------
+// ungapped diagonal rescoring (rescore_api.hip, rescore_kernel.hip): one record per hit of a prefilter result list.  RESCORE_GROUP
+// lanes (one DPP row) share a hit: lane l walks cells [l * run, (l + 1) * run) of the diagonal, run = ceil(len / RESCORE_GROUP)
+// rounded up to RESCORE_STEP (the cells of one dword of residues), and the lanes' summaries are combined in diagonal order.
+constexpr int RESCORE_GROUP = 16;
+constexpr int RESCORE_STEP = 4;
+constexpr int RESCORE_THREADS = 256;      // a workgroup: 16 hits
+constexpr int RESCORE_SLACK = 16;         // bytes behind the last query: an unaligned run reads the dword behind its last cell
+
+struct RescoreArgs {
+    const uint8_t *q_res;              // every query starts on a 4-byte boundary
+    const uint32_t *q_off4, *q_len;    // [nq]
+    const uint8_t *t_res;
+    const uint32_t *t_off4, *t_len;
+    const int8_t *mat;                 // [alphabet][alphabet]
+    int alphabet;
+    const uint32_t *hit_query;         // [n_hits]
+    const mmgpu_rescore_pair *pairs;   // [n_hits]
+    uint32_t n_hits;
+    mmgpu_rescore_hit *out;            // [n_hits]
+};
+hipError_t launch_rescore(const RescoreArgs &A, int mode, hipStream_t stream);
+void warm_rescore();
+
+// ---------------------------------------------------------------------------------------------------------
 // prefilter (pf_kernels.hip)
 constexpr int PF_T = 4096;             // arrival-ordered index entries per tile (2048: 22 % slower, more tiles)
 constexpr int PF_IDS_PER_BIN = 4096;   // targets per replay bin (one 16 KB LDS state table per wavefront)

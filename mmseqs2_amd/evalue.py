@@ -16,6 +16,13 @@ BLOSUM62_11_1 = (0.27359865037097330642, 0.044620920658722244834,
                  1.5938724404943873658, -19.959867650284412122, 1.5938724404943873658, -19.959867650284412122,
                  30.455610143099914211, -622.28684628915891608, 30.455610143099914211, -622.28684628915891608,
                  29.602444874818868215, -601.81087985041381216)
+# the UNGAPPED set the reference ships for the same matrix ("blosum62.out", 0, 0, not gapped; EvalueComputation.h:75-80): what the
+# two-argument constructor EvalueComputation(dbResCount, subMat) selects - `rescorediagonal` builds its evaluer that way
+# (rescorediagonal.cpp:107), so its E-values and bit scores come from this set, not from BLOSUM62_11_1.  Pass it as `par`.
+BLOSUM62_UNGAPPED = (0.3207378152604042354, 0.13904657125294345166,
+                     0.76221128839920349041, 0.0, 0.76221128839920349041, 0.0,
+                     4.5269915477182944841, 0.0, 4.5269915477182944841, 0.0,
+                     4.5269915477182944841, 0.0)
 _NAT_CUT_OFF_IN_MAX = 2.0          # sls_pvalues.cpp:46
 _CONST = 1.0 / math.sqrt(2.0 * math.pi)
 

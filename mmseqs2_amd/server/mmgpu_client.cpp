@@ -226,6 +226,28 @@ int mmgpu_gscan_batch(mmgpu_ctx *, const mmgpu_gscan_params *, const mmgpu_gscan
 int mmgpu_gscan_debug_scores(mmgpu_ctx *, mmgpu_gscan_batch_t *, uint32_t, int32_t *, size_t) {
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_gscan_debug_scores: a test aid, not served through mmgpu_server");
 }
+// the ungapped diagonal rescoring: the binary runs rescorediagonal on the host, nothing of it crosses the socket
+int mmgpu_rescore_prepare(mmgpu_ctx *, const mmgpu_rescore_params *, const mmgpu_rescore_query *, uint32_t, const uint64_t *, const mmgpu_rescore_pair *,
+                          mmgpu_rescore_batch_t **batch) {
+    if (batch) *batch = nullptr;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_prepare: not served through mmgpu_server (the binary runs rescorediagonal on the host)");
+}
+int mmgpu_rescore_run(mmgpu_ctx *, mmgpu_rescore_batch_t *) { return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_run: not served through mmgpu_server"); }
+int mmgpu_rescore_fetch(mmgpu_ctx *, mmgpu_rescore_batch_t *, mmgpu_rescore_hit *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_fetch: not served through mmgpu_server");
+}
+int mmgpu_rescore_fetch_device(mmgpu_ctx *, mmgpu_rescore_batch_t *, void *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_fetch_device: not served through mmgpu_server");
+}
+int mmgpu_rescore_last_kernel_ms(mmgpu_ctx *, mmgpu_rescore_batch_t *, float *ms) {
+    if (ms) *ms = 0;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_last_kernel_ms: not served through mmgpu_server");
+}
+void mmgpu_rescore_free(mmgpu_ctx *, mmgpu_rescore_batch_t *) {}
+int mmgpu_rescore_batch(mmgpu_ctx *, const mmgpu_rescore_params *, const mmgpu_rescore_query *, uint32_t, const uint64_t *, const mmgpu_rescore_pair *,
+                        mmgpu_rescore_hit *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_batch: not served through mmgpu_server (the binary runs rescorediagonal on the host)");
+}
 
 int mmgpu_sw_block_tiers(const mmgpu_sw_batch_t *, uint32_t *first_tier, uint32_t *second_tier) {
     if (first_tier) *first_tier = 0;
