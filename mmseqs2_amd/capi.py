@@ -964,9 +964,12 @@ class MMGpu:
         return b
 
     # ---- nucleotide alignment step ----
-    def nucl_align(self, mat, reverse, queries, pairs, gap_open=5, gap_extend=2, zdrop=40, past_end_query=4, past_end_target=4, wrapped=False):
+    def nucl_align(self, mat, reverse, queries, pairs, gap_open=5, gap_extend=2, zdrop=40, past_end_query=4, past_end_target=4, wrapped=False,
+                   bt_cap=None):
         """queries: list of uint8 arrays (codes 0..4); pairs: structured NUCL_PAIR_DTYPE array (or list of
-        (query, target, diagonal, reverse[, past_end])).  Returns (NUCL_HIT_DTYPE array, list of backtrace strings)."""
+        (query, target, diagonal, reverse[, past_end])).  Returns (NUCL_HIT_DTYPE array, list of backtrace strings).
+        bt_cap: bytes of the backtrace buffer handed to the library (default: room for every backtrace); a pair whose string
+        did not fit has status MMGPU_NUCL_BT_OVERFLOW and None as its string.  self.last_nucl_bt_used: the call's bt_used."""
         mat = np.ascontiguousarray(mat, np.int8).reshape(-1)
         rev = np.ascontiguousarray(reverse, np.uint8)
         if not (isinstance(pairs, np.ndarray) and pairs.dtype == NUCL_PAIR_DTYPE):
@@ -985,6 +988,8 @@ class MMGpu:
         # room for every backtrace; indices are clipped here, the library is the one that rejects bad ones
         ql = np.array([len(q) for q in qs] + [0], np.int64)
         cap = int((ql[np.minimum(pairs["query"], len(qs))] + tl[np.minimum(pairs["target"], len(tl) - 1)] + 2).sum()) if len(pairs) else 16
+        if bt_cap is not None:
+            cap = int(bt_cap)
         bt = np.zeros(max(cap, 16), np.uint8)
         used = ctypes.c_uint64()
         import time
@@ -992,6 +997,7 @@ class MMGpu:
         self._check(self.L.mmgpu_nucl_align(self.ctx, ctypes.byref(par), ctypes.cast(arr, c_p), len(qs), _ptr(pairs), len(pairs),
                                             _ptr(out), _ptr(bt), cap, ctypes.byref(used)))
         self.last_nucl_call_s = time.perf_counter() - t0     # the C-ABI call alone (upload, kernel, download), no binding work
+        self.last_nucl_bt_used = int(used.value)
         raw = bt.tobytes()
         strs = [raw[int(h["bt_off"]):int(h["bt_off"]) + int(h["bt_len"])].decode() if h["status"] == 0 else None for h in out]
         return out, strs

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE - host emulation of the 16 lanes of one alignment group, so that the very source of the GPU
 // kernel (mmseqs2_amd/csrc/nucl_core.h) can be run against the reference's vectors on a machine without a GPU.
-// 16 cooperative contexts (ucontext) stand in for the lanes; a context switch happens exactly where the kernel marks a
+// 16 cooperative contexts (a stack each) stand in for the lanes; a context switch happens exactly where the kernel marks a
 // phase boundary (NUCL_SYNC) or exchanges a value inside the group, which is where lock-step lanes would see each
 // other's LDS writes.  Built and loaded by tests/test_nucl_emu.py only; nothing in the product links this.
 #include <ucontext.h>
@@ -15,11 +15,53 @@ namespace emu {
 #define EMU_LANES 16
 #endif
 constexpr int LANES = EMU_LANES;
-static ucontext_t ctx[LANES], main_ctx;
 static bool done[LANES];
 static int cur = 0, arrived = 0;
 static unsigned generation = 0;
 static unsigned long long xchg[LANES];
+
+#if defined(__x86_64__) && !defined(EMU_UCONTEXT)
+// The switch between lanes is the whole cost of the emulation (two per exchanged value and lane), and swapcontext makes a
+// system call for the signal mask every time.  On x86-64 a lane is its stack pointer: the callee-saved registers are pushed
+// on the lane's own stack, the stack pointers are swapped, the other lane's registers are popped.
+extern "C" void nucl_emu_swap(void **save_sp, void *load_sp);
+asm(".text\n"
+    ".hidden nucl_emu_swap\n"
+    ".globl nucl_emu_swap\n"
+    ".type nucl_emu_swap,@function\n"
+    "nucl_emu_swap:\n"
+    "    pushq %rbp\n    pushq %rbx\n    pushq %r12\n    pushq %r13\n    pushq %r14\n    pushq %r15\n"
+    "    movq %rsp, (%rdi)\n"
+    "    movq %rsi, %rsp\n"
+    "    popq %r15\n    popq %r14\n    popq %r13\n    popq %r12\n    popq %rbx\n    popq %rbp\n"
+    "    ret\n"
+    ".size nucl_emu_swap,.-nucl_emu_swap\n");
+static void *lane_sp[LANES], *main_sp;
+static void lane_to_lane(int from, int to) { nucl_emu_swap(&lane_sp[from], lane_sp[to]); }
+static void lane_to_main(int from) { nucl_emu_swap(&lane_sp[from], main_sp); }
+static void main_to_lane(int to) { nucl_emu_swap(&main_sp, lane_sp[to]); }
+static void make_lane(int l, char *stack, size_t size, void (*entry)()) {
+    // what nucl_emu_swap pops: six registers, then `entry` as its return address; entry never returns (the slot above it
+    // keeps the stack 16-byte aligned at entry, as after a call)
+    void **top = reinterpret_cast<void **>(reinterpret_cast<uintptr_t>(stack + size) & ~(uintptr_t)15);
+    top[-1] = nullptr;
+    top[-2] = reinterpret_cast<void *>(entry);
+    for (int k = 3; k <= 8; k++) top[-k] = nullptr;
+    lane_sp[l] = top - 8;
+}
+#else
+static ucontext_t ctx[LANES], main_ctx;
+static void lane_to_lane(int from, int to) { swapcontext(&ctx[from], &ctx[to]); }
+static void lane_to_main(int from) { swapcontext(&ctx[from], &main_ctx); }
+static void main_to_lane(int to) { swapcontext(&main_ctx, &ctx[to]); }
+static void make_lane(int l, char *stack, size_t size, void (*entry)()) {
+    getcontext(&ctx[l]);
+    ctx[l].uc_stack.ss_sp = stack;
+    ctx[l].uc_stack.ss_size = size;
+    ctx[l].uc_link = &main_ctx;
+    makecontext(&ctx[l], entry, 0);
+}
+#endif
 
 static void switch_to_next() {
     int from = cur;
@@ -28,11 +70,11 @@ static void switch_to_next() {
         if (!done[n]) {
             if (n == from) return;
             cur = n;
-            swapcontext(&ctx[from], &ctx[n]);
+            lane_to_lane(from, n);
             return;
         }
     }
-    swapcontext(&ctx[from], &main_ctx);   // every lane has finished
+    lane_to_main(from);   // every lane has finished
 }
 
 static void sync() {
@@ -165,14 +207,10 @@ extern "C" int nucl_emu_align(const mmgpu_nucl_params *par, const mmgpu_nucl_que
     emu::generation = 0;
     for (int l = 0; l < emu::LANES; l++) {
         emu::done[l] = false;
-        getcontext(&emu::ctx[l]);
-        emu::ctx[l].uc_stack.ss_sp = stacks.data() + stack * l;
-        emu::ctx[l].uc_stack.ss_size = stack;
-        emu::ctx[l].uc_link = &emu::main_ctx;
-        makecontext(&emu::ctx[l], lane_main, 0);
+        emu::make_lane(l, stacks.data() + stack * l, stack, lane_main);
     }
     emu::cur = 0;
-    swapcontext(&emu::main_ctx, &emu::ctx[0]);
+    emu::main_to_lane(0);
     if (bt_used) *bt_used = counters[0];
     return 0;
 }
