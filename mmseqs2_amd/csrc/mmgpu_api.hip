@@ -572,9 +572,16 @@ static TargetView sw_targets(const mmgpu_ctx *c, const mmgpu_sw_batch_t *b) {
 
 // which kernel body serves a query of this length: 16 lanes x R rows per tile (any R since round 5: the padding of a tile is
 // below 16 rows, it was below 32 with even R only), at most 16 * SW_MAX_R rows per tile; longer queries are cut into equal tiles
-// (multi-tile bodies).
-static void pick_class(uint32_t qlen, int *rows_per_lane, bool *multi) {
+// (multi-tile bodies).  wide: a query of up to 32 * SW_MAX_R rows is one tile of a 32-lane group (R = ceil(qlen / 32)) instead of two
+// tiles - a single-tile job in every respect: no scratch slot, no reverse job, rounds of 16 hits (four per wavefront).
+static void pick_class(uint32_t qlen, int *rows_per_lane, bool *multi, bool *wide) {
     constexpr uint32_t max_rows = 16u * (uint32_t)SW_MAX_R;
+    *wide = mmgpu::sw_wide_enabled() && qlen > max_rows && qlen <= 2 * max_rows;
+    if (*wide) {
+        *rows_per_lane = (int)((qlen + 31) / 32);
+        *multi = false;
+        return;
+    }
     const uint32_t n_tiles = (qlen + max_rows - 1) / max_rows;
     const uint32_t rows = (qlen + n_tiles - 1) / n_tiles;       // rows per tile before rounding
     *rows_per_lane = (int)std::max<uint32_t>(1u, (rows + 15) / 16);
@@ -916,17 +923,19 @@ int SwPrepare::copy_queries() {
         }
         int qminp;
         if (int e = copy_query(i, &qminp)) return e;
-        int rpl; bool multi;
-        pick_class(Q.qlen, &rpl, &multi);
+        int rpl; bool multi, wide;
+        pick_class(Q.qlen, &rpl, &multi, &wide);
         any_multi |= multi;
-        const uint32_t shape = (multi ? 32u : 0u) + (uint32_t)rpl - 1;   // [0,32): single tile R = 1..32, [32,64): multi-tile
+        // [0,32): single tile R = 1..32, [32,64): multi-tile, [64,96): single tile on 32-lane groups
+        const uint32_t shape = (multi ? SW_SHAPE_MULTI : wide ? SW_SHAPE_WIDE : 0u) + (uint32_t)rpl - 1;
         const int grp = sw_shape_group(shape);
         // a multi-tile job that fits keeps the profiles of all its tiles (sw_multi_resident: the kernel asks the same question)
         const uint32_t held = multi && sw_multi_resident(sw_tiles(Q.qlen, rpl), rpl, par->alphabet, SW_RESIDENT_LDS) ? sw_tiles(Q.qlen, rpl) : 1u;
-        b->group_lds[grp] = std::max(b->group_lds[grp], (size_t)held * sw_profile_bytes(rpl, par->alphabet));
+        b->group_lds[grp] = std::max(b->group_lds[grp], (size_t)held * sw_profile_bytes(rpl, par->alphabet, wide ? 32 : 16));
         // jobs are cut at multiples of one workgroup round (4 waves x 8 targets); for queries of several tiles a
         // single wave's 8 targets already run for milliseconds, so those are cut per wave to shorten the tail
-        const uint32_t round = (multi && Q.qlen >= LONG_QUERY) ? JOB_ROUND / 4 : JOB_ROUND;
+        // (a wide job's workgroup round is 4 waves x 4 targets)
+        const uint32_t round = (multi && Q.qlen >= LONG_QUERY) ? JOB_ROUND / 4 : wide ? JOB_ROUND / 2 : JOB_ROUND;
         const uint32_t n_slots = pf ? pf_stride : dense ? dense->count[i] : Q.n_targets;
         if (pf) add_slot_jobs(i, shape, round, multi);
         // caller-supplied list: the sort by target length and the job cuts are done for all queries in parallel (cut_list_jobs)
@@ -1490,6 +1499,7 @@ static int sw_launch_groups(mmgpu_ctx *c, mmgpu_sw_batch_t *b, bool rev_only, co
             L.rev_mode = rev_only ? 2 : (b->mode == MMGPU_SW_START_NOT_WORD ? 1 : 0);
             L.rev_only = rev_only ? 1 : 0;
             L.rev_force = rev_force;
+            L.half_wide = sw_half_wide() ? 1 : 0;
             HIP_TRY(launch_sw(L, g, b->group_lds[g], b->mode >= MMGPU_SW_START, st));
             if (g == SW_GROUPS - 1 && b->n_rev_jobs && b->mode >= MMGPU_SW_START) {   // reads the forward results of this stream's kernel
                 SwLaunch Rv = L;

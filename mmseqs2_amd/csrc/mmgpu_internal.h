@@ -68,7 +68,8 @@ struct SwJob {
     uint32_t query;
     uint32_t hit_begin;
     uint32_t hit_end;
-    uint32_t shape;   // low 8 bits: tile shape (rows per lane - 1, + 32 for multi-tile); high 24: multi-tile scratch slot
+    uint32_t shape;   // low 8 bits: tile shape (rows per lane - 1, + 32 for multi-tile, + 64 for a single tile on 32-lane groups);
+                      // high 24: multi-tile scratch slot
 };
 
 // Everything a Smith-Waterman launch needs, device pointers only.
@@ -117,6 +118,9 @@ struct SwLaunch {
     int rev_mode = 0;
     int rev_only = 0;
     const uint8_t *rev_force = nullptr;
+    // the wide (32-lane) bodies of an f16 kernel: 1 = f16 forward scan first like the 16-lane bodies, 0 = every pair goes straight to the
+    // int16 scan of the marked pairs (sw_half_wide, below)
+    int half_wide = 1;
 };
 
 constexpr int SW_PF_MAX_LIST = 16384;  // longest list of the fused hand-over (sw_from_pf_kernel orders it in LDS, 4 bytes per slot; PF_MAX_HITS is the prefilter's own LDS limit)
@@ -183,9 +187,9 @@ __host__ __device__ constexpr int lane_stride_bytes(int R) {
     if ((slots & 1) == 0) slots += 1;
     return slots * 16;
 }
-// one tile's profile: (alphabet + 1) letters x 16 lanes x the lane stride
-__host__ __device__ constexpr uint32_t sw_profile_bytes(int R, int alphabet) {
-    return (uint32_t)(alphabet + 1) * 16u * (uint32_t)lane_stride_bytes(R);
+// one tile's profile: (alphabet + 1) letters x the lanes of a group (16, or 32 for the wide shapes) x the lane stride
+__host__ __device__ constexpr uint32_t sw_profile_bytes(int R, int alphabet, int lanes = 16) {
+    return (uint32_t)(alphabet + 1) * (uint32_t)lanes * (uint32_t)lane_stride_bytes(R);
 }
 // Build knob for A/B measurements: the LDS a multi-tile job may fill with the profiles of all its tiles (header included).  64 KB is
 // what a workgroup may ask for without the launch attribute that raises the ceiling; 0 = no job is resident (every tile's profile is
@@ -204,6 +208,20 @@ __host__ __device__ constexpr bool sw_multi_resident(uint32_t n_tiles, int R, in
 // 21 letters, 64 KB: two tiles of any R (56 320 bytes + header at R = 28), three of R <= 24; not three of R >= 25, not four
 static_assert(sw_multi_resident(2, 28, 21, 65536) && sw_multi_resident(3, 24, 21, 65536) && !sw_multi_resident(3, 25, 21, 65536) &&
               !sw_multi_resident(4, 22, 21, 65536) && !sw_multi_resident(2, 8, 21, 0), "residency rule");
+
+// Wide shapes: a query of 16 * SW_MAX_R + 1 .. 32 * SW_MAX_R residues is ONE tile of a 32-lane group (two DPP rows, sw_body.h) instead
+// of two tiles of a 16-lane group: R = ceil(qlen / 32) rows per lane, shape code SW_SHAPE_WIDE + R - 1.  Its profile is what the two
+// resident tiles took, so it fits the same LDS budget.
+constexpr uint32_t SW_SHAPE_MULTI = 32, SW_SHAPE_WIDE = 64;
+constexpr int SW_WIDE_MIN_R = (16 * SW_MAX_R + 1 + 31) / 32;   // rows per lane of the shortest wide query
+static_assert(sw_profile_bytes(SW_MAX_R, 21, 32) == 2 * sw_profile_bytes(SW_MAX_R, 21) &&
+              sw_profile_bytes(SW_MAX_R, 21, 32) + SW_LDS_HEADER <= 65536u, "a wide tile fits a workgroup's 64 KB");
+static_assert((lane_stride_bytes(SW_MAX_R) / 16) % 2 == 1 && (lane_stride_bytes(SW_WIDE_MIN_R) / 16) % 2 == 1, "odd number of 16-byte slots");
+// Runtime switches for A/B runs and the tests (read from the environment once per process):
+// MMGPU_SW_WIDE=0 keeps those queries on the two-tile path (the shapes of before the wide groups);
+// MMGPU_SW_HALF_WIDE=0 / 1: the forward scan of the wide bodies in int16 / in f16 with the int16 re-run; unset = the measured default.
+bool sw_wide_enabled();
+bool sw_half_wide();
 
 // ---------------------------------------------------------------------------------------------------------
 // exhaustive ungapped scan (scan_kernel.hip): every query against every resident target of its length window

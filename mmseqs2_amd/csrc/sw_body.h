@@ -9,10 +9,10 @@ namespace mmgpu {
 
 namespace {
 
-constexpr int GROUP = 16;            // lanes per target pair (one DPP row)
+constexpr int GROUP = 16;            // lanes per target pair (one DPP row); the wide bodies (W = 32) give a pair two rows
 constexpr int WAVES = 4;             // waves per workgroup
 constexpr int GROUPS_PER_WAVE = 64 / GROUP;
-constexpr int HITS_PER_WAVE = 2 * GROUPS_PER_WAVE;   // two targets per group (lo/hi halves)
+constexpr int HITS_PER_WAVE = 2 * GROUPS_PER_WAVE;   // two targets per group (lo/hi halves); 2 * 64 / W in a body of W-lane groups
 constexpr unsigned NEG2 = 0x80008000u;               // packed (-32768, -32768)
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -73,13 +73,25 @@ __device__ __forceinline__ unsigned h_max3(unsigned a, unsigned b, unsigned c) {
 }
 __device__ __forceinline__ unsigned short h_bits(int v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
 __device__ __forceinline__ int h_value(unsigned bits) { return (int)(float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
-// value of the lane one below inside the 16-lane row; lane 0 of each row keeps `head`
-__device__ __forceinline__ unsigned from_lane_above(unsigned head, unsigned v) {
-    return __builtin_amdgcn_update_dpp(head, v, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
+// A group of W = 32 lanes is two DPP rows, and row_shr stops at the row boundary: a second move, wave_shr:1 restricted to the
+// first bank of the odd rows (row_mask 0xA, bank_mask 0x1: lanes 16 - 19 and 48 - 51), gives lane 16 of the group the value of lane
+// 15 - lanes 17 - 19 get once more what row_shr gave them, the group's head lane (0, 32) keeps what the first move left there.
+// One VALU op more per hand-off, no LDS, no bpermute.
+template <int W>
+__device__ __forceinline__ unsigned across_rows(unsigned x, unsigned v) {
+    static_assert(W == 16 || W == 32, "groups of one or two DPP rows");
+    if constexpr (W == 32) x = __builtin_amdgcn_update_dpp(x, v, 0x138 /*wave_shr:1*/, 0xA, 0x1, false);
+    return x;
 }
-// ... lane 0 of each row gets 0 (bound_ctrl): no register has to hold the zero
+// value of the lane one below inside the W-lane group; lane 0 of each group keeps `head`
+template <int W = GROUP>
+__device__ __forceinline__ unsigned from_lane_above(unsigned head, unsigned v) {
+    return across_rows<W>(__builtin_amdgcn_update_dpp(head, v, 0x111 /*row_shr:1*/, 0xF, 0xF, false), v);
+}
+// ... lane 0 of each group gets 0 (bound_ctrl): no register has to hold the zero
+template <int W = GROUP>
 __device__ __forceinline__ unsigned from_lane_above_or_zero(unsigned v) {
-    return __builtin_amdgcn_update_dpp(0u, v, 0x111 /*row_shr:1*/, 0xF, 0xF, true);
+    return across_rows<W>(__builtin_amdgcn_update_dpp(0u, v, 0x111 /*row_shr:1*/, 0xF, 0xF, true), v);
 }
 
 // Build knob for A/B measurements (no test builds with 0; the default is what the suite and the bench run):
@@ -92,21 +104,21 @@ __device__ __forceinline__ unsigned from_lane_above_or_zero(unsigned v) {
 #define SW_KEEP_IN_ROW(x) asm volatile("" : "+v"(x))
 
 // (lane_stride_bytes and the size of a tile's profile: mmgpu_internal.h, shared with the host's LDS sizing)
-template <int R>
+template <int R, int W = GROUP>
 struct Tile {
-    static constexpr int ROWS = GROUP * R;
+    static constexpr int ROWS = W * R;
     static constexpr int LANE_STRIDE = lane_stride_bytes(R);
-    static constexpr int ROW_STRIDE = GROUP * LANE_STRIDE;   // bytes per letter
+    static constexpr int ROW_STRIDE = W * LANE_STRIDE;   // bytes per letter
 };
-static_assert(GROUP == 16, "sw_profile_bytes and sw_tiles (mmgpu_internal.h) assume 16-lane groups");
+static_assert(GROUP == 16, "sw_profile_bytes' default and sw_tiles (mmgpu_internal.h) assume 16-lane groups for all but the wide shapes");
 
 // Build P[letter][row] for rows [tile_base, tile_base + ROWS) of the query (or of the reversed query).
 // Rows past the query end and the extra letter `alphabet` (padding column of a finished target) are
 // -32768, which keeps H at max(E, F) there and can never raise a running maximum.  HALF: the same values as f16.
-template <int R, bool REV, bool HALF = false>
+template <int R, bool REV, bool HALF = false, int W = GROUP>
 __device__ __forceinline__ void build_profile(unsigned char *lds, const uint8_t *q, const int8_t *cb, int qlen,
                                               int tile_base, const int8_t *mat, int alphabet, const int8_t *prof) {
-    using T = Tile<R>;
+    using T = Tile<R, W>;
     const int total = (alphabet + 1) * T::ROWS;
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
         const int letter = idx / T::ROWS;
@@ -149,11 +161,15 @@ __device__ __forceinline__ uint32_t sw_half_any_marked() {
 // HALF: the cells are computed in packed f16 (above, at SW_HALF_LIMIT); a pair whose score exceeds SW_HALF_LIMIT gets SW_HALF_MARK
 //   for a result and raises the workgroup's flag in the LDS header.
 // MARKED: the int16 forward scan of the pairs so marked, packed to the front like the live pairs of the reverse scan.
-template <int R, bool MULTI, bool REV, bool PF, bool HALF = false, bool MARKED = false>
+// W: lanes of a group, 16 or 32 (wide: a single tile of up to 32 R rows, four pairs per wavefront; the hand-off crosses the DPP row
+//   boundary in the middle of the group, across_rows above).  Multi-tile bodies are 16 lanes wide.
+template <int R, bool MULTI, bool REV, bool PF, bool HALF = false, bool MARKED = false, int W = GROUP>
 __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
     static_assert(!(HALF || MARKED) || (!MULTI && !REV && !(HALF && MARKED)), "f16 and its int16 re-run: single-tile forward scans");
+    static_assert(W == GROUP || (W == 2 * GROUP && !MULTI), "the boundary row of a multi-tile body rotates inside one DPP row");
     constexpr bool PACKED = REV || MARKED;   // the job's pairs to scan are the ones listed in `live`
-    using T = Tile<R>;
+    constexpr int HITS_PER_WAVE = 2 * 64 / W;   // (W = 16: the file's constant)
+    using T = Tile<R, W>;
     // dynamic LDS: a 1 KB header (job-local scheduling state, below) followed by the query profile of the tile
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
     uint16_t *live = reinterpret_cast<uint16_t *>(lds_all);                  // [SW_REV_JOB_HITS] packed live hits (reverse pass)
@@ -166,8 +182,8 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
     if (MULTI) __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = lane & (GROUP - 1);
-    const int grp = lane / GROUP;
+    const int g = lane & (W - 1);
+    const int grp = lane / W;
 
     const uint32_t qbeg = L.q_off[job.query];
     const int qlen = (int)(L.q_off[job.query + 1] - qbeg);
@@ -199,7 +215,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
     if (threadIdx.x == 0) *next_chunk = 0;
     if (HALF && threadIdx.x == 0) *half_flag = 0;
     if (!MULTI && !PACKED) {
-        build_profile<R, REV, HALF>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
+        build_profile<R, REV, HALF, W>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
         __syncthreads();
     }
     if (MULTI && !REV && resident) build_all_tiles();
@@ -238,7 +254,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
         n_hits = total;
         if (n_hits == 0) return;      // (workgroup-uniform) no pair of this job needs a start position: no profile either
         if (!MULTI) {
-            build_profile<R, REV>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
+            build_profile<R, REV, false, W>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
             __syncthreads();
         }
         if (MULTI && resident) build_all_tiles();
@@ -246,7 +262,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
     const uint32_t n_iter = (n_hits + WAVES * HITS_PER_WAVE - 1) / (WAVES * HITS_PER_WAVE);
 
     for (uint32_t it = 0; dynamic || it < n_iter; ++it) {
-        // Single-tile and resident jobs: a wave takes the next chunk of 8 hits when it is done with its last one (the hits
+        // Single-tile and resident jobs: a wave takes the next chunk of 8 hits (4 in a wide body) when it is done with its last one (the hits
         // are sorted by length, so fixed wave <-> chunk striping would give wave 0 the longest chunk of every round).
         // The other multi-tile jobs rebuild the profile per tile with all threads, so their waves stay in step.
         uint32_t chunk = it * WAVES + wave;
@@ -292,7 +308,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
         ncols = max(ncols, __shfl_xor(ncols, 16));
         ncols = max(ncols, __shfl_xor(ncols, 32));
         ncols = __builtin_amdgcn_readfirstlane(ncols);
-        const int nsteps = ncols + GROUP - 1;
+        const int nsteps = ncols + W - 1;
         // the shortest target of the wavefront (a half without a pair counts as 0 columns): letter blocks that end at or
         // before it hold no padding column in any group
         int mincols = colsA < colsB ? colsA : colsB;
@@ -454,7 +470,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                 return (c < colsA ? la0 : pad_letter) | ((c < colsB ? lb0 : pad_letter) << 8);
             };
             letter_block(0);
-            let = from_lane_above(head_letters(0, 0), let);
+            let = from_lane_above<W>(head_letters(0, 0), let);
             if (PF) load_rows(let, pav_next, pbv_next);
 
             // blocks of four steps, one dword of letters per target and block.  Step s hands on the letters of column
@@ -477,8 +493,8 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                 if (has_below && s >= GROUP) {
                     if (g == GROUP - 1) (scr_out + (s - GROUP))[scr_grp] = make_uint2(out_H, out_F);
                 }
-                const unsigned Hup = MULTI ? from_lane_above(bnd.x, out_H) : from_lane_above_or_zero(out_H);
-                unsigned f = MULTI ? from_lane_above(bnd.y, out_F) : from_lane_above_or_zero(out_F);
+                const unsigned Hup = MULTI ? from_lane_above<W>(bnd.x, out_H) : from_lane_above_or_zero<W>(out_H);
+                unsigned f = MULTI ? from_lane_above<W>(bnd.y, out_F) : from_lane_above_or_zero<W>(out_F);
                 if (MULTI) {
                     // the live stretch moves up one lane (row_ror:15)
                     bnd.x = __builtin_amdgcn_update_dpp(bnd.x, bnd.x, 0x12F, 0xF, 0xF, false);
@@ -535,7 +551,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
                         es[r] = pk_sub_sat_u(E[r], ge2);
                     }
                 }
-                let = from_lane_above(head_letters(s + 1, j), let);   // the next column's letters (PF: and profile rows)
+                let = from_lane_above<W>(head_letters(s + 1, j), let);   // the next column's letters (PF: and profile rows)
                 if (PF) load_rows(let, pav_next, pbv_next);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
@@ -622,7 +638,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             unsigned long long keyA = sA ? ((unsigned long long)sA << 32) | ((0xFFFFu - (bestcol & 0xFFFFu)) << 16) | (0xFFFFu - rgA) : 0ull;
             unsigned long long keyB = sB ? ((unsigned long long)sB << 32) | ((0xFFFFu - (bestcol >> 16)) << 16) | (0xFFFFu - rgB) : 0ull;
 #pragma unroll
-            for (int m = 1; m < GROUP; m <<= 1) {
+            for (int m = 1; m < W; m <<= 1) {
                 const unsigned long long oa = __shfl_xor(keyA, m), ob = __shfl_xor(keyB, m);
                 keyA = oa > keyA ? oa : keyA;
                 keyB = ob > keyB ? ob : keyB;
@@ -679,19 +695,20 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
 // multi-tile shape (212 / 256).  Each group is one grid, longest job first; the three run concurrently.
 // BOTH = false: forward scan only (MMGPU_SW_SCORE_END).  BOTH = true: the workgroup runs the reverse scan of its own
 // pairs right after their forward scan - no grid-wide barrier between the passes, so the batch has one tail, not two.
-template <int R, bool MULTI, bool BOTH>
+// W = 32: the wide single-tile bodies (queries of 16 * SW_MAX_R + 1 .. 32 * SW_MAX_R residues); only the R such a query can have exist.
+template <int R, bool MULTI, bool BOTH, int W = GROUP>
 __device__ __forceinline__ void sw_passes(const SwLaunch &L, const SwJob &job) {
-    if constexpr (R <= SW_MAX_R) {
+    if constexpr (R <= SW_MAX_R && (W == GROUP || R >= SW_WIDE_MIN_R)) {
         // the prefetch goes where it costs no wavefront and no wait states: not into the forward-only kernel of R = 25 .. 28
         // (183 registers, two wavefronts instead of three) and not into the multi-tile bodies (with it the compiler puts a
         // wait state into every row of phase 2 again, profiles/sw_isa_audit.txt)
         constexpr bool PF = MMGPU_SW_PREFETCH && !MULTI && (BOTH || R <= 24);
-        if (!(BOTH && L.rev_only)) sw_body<R, MULTI, false, PF>(L, job);
+        if (!(BOTH && L.rev_only)) sw_body<R, MULTI, false, PF, false, false, W>(L, job);
         // multi-tile queries get their reverse scan from sw_rev_multi_kernel (below), per query instead of per job
         if constexpr (BOTH && !MULTI) {
             __threadfence_block();   // the forward results of this job, written by other waves of the workgroup
             __syncthreads();
-            sw_body<R, MULTI, true, PF>(L, job);
+            sw_body<R, MULTI, true, PF, false, false, W>(L, job);
         }
     }
 }

@@ -41,6 +41,13 @@
 //    Where the profiles of all tiles fit the workgroup's LDS (two tiles always, three up to R = 24 with 21 letters:
 //    sw_multi_resident, mmgpu_internal.h) they are built once per job and the tile loop only moves the LDS base;
 //    otherwise the one profile is rebuilt per tile, between two barriers.
+//  * wide groups: a query of 16 * SW_MAX_R + 1 .. 32 * SW_MAX_R residues (449 .. 896) is not two tiles but ONE tile of a group of
+//    32 lanes (two DPP rows, two groups and four pairs per wave64): lane g of 32 owns R = ceil(qlen / 32) rows, and the job is a
+//    single-tile job - f16 forward scan, row prefetch, reverse scan in the workgroup, no scratch line, no slot, no tile loop.  The
+//    hand-off crosses the row boundary with one more move per value, v_mov_b32_dpp wave_shr:1 row_mask:0xa bank_mask:0x1 behind the
+//    row_shr:1 (lanes 16 - 19 and 48 - 51 are rewritten: lane 16 gets lane 15's value, the others what they had): 14 instead of 11
+//    instructions beside the rows, still no LDS and no bpermute (profiles/sw_wide_isa_audit.txt).  Shape codes 64 + R - 1, served
+//    by the grids of groups 1 (R <= 24) and 2 by register need; MMGPU_SW_WIDE=0 in the environment restores the two tiles.
 //
 // Bytes per cell that ever touch HBM: (tlen + 28) / (qlen * tlen) ~ 0.003 - this kernel
 // is bound by VALU issue, not by HBM.
@@ -80,7 +87,7 @@ __attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_S
     // workgroups of this kernel can be resident at once, so the search always ends; a slot is only ever read after its
     // owner wrote it (tile t writes what tile t + 1 reads), so stale content is harmless.
     __shared__ uint32_t scratch_slot;
-    const bool claims = G == SW_GROUPS - 1 && (job.shape & 0xFFu) >= 32u;
+    const bool claims = G == SW_GROUPS - 1 && (job.shape & 0xFFu) >= SW_SHAPE_MULTI && (job.shape & 0xFFu) < SW_SHAPE_WIDE;
     if (claims) {
         if (threadIdx.x == 0) {
             uint32_t s = blockIdx.x % L.scratch_slots;
@@ -92,6 +99,12 @@ __attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_S
     }
 #define MMGPU_SW_SINGLE(R) case (R) - 1: sw_passes<R, false, BOTH>(L, job); break;
 #define MMGPU_SW_MULTI(R) case 32 + (R) - 1: sw_passes<R, true, BOTH>(L, job); break;
+#define MMGPU_SW_WIDE(R) case 64 + (R) - 1: sw_passes<R, false, BOTH, 2 * GROUP>(L, job); break;   // (sw_passes: only the R a wide query can have)
+#define MMGPU_SW_WIDE_M MMGPU_SW_WIDE(8) MMGPU_SW_WIDE(9) MMGPU_SW_WIDE(10) MMGPU_SW_WIDE(11) MMGPU_SW_WIDE(12) MMGPU_SW_WIDE(13)                \
+    MMGPU_SW_WIDE(14) MMGPU_SW_WIDE(15) MMGPU_SW_WIDE(16) MMGPU_SW_WIDE(17) MMGPU_SW_WIDE(18) MMGPU_SW_WIDE(19) MMGPU_SW_WIDE(20)               \
+    MMGPU_SW_WIDE(21) MMGPU_SW_WIDE(22) MMGPU_SW_WIDE(23) MMGPU_SW_WIDE(24)
+#define MMGPU_SW_WIDE_L MMGPU_SW_WIDE(25) MMGPU_SW_WIDE(26) MMGPU_SW_WIDE(27) MMGPU_SW_WIDE(28) MMGPU_SW_WIDE(29) MMGPU_SW_WIDE(30)            \
+    MMGPU_SW_WIDE(31) MMGPU_SW_WIDE(32)
     if constexpr (G == 0) {
         switch (job.shape & 0xFFu) {   // workgroup-uniform
             MMGPU_SW_SINGLE(1) MMGPU_SW_SINGLE(2) MMGPU_SW_SINGLE(3) MMGPU_SW_SINGLE(4) MMGPU_SW_SINGLE(5) MMGPU_SW_SINGLE(6)
@@ -102,12 +115,14 @@ __attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_S
         switch (job.shape & 0xFFu) {
             MMGPU_SW_SINGLE(13) MMGPU_SW_SINGLE(14) MMGPU_SW_SINGLE(15) MMGPU_SW_SINGLE(16) MMGPU_SW_SINGLE(17) MMGPU_SW_SINGLE(18)
             MMGPU_SW_SINGLE(19) MMGPU_SW_SINGLE(20) MMGPU_SW_SINGLE(21) MMGPU_SW_SINGLE(22) MMGPU_SW_SINGLE(23) MMGPU_SW_SINGLE(24)
+            MMGPU_SW_WIDE_M
             default: break;
         }
     } else if constexpr (SW_GROUPS == 4 && G == 2) {
         switch (job.shape & 0xFFu) {
             MMGPU_SW_SINGLE(25) MMGPU_SW_SINGLE(26) MMGPU_SW_SINGLE(27) MMGPU_SW_SINGLE(28) MMGPU_SW_SINGLE(29) MMGPU_SW_SINGLE(30)
             MMGPU_SW_SINGLE(31) MMGPU_SW_SINGLE(32)
+            MMGPU_SW_WIDE_L
             default: break;
         }
     } else if constexpr (SW_GROUPS == 4) {
@@ -119,6 +134,7 @@ __attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_S
         switch (job.shape & 0xFFu) {
             MMGPU_SW_SINGLE(25) MMGPU_SW_SINGLE(26) MMGPU_SW_SINGLE(27) MMGPU_SW_SINGLE(28) MMGPU_SW_SINGLE(29) MMGPU_SW_SINGLE(30)
             MMGPU_SW_SINGLE(31) MMGPU_SW_SINGLE(32)
+            MMGPU_SW_WIDE_L
             MMGPU_SW_MULTI_ALL
             default: break;
         }
@@ -126,6 +142,9 @@ __attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_S
 #undef MMGPU_SW_SINGLE
 #undef MMGPU_SW_MULTI
 #undef MMGPU_SW_MULTI_ALL
+#undef MMGPU_SW_WIDE
+#undef MMGPU_SW_WIDE_M
+#undef MMGPU_SW_WIDE_L
     if (claims) {
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -273,10 +292,25 @@ hipError_t launch_sw_rev_multi(const SwLaunch &L, size_t lds_bytes, hipStream_t 
     return hipGetLastError();
 }
 
+// by register need: a wide body has the registers of the 16-lane single-tile body of its R
 int sw_shape_group(uint32_t shape) {
-    if (shape >= 32) return SW_GROUPS - 1;
+    if (shape >= SW_SHAPE_WIDE) return (int)(shape - SW_SHAPE_WIDE) + 1 <= 24 ? 1 : 2;
+    if (shape >= SW_SHAPE_MULTI) return SW_GROUPS - 1;
     const int R = (int)shape + 1;
     return R <= 12 ? 0 : (R <= 24 ? 1 : 2);
+}
+
+static bool env_switch(const char *name, bool unset) {
+    const char *v = getenv(name);
+    return v && *v ? atoi(v) != 0 : unset;
+}
+bool sw_wide_enabled() {
+    static const bool on = env_switch("MMGPU_SW_WIDE", true);
+    return on;
+}
+bool sw_half_wide() {
+    static const bool on = env_switch("MMGPU_SW_HALF_WIDE", true);
+    return on;
 }
 
 // May this batch's single-tile forward scans run in f16 (sw_half_kernel.hip)?  The exactness rule of sw_body.h (at SW_HALF_LIMIT)
@@ -289,7 +323,7 @@ static bool sw_half_eligible(const SwLaunch &L) {
 }
 
 hipError_t launch_sw(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream) {
-    static_assert(GROUP == 16, "the shape codes assume 16-lane groups");
+    static_assert(GROUP == 16 && SW_SHAPE_MULTI == 32 && SW_SHAPE_WIDE == 64, "the shape codes of the dispatch: 16-lane groups, + 32 multi-tile, + 64 wide");
     if (L.n_jobs == 0) return hipSuccess;
     if (sw_half_eligible(L) && launch_sw_half(L, group, lds_bytes, both_passes, stream)) return hipGetLastError();
     dim3 grid(L.n_jobs), block(WAVES * 64);

@@ -48,6 +48,13 @@ PROBE(k_mov_dpp, "v_mov_b32_dpp %0, %1 row_shr:1 row_mask:0xf bank_mask:0xf\nv_m
                  "v_mov_b32_dpp %2, %3 row_shr:1 row_mask:0xf bank_mask:0xf\nv_mov_b32_dpp %3, %4 row_shr:1 row_mask:0xf bank_mask:0xf\n"
                  "v_mov_b32_dpp %4, %5 row_shr:1 row_mask:0xf bank_mask:0xf\nv_mov_b32_dpp %5, %6 row_shr:1 row_mask:0xf bank_mask:0xf\n"
                  "v_mov_b32_dpp %6, %7 row_shr:1 row_mask:0xf bank_mask:0xf\nv_mov_b32_dpp %7, %0 row_shr:1 row_mask:0xf bank_mask:0xf")
+// the move that carries the hand-off across the DPP row boundary of a 32-lane group (sw_body.h, across_rows): wave_shr:1 over
+// the whole wavefront, and restricted to the first bank of the odd rows as the column loop has it
+#define DPP8(ctrl)                                                                                                       \
+    "v_mov_b32_dpp %0, %1 " ctrl "\nv_mov_b32_dpp %1, %2 " ctrl "\nv_mov_b32_dpp %2, %3 " ctrl "\nv_mov_b32_dpp %3, %4 " ctrl "\n" \
+    "v_mov_b32_dpp %4, %5 " ctrl "\nv_mov_b32_dpp %5, %6 " ctrl "\nv_mov_b32_dpp %6, %7 " ctrl "\nv_mov_b32_dpp %7, %0 " ctrl
+PROBE(k_mov_dpp_wave, DPP8("wave_shr:1 row_mask:0xf bank_mask:0xf"))
+PROBE(k_mov_dpp_wave_masked, DPP8("wave_shr:1 row_mask:0xa bank_mask:0x1"))
 PROBE(k_pk_fma_f16, "v_pk_fma_f16 %0, %0, %8, %8\nv_pk_fma_f16 %1, %1, %8, %8\nv_pk_fma_f16 %2, %2, %8, %8\nv_pk_fma_f16 %3, %3, %8, %8\n"
                     "v_pk_fma_f16 %4, %4, %8, %8\nv_pk_fma_f16 %5, %5, %8, %8\nv_pk_fma_f16 %6, %6, %8, %8\nv_pk_fma_f16 %7, %7, %8, %8")
 PROBE(k_pk_add_u16, OP8("v_pk_add_u16", ""))
@@ -82,7 +89,8 @@ int main() {
         {"v_pk_sub_u16 clamp", k_pk_sub_u16}, {"v_pk_add_u16", k_pk_add_u16}, {"v_pk_min_i16", k_pk_min_i16},
         {"v_max_i16", k_max_i16}, {"v_max_i32", k_max_i32}, {"v_add_u32", k_add_u32}, {"v_sub_u32 clamp", k_sub_u32_clamp},
         {"v_and_b32", k_and_b32}, {"v_max3_i32", k_max3_i32}, {"v_add3_u32", k_add3_u32}, {"v_perm_b32", k_perm_b32},
-        {"v_bfi_b32", k_bfi_b32}, {"v_mov_b32_dpp row_shr:1", k_mov_dpp}, {"v_sad_u16", k_sad_u16},
+        {"v_bfi_b32", k_bfi_b32}, {"v_mov_b32_dpp row_shr:1", k_mov_dpp}, {"v_mov_b32_dpp wave_shr:1", k_mov_dpp_wave},
+        {"v_mov_dpp wave_shr:1 0xa/0x1", k_mov_dpp_wave_masked}, {"v_sad_u16", k_sad_u16},
         {"v_fma_f32", k_fma_f32}, {"v_pk_fma_f16", k_pk_fma_f16},
         {"v_pk_add_f16", k_pk_add_f16, 0x42004200u}, {"v_pk_add_f16 neg_lo neg_hi", k_pk_add_f16_neg, 0x42004200u},
         {"v_pk_max_f16", k_pk_max_f16, 0x42004200u}, {"v_pk_maximum3_f16", k_pk_maximum3_f16, 0x42004200u},

@@ -15,6 +15,12 @@ the rarely taken `nm != vmax` branch (running maximum, snapshot / row search) is
     python scripts/sw_isa_audit.py --asm FILE.s    # audit an assembly file made earlier
     python scripts/sw_isa_audit.py -D MMGPU_SW_WAVES_G1B=3
     python scripts/sw_isa_audit.py --src sw_half_kernel.hip --pk-per-row 7.5 -o profiles/sw_half_isa_audit.txt
+    python scripts/sw_isa_audit.py --wide [--src ...]   # the bodies of 32-lane groups instead of the 16-lane ones
+
+The wide bodies (a group of 32 lanes, sw_body.h) follow each `row_shr:1` move with a `wave_shr:1` move that carries the value
+across the DPP row boundary: a loop that holds three of those is a wide body.  They sit in the same kernels under the same
+R as the 16-lane bodies, so an audit lists one kind or the other: the 16-lane bodies by default (the committed audits and
+the tests that compare against them), the wide ones with --wide.
 
 --src names another file of mmseqs2_amd/csrc that instantiates sw_body (sw_half_kernel.hip: the f16 forward scan).  Its f16
 loops - the ones that hold v_pk_maximum3_f16 - are listed as dir=half, and the tool's own check on them is
@@ -212,10 +218,13 @@ def audit(asm_path):
             path, skipped, closed = walk_column(lines, labels, i)
             if not closed or sum("row_shr:1" in p for p in path) != 3:
                 continue
+            wide = sum("wave_shr:1" in p for p in path)
+            if wide not in (0, 3):
+                continue
             c, pairs = audit_loop(path)
             R = c["perm"]
             direction = "rev" if c["select"] >= R and R > 0 else ("half" if c["max3_f16"] else "fwd")
-            loops.append(dict(kernel=name, label=lab, dir=direction, R=R,
+            loops.append(dict(kernel=name, label=lab, dir=direction, R=R, wide=wide == 3,
                               counts=c, pairs=pairs, skipped=skipped))
     return kernels, loops
 
@@ -223,8 +232,11 @@ def audit(asm_path):
 FIELDS = ["instr", "valu", "pk", "perm", "ds_read", "s_nop", "v_mov", "s_waitcnt", "lgkm_wait_within2"]
 
 
-def report(kernels, loops, out, src="sw_kernel.hip", pk_per_row=9.0):
+def report(kernels, loops, out, src="sw_kernel.hip", pk_per_row=9.0, wide=False):
     w = out.write
+    loops = [lp for lp in loops if lp["wide"] == wide]
+    if wide:
+        w("# The bodies of 32-lane groups (three wave_shr:1 moves per column beside the three row_shr:1).\n")
     w("# SW column loop audit (scripts/sw_isa_audit.py): gfx950 assembly of mmseqs2_amd/csrc/%s, Makefile flags\n" % src)
     w("# Per loop: one column's straight path.  Skipped: the block under s_and_saveexec / s_cbranch_execz of the rare\n")
     w("# `nm != vmax` branch (its instruction count is given as skipped=).  R is the v_perm_b32 count of the loop.\n")
@@ -270,7 +282,7 @@ def parse_records(text):
     return kernels, loops
 
 
-def run(defines=(), asm=None, src="sw_kernel.hip", pk_per_row=9.0):
+def run(defines=(), asm=None, src="sw_kernel.hip", pk_per_row=9.0, wide=False):
     """Audit text of the tree (or of an assembly file made earlier)."""
     import io
     if asm is None:
@@ -281,7 +293,7 @@ def run(defines=(), asm=None, src="sw_kernel.hip", pk_per_row=9.0):
     else:
         kernels, loops = audit(asm)
     buf = io.StringIO()
-    bad = report(kernels, loops, buf, src, pk_per_row)
+    bad = report(kernels, loops, buf, src, pk_per_row, wide)
     return buf.getvalue(), bad
 
 
@@ -292,8 +304,9 @@ def main():
     ap.add_argument("-o", dest="out", help="write the audit here instead of stdout")
     ap.add_argument("--src", default="sw_kernel.hip", help="file of mmseqs2_amd/csrc to audit (default sw_kernel.hip)")
     ap.add_argument("--pk-per-row", type=float, default=9.0, help="v_pk_* per row the f16 loops may hold (dir=half); default 9")
+    ap.add_argument("--wide", action="store_true", help="list the bodies of 32-lane groups instead of the 16-lane ones")
     a = ap.parse_args()
-    text, bad = run(a.defines, a.asm, a.src, a.pk_per_row)
+    text, bad = run(a.defines, a.asm, a.src, a.pk_per_row, a.wide)
     if a.out:
         open(a.out, "w").write(text)
     else:
