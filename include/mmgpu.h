@@ -901,6 +901,68 @@ typedef struct {
 int mmgpu_host_rescore_accept(const mmgpu_rescore_hit *rec, uint32_t qlen, uint32_t tlen, int is_identity, double evalue,
                               const mmgpu_rescore_accept_params *params, mmgpu_rescore_verdict *out);
 
+/* ---- linclust's k-mer matching stage (`mmseqs kmermatcher --linclust-version 1`, src/linclust/kmermatcher.cpp) -------------------
+ * Over the resident protein database (alphabet 21), in four steps:
+ *   extract  per sequence: residues through `reduce`, every window of k residues without the reduced X, k-mer index
+ *            sum r[i] * (alph_size - 1)^i, score = low 16 bits of XXH64(index, seed hash_shift); the
+ *            min((size_t)(kmers_per_seq - 1 + kmers_per_seq_scale * L), windows) lowest-scoring windows are selected by
+ *            fillKmerPositionArray's own loop (:287-323, with its handling of a last bin that holds more than needed), plus one
+ *            record XXH64(Util::hash(reduced sequence)) at position 0 for the sequence as a whole
+ *   sort     by (k-mer, length descending, id, position)
+ *   group    the first record of a k-mer is the representative; every record of a group of two or more emits
+ *            (representative, member, representative's position - member's) when Util::canBeCovered(cov_thr, cov_mode) holds - or,
+ *            with include_only_extendable, when the diagonal is negative or above the length difference
+ *   vote     per (representative, member): score = number of emitted records, diagonal = the value with the most records, the
+ *            largest on a tie; the member equal to its representative is dropped
+ * The result is a CSR over all sequences in id order: list i is {i, 0, 0}, followed - if i represents anything - by its members in
+ * id order as {member, score, diagonal as the uint16 of a short}: the lines `kmermatcher` writes.
+ * The parameters carry no defaults: the caller passes what setKmerLengthAndAlphabet (:2043-2071) would have chosen, and the reduction
+ * table of its ReducedMatrix (the identity for alph_size 21).
+ * MMGPU_ERR_STATE: no targets loaded; a batch used after the targets were reloaded; fetch before run.  MMGPU_ERR_UNSUPPORTED: a
+ * nucleotide or profile database, a context that holds a shard, a sequence of 32 767 residues or more, (alph_size - 1)^k >= 2^63,
+ * cov_mode outside 0 .. 5, 2^31 records or more.  MMGPU_ERR_ARG: NULL arguments, k outside 1 .. 32, alph_size outside 3 .. 21,
+ * kmers_per_seq < 1, a negative scale, a reduce entry >= alph_size.  MMGPU_ERR_HIP (out of memory) before any kernel runs when the
+ * records, bounded as computeKmerCount (:1100-1108) bounds them, do not fit in free device memory.
+ * run synchronises three times (the record, pair and kept-run counts size the next step) and ends synchronised. */
+typedef struct {
+    int k;                          /* par.kmerSize */
+    int alph_size;                  /* par.alphabetSize (with X) */
+    uint8_t reduce[21];             /* full numeric residue -> reduced numeric residue; reduce[20] == alph_size - 1 */
+    int kmers_per_seq;              /* par.kmersPerSequence */
+    float kmers_per_seq_scale;      /* par.kmersPerSequenceScale (amino acids) */
+    int hash_shift;                 /* par.hashShift: the XXH64 seed */
+    float cov_thr;                  /* -c */
+    int cov_mode;                   /* --cov-mode */
+    int include_only_extendable;    /* --include-only-extendable */
+} mmgpu_kmermatch_params;
+typedef struct {
+    uint64_t n_seqs;      /* lists of the result */
+    uint64_t n_entries;   /* entries of the result: n_seqs + (representative, member) pairs kept */
+    uint64_t n_records;   /* records extracted */
+    uint64_t n_pairs;     /* records emitted by the grouping */
+} mmgpu_kmermatch_counts;
+typedef struct mmgpu_kmermatch_batch_t mmgpu_kmermatch_batch_t;
+
+int mmgpu_kmermatch_prepare(mmgpu_ctx *ctx, const mmgpu_kmermatch_params *params, mmgpu_kmermatch_batch_t **batch);
+int mmgpu_kmermatch_run(mmgpu_ctx *ctx, mmgpu_kmermatch_batch_t *batch);
+/* two steps: counts (offsets == records == NULL), then offsets[n_seqs + 1] and records[n_entries] into caller-owned arrays; either
+ * pointer group may be NULL.  Synchronises. */
+int mmgpu_kmermatch_fetch(mmgpu_ctx *ctx, mmgpu_kmermatch_batch_t *batch, mmgpu_kmermatch_counts *counts, uint64_t *offsets, mmgpu_pf_hit *records);
+/* the same two arrays copied device to device on the context's stream */
+int mmgpu_kmermatch_fetch_device(mmgpu_ctx *ctx, mmgpu_kmermatch_batch_t *batch, void *d_offsets, void *d_records);
+/* ms[6] of the last run: the whole run, then extract, sort 1, group, sort 2, vote */
+int mmgpu_kmermatch_last_kernel_ms(mmgpu_ctx *ctx, mmgpu_kmermatch_batch_t *batch, float *ms);
+void mmgpu_kmermatch_free(mmgpu_ctx *ctx, mmgpu_kmermatch_batch_t *batch);
+
+/* The hand-over to the ungapped rescoring: a rescore batch whose queries are the resident sequences themselves and whose hit list is
+ * the result of a k-mer matching batch that has been run - query = the list's sequence, (target, diagonal) = every entry of the list,
+ * the {i, 0, 0} entry included, the diagonal as the uint16 the result line would have carried.  hit_query and the pairs are written
+ * on the device; no host list exists.  The records of the batch are in the order of mmgpu_kmermatch_fetch's records.  Nothing is
+ * dropped by coverage here (rescorediagonal.cpp:219-221 does, before it scores): the caller drops those records.
+ * Errors as mmgpu_rescore_prepare and as a fetch of the k-mer matching batch. */
+int mmgpu_kmermatch_rescore_prepare(mmgpu_ctx *ctx, const mmgpu_rescore_params *params, mmgpu_kmermatch_batch_t *kmermatch,
+                                         mmgpu_rescore_batch_t **batch);
+
 #ifdef __cplusplus
 }
 #endif

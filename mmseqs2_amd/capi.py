@@ -94,6 +94,8 @@ EXPORTED_SYMBOLS = [
     "mmgpu_gscan_batch", "mmgpu_gscan_debug_scores", "mmgpu_gscan_stage_ms",
     "mmgpu_rescore_prepare", "mmgpu_rescore_run", "mmgpu_rescore_fetch", "mmgpu_rescore_fetch_device", "mmgpu_rescore_last_kernel_ms",
     "mmgpu_rescore_free", "mmgpu_rescore_batch", "mmgpu_host_rescore_accept",
+    "mmgpu_kmermatch_prepare", "mmgpu_kmermatch_run", "mmgpu_kmermatch_fetch", "mmgpu_kmermatch_fetch_device", "mmgpu_kmermatch_last_kernel_ms",
+    "mmgpu_kmermatch_free", "mmgpu_kmermatch_rescore_prepare",
 ]
 
 
@@ -171,6 +173,18 @@ class RescoreVerdict(ctypes.Structure):      # mmgpu_rescore_verdict
                 ("t_cov", ctypes.c_float), ("q_start", ctypes.c_int32), ("q_end", ctypes.c_int32), ("t_start", ctypes.c_int32),
                 ("t_end", ctypes.c_int32)]
 
+
+class KmermatchParams(ctypes.Structure):      # mmgpu_kmermatch_params
+    _fields_ = [("k", ctypes.c_int), ("alph_size", ctypes.c_int), ("reduce", ctypes.c_uint8 * 21), ("kmers_per_seq", ctypes.c_int),
+                ("kmers_per_seq_scale", ctypes.c_float), ("hash_shift", ctypes.c_int), ("cov_thr", ctypes.c_float), ("cov_mode", ctypes.c_int),
+                ("include_only_extendable", ctypes.c_int)]
+
+
+class KmermatchCounts(ctypes.Structure):      # mmgpu_kmermatch_counts
+    _fields_ = [("n_seqs", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("n_records", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64)]
+
+
+KMERMATCH_STAGES = ("extract", "sort1", "group", "sort2", "vote")      # mmgpu_kmermatch_last_kernel_ms: ms[0] the whole run, ms[1 + i] stage i
 
 RESCORE_HAMMING, RESCORE_SUBSTITUTION, RESCORE_ALIGNMENT = 0, 1, 2      # mmgpu_rescore_params::mode
 RESCORE_PAIR_DTYPE = np.dtype([("target", np.uint32), ("diagonal", np.uint16), ("reserved", np.uint16)])      # mmgpu_rescore_pair
@@ -314,6 +328,14 @@ def load_library():
     L.mmgpu_rescore_free.argtypes = [c_p, c_p]
     L.mmgpu_rescore_free.restype = None
     L.mmgpu_rescore_batch.argtypes = [c_p, ctypes.POINTER(RescoreParams), c_p, ctypes.c_uint32, c_p, c_p, c_p]
+    L.mmgpu_kmermatch_prepare.argtypes = [c_p, ctypes.POINTER(KmermatchParams), ctypes.POINTER(c_p)]
+    L.mmgpu_kmermatch_run.argtypes = [c_p, c_p]
+    L.mmgpu_kmermatch_fetch.argtypes = [c_p, c_p, ctypes.POINTER(KmermatchCounts), c_p, c_p]
+    L.mmgpu_kmermatch_fetch_device.argtypes = [c_p, c_p, c_p, c_p]
+    L.mmgpu_kmermatch_last_kernel_ms.argtypes = [c_p, c_p, ctypes.POINTER(ctypes.c_float)]
+    L.mmgpu_kmermatch_free.argtypes = [c_p, c_p]
+    L.mmgpu_kmermatch_free.restype = None
+    L.mmgpu_kmermatch_rescore_prepare.argtypes = [c_p, ctypes.POINTER(RescoreParams), c_p, ctypes.POINTER(c_p)]
     L.mmgpu_host_rescore_accept.argtypes = [c_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_double,
                                             ctypes.POINTER(RescoreAcceptParams), ctypes.POINTER(RescoreVerdict)]
     return L
@@ -645,6 +667,60 @@ class RescoreBatch:
     def free(self):
         if self.handle is not None:
             self.gpu.L.mmgpu_rescore_free(self.gpu.ctx, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class KmermatchBatch:
+    """A prepared k-mer matching stage of linclust (mmgpu_kmermatch_*) over the resident database."""
+
+    def __init__(self, gpu, handle):
+        self.gpu, self.handle = gpu, handle
+
+    def run(self):
+        self.gpu._check(self.gpu.L.mmgpu_kmermatch_run(self.gpu.ctx, self.handle))
+
+    def counts(self):
+        """-> dict n_seqs, n_entries (of the result), n_records (extracted), n_pairs (emitted by the grouping)"""
+        c = KmermatchCounts()
+        self.gpu._check(self.gpu.L.mmgpu_kmermatch_fetch(self.gpu.ctx, self.handle, ctypes.byref(c), None, None))
+        return {k: int(getattr(c, k)) for k, _ in KmermatchCounts._fields_}
+
+    def fetch(self):
+        """-> (offsets uint64[n + 1], records PF_HIT_DTYPE[offsets[n]]): per sequence {id, 0, 0}, then its members in id order"""
+        c = self.counts()
+        off = np.zeros(c["n_seqs"] + 1, np.uint64)
+        rec = np.zeros(max(c["n_entries"], 1), PF_HIT_DTYPE)
+        self.gpu._check(self.gpu.L.mmgpu_kmermatch_fetch(self.gpu.ctx, self.handle, None, _ptr(off), _ptr(rec)))
+        return off, rec[:c["n_entries"]]
+
+    def fetch_device(self, d_offsets_ptr, d_records_ptr):
+        """D2D copy of the CSR into caller-owned device memory (raw pointers), on the context's stream"""
+        self.gpu._check(self.gpu.L.mmgpu_kmermatch_fetch_device(self.gpu.ctx, self.handle, c_p(d_offsets_ptr), c_p(d_records_ptr)))
+
+    def stage_ms(self):
+        """-> (ms of the whole last run, dict stage -> ms)"""
+        ms = (ctypes.c_float * (1 + len(KMERMATCH_STAGES)))()
+        self.gpu._check(self.gpu.L.mmgpu_kmermatch_last_kernel_ms(self.gpu.ctx, self.handle, ms))
+        return ms[0], {name: ms[1 + i] for i, name in enumerate(KMERMATCH_STAGES)}
+
+    def rescore_prepare(self, mat, mode):
+        """mmgpu_kmermatch_rescore_prepare: every entry of the result as a hit of its list's sequence, written on the device ->
+        RescoreBatch (records in the order of fetch()'s records)"""
+        mat = np.ascontiguousarray(mat, np.int8)
+        par = RescoreParams(_ptr(mat), mat.shape[0], int(mode))
+        h = c_p()
+        self.gpu._check(self.gpu.L.mmgpu_kmermatch_rescore_prepare(self.gpu.ctx, ctypes.byref(par), self.handle, ctypes.byref(h)))
+        return RescoreBatch(self.gpu, h, [mat], self.counts()["n_entries"])
+
+    def free(self):
+        if self.handle is not None:
+            self.gpu.L.mmgpu_kmermatch_free(self.gpu.ctx, self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1251,6 +1327,21 @@ class MMGpu:
         del keep
         return out[:int(off[-1])]
 
+    def kmermatch_prepare(self, params):
+        """mmgpu_kmermatch_prepare: params = KmermatchParams, or a dict of its fields (`reduce`: 21 numbers) -> KmermatchBatch"""
+        h = c_p()
+        self._check(self.L.mmgpu_kmermatch_prepare(self.ctx, ctypes.byref(kmermatch_params(params)), ctypes.byref(h)))
+        return KmermatchBatch(self, h)
+
+    def kmermatch(self, params):
+        """linclust's k-mer matching stage (`kmermatcher --linclust-version 1`) over the resident database -> (offsets, records)"""
+        b = self.kmermatch_prepare(params)
+        try:
+            b.run()
+            return b.fetch()
+        finally:
+            b.free()
+
     def pf_set_shard(self, n_shards, shard, global_db_size, global_ids, shard_of, local_id):
         """this context holds shard `shard` of a database of global_db_size targets (None-like: pf_clear_shard)"""
         g = np.ascontiguousarray(global_ids, np.uint32)
@@ -1363,6 +1454,62 @@ def host_rescore_accept(rec, qlen, tlen, is_identity, evalue_of_score, mode, seq
     if L.mmgpu_host_rescore_accept(_ptr(r), int(qlen), int(tlen), int(bool(is_identity)), float(evalue_of_score), ctypes.byref(par), ctypes.byref(v)) != 0:
         raise MMGpuError(L.mmgpu_last_error().decode())
     return {k: getattr(v, k) for k, _ in RescoreVerdict._fields_}
+
+
+def kmermatch_params(p):
+    """a dict of mmgpu_kmermatch_params' fields -> KmermatchParams (a KmermatchParams passes through)"""
+    if isinstance(p, KmermatchParams):
+        return p
+    red = [int(x) for x in p["reduce"]]
+    if len(red) != 21:
+        raise ValueError("reduce must hold 21 numbers")
+    return KmermatchParams(int(p["k"]), int(p["alph_size"]), (ctypes.c_uint8 * 21)(*red), int(p["kmers_per_seq"]), float(p["kmers_per_seq_scale"]),
+                           int(p["hash_shift"]), float(p["cov_thr"]), int(p["cov_mode"]), int(bool(p["include_only_extendable"])))
+
+
+def kmermatch_defaults(min_seq_id, n_residues):
+    """setKmerLengthAndAlphabet (kmermatcher.cpp:2043-2071) for an amino-acid database of n_residues residues when neither -k nor
+    --alph-size is given -> (k, alphabet size).  seqIdThr is a float widened for the comparison; the logarithm of the float
+    database size is divided by the double log(8.7)"""
+    thr = float(np.float32(min_seq_id)) + 0.001
+    if thr >= 0.99:
+        return 14, 21
+    if thr >= 0.9:
+        return 14, 13
+    return max(10, int(float(np.log(np.float32(n_residues))) / float(np.log(8.7)))), 13
+
+
+def linclust_prefilter(gpu, mat, params, rescore_mode, e=0.001, min_seq_id=0.0, seq_id_mode=0, cov=0.0, cov_mode=0, min_aln_len=0,
+                       filter_hits=False, score_per_col_thr=0.0, sort_results=False, backtrace=False, evalue_par=None):
+    """linclust's `kmermatcher` and the `rescorediagonal` behind it over the resident database, without a host list in between:
+    params = the k-mer matching parameters (with their `reduce` table), the rest as rescore_diagonal names it.  Every entry of
+    the k-mer matching result is rescored on the device; the records are fetched once, and the host drops what canBeCovered would
+    have dropped before the scoring and applies the acceptance rule.  -> (offsets, records of the k-mer matching,
+    per sequence what rescorediagonal would write)"""
+    mode = rescore_effective_mode(rescore_mode, filter_hits)
+    km = gpu.kmermatch_prepare(params)
+    try:
+        km.run()
+        rb = km.rescore_prepare(mat, mode)
+        try:
+            rb.run()
+            rec = rb.fetch()
+        finally:
+            rb.free()
+        off, hits = km.fetch()
+    finally:
+        km.free()
+    tl = gpu._target_lens
+    kept, keep_rec = [], []
+    for q in range(len(off) - 1):
+        a, b = int(off[q]), int(off[q + 1])
+        ok = _can_be_covered(cov, int(cov_mode), int(tl[q]), tl[hits["id"][a:b].astype(np.int64)])
+        kept.append(np.stack([hits["id"][a:b].astype(np.int64), hits["diagonal"][a:b].astype(np.int64)], axis=1)[ok])
+        keep_rec.append(rec[a:b][ok])
+    rec = np.concatenate(keep_rec) if keep_rec else rec[:0]
+    lines = rescore_lists(rec, [int(x) for x in tl], kept, tl, int(tl.sum()), mode, e, min_seq_id, seq_id_mode, cov, cov_mode, min_aln_len,
+                          filter_hits, score_per_col_thr, sort_results, backtrace, list(range(len(tl))), evalue_par, gpu.L)
+    return off, hits, lines
 
 
 def rescore_effective_mode(mode, filter_hits):

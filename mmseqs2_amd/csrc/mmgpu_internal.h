@@ -370,6 +370,51 @@ hipError_t launch_rescore(const RescoreArgs &A, int mode, hipStream_t stream);
 void warm_rescore();
 
 // ---------------------------------------------------------------------------------------------------------
+// linclust's k-mer matching stage (kmermatch_api.hip, kmermatch_kernel.hip).  A record of the extraction is a k-mer and a packed
+// value (0x7FFF - length) << 47 | id << 15 | position (15, 32 and 15 bits): the reference's first sort order (k-mer, length
+// descending, id, position) is (k-mer, value) ascending, and the records leave the extraction in (id, position) order.  The length
+// field ends below bit 63 on purpose: rocprim's merge path builds its mask as (1 << end_bit) - 1, which for end_bit 64 and a begin_bit
+// above 0 shifts by the key's width and then compares the wrong bits.
+constexpr uint32_t KMM_LEN_MASK = 0x7FFFu;
+constexpr unsigned KMM_ID_SHIFT = 15, KMM_LEN_SHIFT = 47, KMM_LEN_END = 62;
+constexpr int KMM_MAX_K = 32;                 // the staging of a round of windows holds 64 + KMM_MAX_K residues
+constexpr uint32_t KMM_MAX_LEN = 32766;       // the reference switches its records to int at 32 767 residues; lengths and positions are 15 bits here
+constexpr int KMM_STAGES = 5;                 // extract, sort 1, group, sort 2, vote
+
+struct KmmExtractArgs {
+    const uint8_t *res;                // the resident database
+    const uint32_t *off4, *len;
+    uint32_t n;
+    int k, alph_size;
+    uint8_t reduce[21];
+    int kmers_per_seq;
+    float kmers_per_seq_scale;
+    unsigned long long seed;           // (uint64_t) par.hashShift
+    uint4 *rule;                       // [n] {threshold score t, surplus of its bin, kmerConsidered, -}
+    uint32_t *count;                   // [n] records of the sequence, the identity record included
+    const uint32_t *rec_off;           // [n + 1] exclusive sum of count
+    unsigned long long *rec_kmer, *rec_val;
+};
+struct KmmGroupArgs {
+    const unsigned long long *kmer, *val;      // the sorted records
+    uint32_t n_records;
+    uint32_t *group_start;                     // [n_records] index of the record's representative
+    float cov_thr;
+    int cov_mode, only_extendable;
+};
+hipError_t launch_kmm_extract_count(const KmmExtractArgs &A, hipStream_t s);
+hipError_t launch_kmm_record_offsets(const uint32_t *count, uint32_t n, uint32_t *tile_sum, uint32_t *rec_off, hipStream_t s);
+hipError_t launch_kmm_extract_write(const KmmExtractArgs &A, hipStream_t s);
+hipError_t launch_kmm_group_scan(const KmmGroupArgs &A, uint32_t *tile_sum, uint32_t *emit_at, hipStream_t s);
+hipError_t launch_kmm_emit(const KmmGroupArgs &A, const uint32_t *emit_at, unsigned long long *pair, uint16_t *diag, hipStream_t s);
+hipError_t launch_kmm_vote_scan(const unsigned long long *pair, uint32_t n_pairs, uint32_t *tile_sum, uint32_t *kept_at, hipStream_t s);
+hipError_t launch_kmm_vote(const unsigned long long *pair, const uint16_t *diag, uint32_t n_pairs, const uint32_t *kept_at, uint32_t n_kept, uint32_t n,
+                           uint32_t *kept_rep, unsigned long long *offsets, mmgpu_pf_hit *records, hipStream_t s);
+hipError_t launch_kmm_handover(const unsigned long long *offsets, uint32_t n, const mmgpu_pf_hit *records, uint32_t n_entries, uint32_t *hit_query,
+                               mmgpu_rescore_pair *pairs, hipStream_t s);
+inline uint32_t kmm_scan_tiles(uint64_t n) { return (uint32_t)((n + 2047) / 2048); }      // tile sums a scan of n elements needs
+
+// ---------------------------------------------------------------------------------------------------------
 // prefilter (pf_kernels.hip)
 constexpr int PF_T = 4096;             // arrival-ordered index entries per tile (2048: 22 % slower, more tiles)
 constexpr int PF_IDS_PER_BIN = 4096;   // targets per replay bin (one 16 KB LDS state table per wavefront)
@@ -1223,4 +1268,20 @@ int scan_debug_scores(const char *who, const char *kind, mmgpu_ctx *c, ScanBatch
                       size_t score_size, uint32_t query, void *out, size_t cap);
 void scan_sync_for_free(mmgpu_ctx *c);      // before a batch is deleted: nothing of it is in flight
 }
+
+// a k-mer matching batch (kmermatch_api.hip); rescore_api.hip reads its result for the hand-over
+struct mmgpu_kmermatch_batch_t {
+    mmgpu_kmermatch_params par{};
+    uint32_t n = 0;                           // sequences
+    uint64_t bound = 0;                       // records at most (computeKmerCount)
+    const uint8_t *db_res = nullptr;          // the resident database the batch was prepared against (a reload invalidates the batch)
+    bool ran = false;
+    uint64_t n_records = 0, n_pairs = 0, n_kept = 0;
+    mmgpu::DevBuf d_offsets, d_records;       // the result: uint64[n + 1], mmgpu_pf_hit[n + n_kept]
+    hipEvent_t ev[mmgpu::KMM_STAGES + 1] = {};      // around the stages of the last run
+    ~mmgpu_kmermatch_batch_t() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
 #endif

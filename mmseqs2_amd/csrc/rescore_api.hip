@@ -18,6 +18,7 @@ struct mmgpu_rescore_batch_t {
     int mode = 0, alphabet = 0;
     const uint8_t *db_res = nullptr;      // the resident database the batch was prepared against (a reload invalidates the batch)
     bool ran = false;
+    bool db_queries = false;              // mmgpu_kmermatch_rescore_prepare: the queries are the resident sequences themselves
     DevBuf d_qres, d_qoff4, d_qlen, d_mat, d_hit_query, d_pairs, d_out;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;      // around the last run
     ~mmgpu_rescore_batch_t() {
@@ -184,14 +185,54 @@ extern "C" int mmgpu_rescore_prepare(mmgpu_ctx *c, const mmgpu_rescore_params *p
     return rescore_prepare_impl(c, par, qs, nq, hit_off, pairs, out);
 }
 
+// the hit list of a k-mer matching batch, handed over on the device: hit_query and the pairs are cut from its CSR by a kernel
+extern "C" int mmgpu_kmermatch_rescore_prepare(mmgpu_ctx *c, const mmgpu_rescore_params *par, mmgpu_kmermatch_batch_t *km, mmgpu_rescore_batch_t **out) {
+    const char *who = "mmgpu_kmermatch_rescore_prepare";
+    if (out) *out = nullptr;
+    if (!c || !out || !km || !par || !par->mat) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
+    if (!c->db.res || c->db.n == 0) return fail(MMGPU_ERR_STATE, std::string(who) + ": no targets loaded");
+    if (c->shard.on) return fail(MMGPU_ERR_UNSUPPORTED, std::string(who) + ": the context holds a shard of a multi-GPU run");
+    if (par->alphabet != 21 || c->db.alphabet != 21)
+        return fail(MMGPU_ERR_UNSUPPORTED, std::string(who) + ": protein sequences only (alphabet 21, parameters and resident targets alike)");
+    if (par->mode == 3 || par->mode == 4)
+        return fail(MMGPU_ERR_UNSUPPORTED, std::string(who) + ": --rescore-mode 3 and 4 trim a leading or trailing '*', which numeric residues cannot tell from X");
+    if (par->mode < 0 || par->mode > 4) return fail(MMGPU_ERR_ARG, std::string(who) + ": unknown mode");
+    if (km->db_res != c->db.res || km->n != c->db.n) return fail(MMGPU_ERR_STATE, std::string(who) + ": the targets were reloaded since the k-mer matching batch was prepared");
+    if (!km->ran) return fail(MMGPU_ERR_STATE, std::string(who) + ": the k-mer matching batch has not been run");
+    const uint64_t total = (uint64_t)km->n + km->n_kept;
+    if (total >= (1ull << 31)) return fail(MMGPU_ERR_UNSUPPORTED, std::string(who) + ": 2^31 hits or more");
+    HIP_TRY(hipSetDevice(c->device));
+    std::unique_ptr<mmgpu_rescore_batch_t> b(new mmgpu_rescore_batch_t());
+    b->nq = c->db.n;
+    b->n_hits = (uint32_t)total;
+    b->n_targets = c->db.n;
+    b->mode = par->mode;
+    b->alphabet = par->alphabet;
+    b->db_res = c->db.res;
+    b->db_queries = true;
+    for (DevBuf *d : {&b->d_mat, &b->d_hit_query, &b->d_pairs, &b->d_out}) d->bind(c->cache);
+    const std::vector<int8_t> mat(par->mat, par->mat + (size_t)par->alphabet * par->alphabet);
+    HIP_TRY(upload(b->d_mat, mat, c->stream));
+    HIP_TRY(b->d_hit_query.alloc((size_t)b->n_hits * sizeof(uint32_t)));
+    HIP_TRY(b->d_pairs.alloc((size_t)b->n_hits * sizeof(mmgpu_rescore_pair)));
+    HIP_TRY(b->d_out.alloc((size_t)b->n_hits * sizeof(mmgpu_rescore_hit)));
+    HIP_TRY(launch_kmm_handover(km->d_offsets.as<unsigned long long>(), km->n, km->d_records.as<mmgpu_pf_hit>(), b->n_hits, b->d_hit_query.as<uint32_t>(),
+                                b->d_pairs.as<mmgpu_rescore_pair>(), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));      // the host copy of the matrix goes with this call
+    HIP_TRY(hipEventCreate(&b->ev0));
+    HIP_TRY(hipEventCreate(&b->ev1));
+    *out = b.release();
+    return MMGPU_OK;
+}
+
 extern "C" int mmgpu_rescore_run(mmgpu_ctx *c, mmgpu_rescore_batch_t *b) {
     const int rc = rescore_check_batch("mmgpu_rescore_run", c, b, false);
     if (rc != MMGPU_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     RescoreArgs A;
-    A.q_res = b->d_qres.as<uint8_t>();
-    A.q_off4 = b->d_qoff4.as<uint32_t>();
-    A.q_len = b->d_qlen.as<uint32_t>();
+    A.q_res = b->db_queries ? c->db.res : b->d_qres.as<uint8_t>();      // (the database's tail slack exceeds RESCORE_SLACK)
+    A.q_off4 = b->db_queries ? c->db.off4 : b->d_qoff4.as<uint32_t>();
+    A.q_len = b->db_queries ? c->db.len : b->d_qlen.as<uint32_t>();
     A.t_res = c->db.res;
     A.t_off4 = c->db.off4;
     A.t_len = c->db.len;

@@ -244,6 +244,26 @@ int mmgpu_rescore_last_kernel_ms(mmgpu_ctx *, mmgpu_rescore_batch_t *, float *ms
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_last_kernel_ms: not served through mmgpu_server");
 }
 void mmgpu_rescore_free(mmgpu_ctx *, mmgpu_rescore_batch_t *) {}
+// linclust's k-mer matching stage and its hand-over to the rescoring: the binary runs kmermatcher on the host, nothing of it crosses the socket
+int mmgpu_kmermatch_prepare(mmgpu_ctx *, const mmgpu_kmermatch_params *, mmgpu_kmermatch_batch_t **batch) {
+    if (batch) *batch = nullptr;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_kmermatch_prepare: not served through mmgpu_server (the binary runs kmermatcher on the host)");
+}
+int mmgpu_kmermatch_run(mmgpu_ctx *, mmgpu_kmermatch_batch_t *) { return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_kmermatch_run: not served through mmgpu_server"); }
+int mmgpu_kmermatch_fetch(mmgpu_ctx *, mmgpu_kmermatch_batch_t *, mmgpu_kmermatch_counts *, uint64_t *, mmgpu_pf_hit *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_kmermatch_fetch: not served through mmgpu_server");
+}
+int mmgpu_kmermatch_fetch_device(mmgpu_ctx *, mmgpu_kmermatch_batch_t *, void *, void *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_kmermatch_fetch_device: not served through mmgpu_server");
+}
+int mmgpu_kmermatch_last_kernel_ms(mmgpu_ctx *, mmgpu_kmermatch_batch_t *, float *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_kmermatch_last_kernel_ms: not served through mmgpu_server");
+}
+void mmgpu_kmermatch_free(mmgpu_ctx *, mmgpu_kmermatch_batch_t *) {}
+int mmgpu_kmermatch_rescore_prepare(mmgpu_ctx *, const mmgpu_rescore_params *, mmgpu_kmermatch_batch_t *, mmgpu_rescore_batch_t **batch) {
+    if (batch) *batch = nullptr;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_kmermatch_rescore_prepare: not served through mmgpu_server");
+}
 int mmgpu_rescore_batch(mmgpu_ctx *, const mmgpu_rescore_params *, const mmgpu_rescore_query *, uint32_t, const uint64_t *, const mmgpu_rescore_pair *,
                         mmgpu_rescore_hit *) {
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_batch: not served through mmgpu_server (the binary runs rescorediagonal on the host)");
