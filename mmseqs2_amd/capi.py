@@ -1139,11 +1139,13 @@ class MMGpu:
         return True
 
     def pf_mask_targets(self, likelihood_ratios, min_mask_prob=0.9, mask_letter=20):
-        """mmgpu_pf_mask_targets: tantan masking of the resident targets for the prefilter -> residues masked"""
-        lr = np.ascontiguousarray(likelihood_ratios, np.float64)
+        """mmgpu_pf_mask_targets: tantan masking of the resident targets for the prefilter -> residues masked.
+        likelihood_ratios None: back to the unmasked view (the C call's NULL table) -> 0"""
+        lr = None if likelihood_ratios is None else np.ascontiguousarray(likelihood_ratios, np.float64)
         n = ctypes.c_uint64()
         self.L.mmgpu_pf_mask_targets.argtypes = [c_p, c_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-        self._check(self.L.mmgpu_pf_mask_targets(self.ctx, _ptr(lr), lr.shape[0], float(min_mask_prob), int(mask_letter), ctypes.byref(n)))
+        self._check(self.L.mmgpu_pf_mask_targets(self.ctx, _ptr(lr), 0 if lr is None else lr.shape[0], float(min_mask_prob), int(mask_letter),
+                                                 ctypes.byref(n)))
         return n.value
 
     def pf_debug_masked_targets(self, offsets):
@@ -1791,11 +1793,13 @@ class MMGpuMulti:
         self.n_targets = len(offsets) - 1
 
     def pf_mask_targets(self, likelihood_ratios, min_mask_prob=0.9, mask_letter=20):
-        """mmgpu_multi_pf_mask_targets: tantan masking of every shard -> residues masked over all shards"""
-        lr = np.ascontiguousarray(likelihood_ratios, np.float64)
+        """mmgpu_multi_pf_mask_targets: tantan masking of every shard -> residues masked over all shards.
+        likelihood_ratios None: every shard back to its unmasked view -> 0"""
+        lr = None if likelihood_ratios is None else np.ascontiguousarray(likelihood_ratios, np.float64)
         n = ctypes.c_uint64()
         self.L.mmgpu_multi_pf_mask_targets.argtypes = [c_p, c_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-        self._check(self.L.mmgpu_multi_pf_mask_targets(self.h, _ptr(lr), lr.shape[0], float(min_mask_prob), int(mask_letter), ctypes.byref(n)))
+        self._check(self.L.mmgpu_multi_pf_mask_targets(self.h, _ptr(lr), 0 if lr is None else lr.shape[0], float(min_mask_prob), int(mask_letter),
+                                                       ctypes.byref(n)))
         return n.value
 
     def pf_build_index(self, k, alphabet, spaced, score3, index3, kmer_submat16, kmer_thr, ungapped_mat):

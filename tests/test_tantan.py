@@ -6,7 +6,16 @@ of every operation, and the reference's AVX2 build is compiled with -mfma, so gc
   * oracle/tantan_oracle.c (plain C, fused operations written out) == the reference's compiled tantan, probabilities bit for
     bit and masks byte for byte: against vectors recorded from oracle/_ref/libmmref.so (tests/golden/make_tantan_golden.py) and,
     where that library and /root/reference/data are present, against the library itself on fresh sequences;
-  * the device == the recorded vectors and == the restatement on a larger set (gpu tests);
+  * the same at the edges (tests/test_tantan_edges.py, vectors tests/golden/tantan_edge_vectors.npz recorded by
+    tests/golden/make_tantan_edge_golden.py from the sets of tests/tantan_cases.py): every length 0 .. 70, one planted repeat per
+    period 1 .. 52, X inside and as a repeat, the likelihood ratios of VTML80 and of BLOSUM62, masks at 0.9f and 0.5f; and the longest
+    admitted sequence (65 535 letters) against the library itself;
+  * the device == the recorded vectors and == the restatement on a larger set (gpu tests below: the default threshold and table,
+    periods 1 .. 11, lengths >= 30 but for three);
+  * the device's probabilities themselves, float for float, and the device at those edges (tests/test_tantan_gpu.py): every
+    probability of a 388-letter probe set through two masks per value (at the value and at the next float above it), the edge
+    vectors, thresholds 0 .. 1.5, wavefronts of 1 / 63 / 64 / 65 / 129 sequences and of lanes of very different lengths, 65 535
+    letters, one wavefront per chunk, alphabet 5 and other mask letters, masking twice, unmasking, the refused arguments;
   * `mmseqs prefilter` with default masking through the patched binary == stock (tests/test_mmseqs_dropin.py)."""
 import os
 
