@@ -162,10 +162,16 @@ constexpr int SW_MIN_WAVES = MMGPU_SW_MIN_WAVES;   // occupancy floor (waves per
 #ifndef MMGPU_SW_GROUPS
 #define MMGPU_SW_GROUPS 4
 #endif
-// kernels per pass: tile shapes grouped by register need (sw_kernel.hip): R <= 12, R <= 24, single tiles of R >= 26, and - always
-// the last group - the queries cut into several tiles (3: the last two in one kernel, rounds 1-2)
+// kernels per pass: tile shapes grouped by register need (sw_kernel.hip): single tiles of up to SW_GROUP0_MAX_R rows per lane, of up
+// to SW_GROUP1_MAX_R, the larger ones, and - always the last group - the queries cut into several tiles (3: the last two in one
+// kernel, rounds 1-2).  A wide body has the registers of the 16-lane single-tile body of its R, and its group.
 constexpr int SW_GROUPS = MMGPU_SW_GROUPS;
 static_assert(SW_GROUPS == 3 || SW_GROUPS == 4, "three or four kernel groups");
+constexpr int SW_GROUP0_MAX_R = 12;
+constexpr int SW_GROUP1_MAX_R = 24;
+__host__ __device__ constexpr int sw_group_of(bool multi, int R) {
+    return multi ? SW_GROUPS - 1 : (R <= SW_GROUP0_MAX_R ? 0 : (R <= SW_GROUP1_MAX_R ? 1 : 2));
+}
 int sw_shape_group(uint32_t shape);
 hipError_t launch_sw(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream);
 // Build knob for A/B measurements: MMGPU_SW_HALF=0 keeps every batch on the int16 kernels of sw_kernel.hip.  1 (default): the

@@ -149,14 +149,180 @@ __device__ __forceinline__ bool sw_rev_wanted(const SwLaunch &L, uint32_t slot, 
 
 constexpr int SW_REV_JOB_HITS = 1024;   // most hits a reverse-scan job may hold (mmgpu_internal.h: SW_REV_JOB_MAX)
 static_assert(SW_REV_JOB_HITS == SW_REV_JOB_MAX, "host and kernel disagree on the reverse job size");
-static_assert(SW_LDS_HEADER == SW_REV_JOB_HITS * 2 + 64, "the header holds the live hits and the scheduling words");
-constexpr int SW_HALF_FLAG_AT = SW_REV_JOB_HITS * 2 + 20;   // byte offset in the header of the f16 pass's "some pair is marked" word
+// dynamic LDS of an alignment workgroup: a 1 KB header (job-local scheduling state) followed by the query profiles of the tiles held
+struct SwLds {
+    uint16_t live[SW_REV_JOB_HITS];   // packed live hits (reverse pass, MARKED)
+    uint32_t live_wave[WAVES];
+    uint32_t next_chunk;              // next 8-hit chunk to hand to a wave
+    uint32_t half_flag;               // HALF: some pair of the job is marked
+    uint32_t unused[10];
+    __device__ unsigned char *profiles() { return reinterpret_cast<unsigned char *>(this + 1); }   // (as many bytes as the launch asked for)
+};
+constexpr int SW_HALF_FLAG_AT = offsetof(SwLds, half_flag);   // byte offset in the header of the f16 pass's "some pair is marked" word
+static_assert(SW_LDS_HEADER == SW_REV_JOB_HITS * 2 + 64 && sizeof(SwLds) == SW_LDS_HEADER && SW_HALF_FLAG_AT == SW_REV_JOB_HITS * 2 + 20 &&
+              offsetof(SwLds, next_chunk) == SW_REV_JOB_HITS * 2 + 16, "the header holds the live hits and the scheduling words");
 // (every `extern __shared__` array of a kernel is the one dynamic LDS block: this is sw_body's header)
-__device__ __forceinline__ uint32_t sw_half_any_marked() {
+__device__ __forceinline__ SwLds &sw_lds() {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-    return *reinterpret_cast<const uint32_t *>(lds_all + SW_HALF_FLAG_AT);
+    return *reinterpret_cast<SwLds *>(lds_all);
+}
+__device__ __forceinline__ uint32_t sw_half_any_marked() { return sw_lds().half_flag; }
+
+// the query of a job
+struct SwQuery {
+    const uint8_t *q;
+    const int8_t *cb;
+    int qlen, qbias;
+    const int8_t *prof;   // profile query: its score rows, else nullptr
+};
+__device__ __forceinline__ SwQuery sw_query(const SwLaunch &L, uint32_t query) {
+    const uint32_t qbeg = L.q_off[query];
+    SwQuery Q;
+    Q.qlen = (int)(L.q_off[query + 1] - qbeg);
+    Q.q = L.q_res + qbeg;
+    Q.cb = L.q_cb + qbeg;
+    Q.qbias = L.q_bias[query];
+    Q.prof = nullptr;
+    if (L.q_prof_off) {
+        const uint32_t po = L.q_prof_off[query];
+        if (po != 0xFFFFFFFFu) Q.prof = L.q_prof + po;
+    }
+    return Q;
 }
 
+// The profiles a job holds, and when which is built.  A single-tile job has the one.  A multi-tile job whose tiles all fit the LDS
+// the host granted by the same rule (sw_multi_resident) keeps every tile's profile: built once, in front of the chunk loop, which
+// then runs without a barrier - its wavefronts take chunks as they finish, like the single-tile bodies.  The other jobs rebuild
+// the one profile they have room for per tile and round.  (workgroup-uniform)
+struct SwProfiles {
+    unsigned char *lds;    // where the profiles start (behind the header)
+    int n_tiles;
+    uint32_t tile_bytes;
+    bool resident;         // MULTI: all tiles held
+    bool dynamic;          // all profiles held: chunks handed out through next_chunk, no barrier in the loop
+};
+template <int R, bool MULTI>
+__device__ __forceinline__ SwProfiles sw_profiles(const SwLaunch &L, int qlen) {
+    SwProfiles P;
+    P.lds = sw_lds().profiles();
+    P.n_tiles = MULTI ? (int)sw_tiles((uint32_t)qlen, R) : 1;
+    P.tile_bytes = sw_profile_bytes(R, L.alphabet);
+    P.resident = MULTI && sw_multi_resident((uint32_t)P.n_tiles, R, L.alphabet, L.resident_lds);
+    P.dynamic = !MULTI || P.resident;
+    return P;
+}
+enum SwBuildAt { SW_AT_JOB_START, SW_AT_PACKED, SW_AT_TILE };
+// The one place profiles are built from.  A job that holds all its profiles builds them once, all threads, a barrier behind them: at
+// the start of the job, or (PACKED: the reverse scan and the re-run of the marked pairs) behind the packing, which may leave nothing
+// to scan.  The other jobs build the profile of `tile` at the top of that tile, between two barriers.
+template <SwBuildAt AT, int R, bool REV, bool HALF, bool PACKED, int W>
+__device__ __forceinline__ void sw_build_profiles(const SwLaunch &L, const SwQuery &Q, const SwProfiles &P, int tile = 0) {
+    using T = Tile<R, W>;
+    if (AT == SW_AT_TILE) {
+        if (!P.dynamic) {
+            __syncthreads();   // everyone is done reading the previous tile's profile
+            build_profile<R, REV, HALF, W>(P.lds, Q.q, Q.cb, Q.qlen, tile * T::ROWS, L.mat, L.alphabet, Q.prof);
+            __syncthreads();
+        }
+    } else if ((AT == SW_AT_PACKED) == PACKED && P.dynamic) {
+        for (int t = 0; t < P.n_tiles; ++t)
+            build_profile<R, REV, HALF, W>(P.lds + (uint32_t)t * P.tile_bytes, Q.q, Q.cb, Q.qlen, t * T::ROWS, L.mat, L.alphabet, Q.prof);
+        __syncthreads();
+    }
+}
+
+// Reverse pass: only the pairs whose forward score reaches the query's start-score threshold are scanned
+// (ssw_align_private, StripedSmithWaterman.cpp:857-863) - typically one hit in six, scattered over the
+// length-sorted list.  They are packed to the front (order kept), so that the waves run full instead of every
+// wave waiting for its one or two live targets.
+// MARKED packs the pairs the f16 pass marked in the same way (their int16 profile replaces the f16 one: the caller's barrier
+// stands between the last read of that and this).
+// Returns how many pairs `live` lists.
+template <bool REV, bool MARKED>
+__device__ __forceinline__ uint32_t sw_pack_live(const SwLaunch &L, const SwJob &job, SwLds &H, uint32_t n_hits) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int min_start = REV ? L.q_minstart[job.query] : 0;
+    uint32_t total = 0;
+    for (uint32_t base = 0; base < n_hits; base += WAVES * 64) {   // a job of the BOTH kernels holds at most 256 hits: one round
+        const uint32_t idx = base + threadIdx.x;
+        bool pass = false;
+        if (idx < n_hits) {
+            const uint32_t slot = L.hit_out[job.hit_begin + idx];
+            pass = MARKED ? L.out[slot].score == SW_HALF_MARK : sw_rev_wanted(L, slot, min_start);
+        }
+        const unsigned long long bal = __ballot(pass);
+        if (lane == 0) H.live_wave[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = 0, round_total = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const uint32_t c = H.live_wave[w];
+            before += w < wave ? c : 0u;
+            round_total += c;
+        }
+        if (pass) H.live[total + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)idx;
+        total += round_total;
+        __syncthreads();
+    }
+    return total;
+}
+
+// Single-tile and resident jobs: a wave takes the next chunk of 8 hits (4 in a wide body) when it is done with its last one (the hits
+// are sorted by length, so fixed wave <-> chunk striping would give wave 0 the longest chunk of every round).
+// The other multi-tile jobs rebuild the profile per tile with all threads, so their waves stay in step.
+// Returns the first slot of the wavefront's chunk in round `it` (wave-uniform).
+template <int W>
+__device__ __forceinline__ uint32_t sw_claim_chunk(SwLds &H, bool dynamic, uint32_t it) {
+    constexpr int HITS_PER_WAVE = 2 * 64 / W;   // (W = 16: the file's constant)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t chunk = it * WAVES + wave;
+    if (dynamic) {
+        if (lane == 0) chunk = atomicAdd(&H.next_chunk, 1u);
+        chunk = __builtin_amdgcn_readfirstlane(chunk);
+    }
+    return chunk * HITS_PER_WAVE;
+}
+
+// ---- write the result of one pair (its group's head lane) ----
+// end, cols: the pair's forward t_end and its columns (REV)
+template <bool REV, bool HALF>
+__device__ __forceinline__ void sw_write_result(const SwLaunch &L, const SwQuery &Q, unsigned long long key, uint32_t h, int end, int cols) {
+    // HALF: the key holds the score's f16 bits (ordered like the value); past the limit the pair is left to the int16 pass
+    const bool marked = HALF && (unsigned)(key >> 32) > (unsigned)h_bits(SW_HALF_LIMIT);
+    const int score = HALF ? (marked ? SW_HALF_MARK : h_value((unsigned)(key >> 32))) : (int)(key >> 32);
+    const int col = 0xFFFF - (int)((key >> 16) & 0xFFFFu);
+    const int row = 0xFFFF - (int)(key & 0xFFFFu);
+    mmgpu_sw_hit *o = L.out + L.hit_out[h];
+    if (!REV) {
+        mmgpu_sw_hit res;
+        res.score = score;
+        res.q_end = score ? row : 0;       // all-zero saved column matches at index 0 (:263-271)
+        res.t_end = score ? col : -1;      // byte pass initialises end_db = -1 (:118)
+        res.q_start = -1;
+        res.t_start = -1;
+        res.word = (score + Q.qbias >= 255) ? 1 : 0;
+        *o = res;
+        if (marked) sw_lds().half_flag = 1;
+    } else {
+        if (cols > 0) {
+            // column index counts backwards from t_end; row is an index into the reversed query
+            // score 0: no strip reached the forward score - "Score of forward/backward SW differ" (:1191-1201)
+            o->t_start = (score == o->score) ? end - col : -2;
+            o->q_start = (score == o->score) ? Q.qlen - 1 - row : -2;
+        }
+    }
+}
+
+// One job: the pairs of its hit list against its query, eight (W = 32: four) per wavefront at a time.  The steps around the scan are
+// the functions above.  Three steps stay inline, under their banners: the pair setup, the tile scan and the fold of a tile.  What the
+// compiler makes of the column loop depends on them standing in one function with it - a function is simplified on its own before it is
+// inlined, and what it settles there stays.  Tried as functions (scripts/sw_isa_audit.py against the inline form): the tile scan
+// with its results by reference turns the selects of the rare `nm != vmax` block into branches; the pair setup changes the row
+// search of the reverse bodies' rare block (rev_target's halves are opaque to the column step) and costs the wide bodies of R = 15, 16
+// a wait state per column; the fold costs the multi-tile reverse body of R = 10 a wait state, and with its inputs as plain values
+// the multi-tile bodies of R = 13, 14 two ds_reads.
 // PF: the profile rows of a column are fetched one column ahead (see the column loop)
 // HALF: the cells are computed in packed f16 (above, at SW_HALF_LIMIT); a pair whose score exceeds SW_HALF_LIMIT gets SW_HALF_MARK
 //   for a result and raises the workgroup's flag in the LDS header.
@@ -170,13 +336,7 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
     constexpr bool PACKED = REV || MARKED;   // the job's pairs to scan are the ones listed in `live`
     constexpr int HITS_PER_WAVE = 2 * 64 / W;   // (W = 16: the file's constant)
     using T = Tile<R, W>;
-    // dynamic LDS: a 1 KB header (job-local scheduling state, below) followed by the query profile of the tile
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-    uint16_t *live = reinterpret_cast<uint16_t *>(lds_all);                  // [SW_REV_JOB_HITS] packed live hits (reverse pass)
-    uint32_t *live_wave = reinterpret_cast<uint32_t *>(lds_all + SW_REV_JOB_HITS * 2);       // [WAVES]
-    uint32_t *next_chunk = reinterpret_cast<uint32_t *>(lds_all + SW_REV_JOB_HITS * 2 + 16); // next 8-hit chunk to hand to a wave
-    uint32_t *half_flag = reinterpret_cast<uint32_t *>(lds_all + SW_HALF_FLAG_AT);           // HALF: some pair of the job is marked
-    unsigned char *lds = lds_all + SW_LDS_HEADER;
+    SwLds &H = sw_lds();
     // A multi-tile job is one long dependent chain (tiles x columns) however few targets it holds, and the batch ends
     // with the longest of them: those waves take the issue slots first, the short jobs sharing the SIMD fill the gaps.
     if (MULTI) __builtin_amdgcn_s_setprio(3);
@@ -184,100 +344,32 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane & (W - 1);
     const int grp = lane / W;
-
-    const uint32_t qbeg = L.q_off[job.query];
-    const int qlen = (int)(L.q_off[job.query + 1] - qbeg);
-    const uint8_t *q = L.q_res + qbeg;
-    const int8_t *cb = L.q_cb + qbeg;
-    const int qbias = L.q_bias[job.query];
-    const int8_t *prof = nullptr;
-    if (L.q_prof_off) {
-        const uint32_t po = L.q_prof_off[job.query];
-        if (po != 0xFFFFFFFFu) prof = L.q_prof + po;
-    }
-    const int n_tiles = MULTI ? (int)sw_tiles((uint32_t)qlen, R) : 1;
-    // A multi-tile job whose tiles all fit the LDS the host granted by the same rule keeps every tile's profile: built once, in
-    // front of the chunk loop, which then runs without a barrier - its wavefronts take chunks as they finish, like the single-tile
-    // bodies.  The other jobs rebuild the one profile they have room for per tile and round.  (workgroup-uniform)
-    const uint32_t tile_bytes = sw_profile_bytes(R, L.alphabet);
-    const bool resident = MULTI && sw_multi_resident((uint32_t)n_tiles, R, L.alphabet, L.resident_lds);
-    const bool dynamic = !MULTI || resident;   // chunks handed out through next_chunk, no barrier in the loop
-    auto build_all_tiles = [&]() {
-        for (int tile = 0; tile < n_tiles; ++tile)
-            build_profile<R, REV>(lds + (uint32_t)tile * tile_bytes, q, cb, qlen, tile * T::ROWS, L.mat, L.alphabet, prof);
-        __syncthreads();
-    };
-
+    const SwQuery Q = sw_query(L, job.query);
+    const SwProfiles prof = sw_profiles<R, MULTI>(L, Q.qlen);
     const unsigned go2 = (HALF ? (unsigned)h_bits(L.gap_open) : (unsigned)L.gap_open) * 0x10001u;
     const unsigned ge2 = (HALF ? (unsigned)h_bits(L.gap_extend) : (unsigned)L.gap_extend) * 0x10001u;
     const unsigned pad_letter = (unsigned)L.alphabet;
 
-    if (threadIdx.x == 0) *next_chunk = 0;
-    if (HALF && threadIdx.x == 0) *half_flag = 0;
-    if (!MULTI && !PACKED) {
-        build_profile<R, REV, HALF, W>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
-        __syncthreads();
-    }
-    if (MULTI && !REV && resident) build_all_tiles();
-
+    if (threadIdx.x == 0) H.next_chunk = 0;
+    if (HALF && threadIdx.x == 0) H.half_flag = 0;
+    sw_build_profiles<SW_AT_JOB_START, R, REV, HALF, PACKED, W>(L, Q, prof);
     uint32_t n_hits = job.hit_end - job.hit_begin;
-    // Reverse pass: only the pairs whose forward score reaches the query's start-score threshold are scanned
-    // (ssw_align_private, StripedSmithWaterman.cpp:857-863) - typically one hit in six, scattered over the
-    // length-sorted list.  They are packed to the front (order kept), so that the waves run full instead of every
-    // wave waiting for its one or two live targets.
-    // MARKED packs the pairs the f16 pass marked in the same way (their int16 profile replaces the f16 one: the caller's barrier
-    // stands between the last read of that and this).
     if (PACKED) {
-        const int min_start = REV ? L.q_minstart[job.query] : 0;
-        uint32_t total = 0;
-        for (uint32_t base = 0; base < n_hits; base += WAVES * 64) {   // a job of the BOTH kernels holds at most 256 hits: one round
-            const uint32_t idx = base + threadIdx.x;
-            bool pass = false;
-            if (idx < n_hits) {
-                const uint32_t slot = L.hit_out[job.hit_begin + idx];
-                pass = MARKED ? L.out[slot].score == SW_HALF_MARK : sw_rev_wanted(L, slot, min_start);
-            }
-            const unsigned long long bal = __ballot(pass);
-            if (lane == 0) live_wave[wave] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            uint32_t before = 0, round_total = 0;
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) {
-                const uint32_t c = live_wave[w];
-                before += w < wave ? c : 0u;
-                round_total += c;
-            }
-            if (pass) live[total + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)idx;
-            total += round_total;
-            __syncthreads();
-        }
-        n_hits = total;
+        n_hits = sw_pack_live<REV, MARKED>(L, job, H, n_hits);
         if (n_hits == 0) return;      // (workgroup-uniform) no pair of this job needs a start position: no profile either
-        if (!MULTI) {
-            build_profile<R, REV, false, W>(lds, q, cb, qlen, 0, L.mat, L.alphabet, prof);
-            __syncthreads();
-        }
-        if (MULTI && resident) build_all_tiles();
     }
+    sw_build_profiles<SW_AT_PACKED, R, REV, HALF, PACKED, W>(L, Q, prof);
     const uint32_t n_iter = (n_hits + WAVES * HITS_PER_WAVE - 1) / (WAVES * HITS_PER_WAVE);
 
-    for (uint32_t it = 0; dynamic || it < n_iter; ++it) {
-        // Single-tile and resident jobs: a wave takes the next chunk of 8 hits (4 in a wide body) when it is done with its last one (the hits
-        // are sorted by length, so fixed wave <-> chunk striping would give wave 0 the longest chunk of every round).
-        // The other multi-tile jobs rebuild the profile per tile with all threads, so their waves stay in step.
-        uint32_t chunk = it * WAVES + wave;
-        if (dynamic) {
-            if (lane == 0) chunk = atomicAdd(next_chunk, 1u);
-            chunk = __builtin_amdgcn_readfirstlane(chunk);
-        }
-        const uint32_t slot0 = chunk * HITS_PER_WAVE;
-        if (dynamic && slot0 >= n_hits) break;   // wave-uniform; the jobs in step keep every wave in the barrier loop
+    for (uint32_t it = 0; prof.dynamic || it < n_iter; ++it) {
+        const uint32_t slot0 = sw_claim_chunk<W>(H, prof.dynamic, it);
+        if (prof.dynamic && slot0 >= n_hits) break;   // wave-uniform; the jobs in step keep every wave in the barrier loop
 
         // ---- the two targets of this group ------------------------------------------------------
         const uint32_t sA = slot0 + grp * 2, sB = sA + 1;
         const bool vA = sA < n_hits, vB = sB < n_hits;
-        const uint32_t hA = job.hit_begin + (PACKED ? (uint32_t)live[vA ? sA : 0] : sA);
-        const uint32_t hB = job.hit_begin + (PACKED ? (uint32_t)live[vB ? sB : 0] : sB);
+        const uint32_t hA = job.hit_begin + (PACKED ? (uint32_t)H.live[vA ? sA : 0] : sA);
+        const uint32_t hB = job.hit_begin + (PACKED ? (uint32_t)H.live[vB ? sB : 0] : sB);
         const uint32_t tA = vA ? L.hit_target[hA] : 0u, tB = vB ? L.hit_target[hB] : 0u;
         const uint8_t *pA = L.t_res + (size_t)L.t_off4[tA] * 4;
         const uint8_t *pB = L.t_res + (size_t)L.t_off4[tB] * 4;
@@ -299,8 +391,8 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             colsB = vB ? fb.t_end + 1 : 0;
             endA = colsA > 0 ? fa.t_end : 0;
             endB = colsB > 0 ? fb.t_end : 0;
-            r0A = colsA > 0 ? qlen - 1 - fa.q_end : 0;
-            r0B = colsB > 0 ? qlen - 1 - fb.q_end : 0;
+            r0A = colsA > 0 ? Q.qlen - 1 - fa.q_end : 0;
+            r0B = colsB > 0 ? Q.qlen - 1 - fb.q_end : 0;
             // the score the reverse scan has to reach (terminate = r.score1, :1159-1175); 0xFFFF can never be reached
             rev_target = (colsA > 0 ? (unsigned)fa.score & 0xFFFFu : 0xFFFFu) | ((colsB > 0 ? (unsigned)fb.score & 0xFFFFu : 0xFFFFu) << 16);
         }
@@ -326,23 +418,20 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
             scr_grp = (unsigned)grp * 2u * L.scratch_cols;
         }
 
-        for (int tile = 0; tile < n_tiles; ++tile) {
+        // ---- tile scan: one tile of the query against the two targets of every group, column by column ----
+        for (int tile = 0; tile < prof.n_tiles; ++tile) {
             const int tile_base = tile * T::ROWS;
-            if (MULTI && !resident) {
-                __syncthreads();   // everyone is done reading the previous tile's profile
-                build_profile<R, REV>(lds, q, cb, qlen, tile_base, L.mat, L.alphabet, prof);
-                __syncthreads();
-            }
+            sw_build_profiles<SW_AT_TILE, R, REV, HALF, PACKED, W>(L, Q, prof, tile);
             // the profile of this tile: the one there is, or this tile's of the resident ones (no barrier: nobody writes them).
             // Without the barriers nothing but program order stands between tile t's stores to its scratch line (lane 15 of a
             // group) and tile t + 1's loads from it (the group's head lane): the hand-over of the boundary row relies on both
             // being lanes of ONE wavefront, whose vector memory operations on the same addresses complete in order.  A group
             // spread over two wavefronts would need a fence and a barrier here again.
-            const unsigned char *const lds_tile = MULTI && resident ? lds + (uint32_t)tile * tile_bytes : lds;
+            const unsigned char *const lds_tile = MULTI && prof.resident ? prof.lds + (uint32_t)tile * prof.tile_bytes : prof.lds;
             const uint2 *scr_in = MULTI ? scr + (size_t)((tile + 1) & 1) * L.scratch_cols : nullptr;
             uint2 *scr_out = MULTI ? scr + (size_t)(tile & 1) * L.scratch_cols : nullptr;
             const bool has_above = MULTI && tile > 0;
-            const bool has_below = MULTI && tile + 1 < n_tiles;
+            const bool has_below = MULTI && tile + 1 < prof.n_tiles;
 
             // forward: snap[] = the strip's H values in the column where the running maximum last rose (q_end);
             // reverse: rmask[] = rows of the reversed query that lie inside q[0..q_end] - the reverse scan needs no
@@ -649,39 +738,8 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
 
         // ---- write results -----------------------------------------------------------------------
         if (g == 0) {
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const bool valid = half ? vB : vA;
-                if (!valid) continue;
-                const unsigned long long key = half ? bestB : bestA;
-                const uint32_t h = half ? hB : hA;
-                // HALF: the key holds the score's f16 bits (ordered like the value); past the limit the pair is left to the int16 pass
-                const bool marked = HALF && (unsigned)(key >> 32) > (unsigned)h_bits(SW_HALF_LIMIT);
-                const int score = HALF ? (marked ? SW_HALF_MARK : h_value((unsigned)(key >> 32))) : (int)(key >> 32);
-                const int col = 0xFFFF - (int)((key >> 16) & 0xFFFFu);
-                const int row = 0xFFFF - (int)(key & 0xFFFFu);
-                mmgpu_sw_hit *o = L.out + L.hit_out[h];
-                if (!REV) {
-                    mmgpu_sw_hit res;
-                    res.score = score;
-                    res.q_end = score ? row : 0;       // all-zero saved column matches at index 0 (:263-271)
-                    res.t_end = score ? col : -1;      // byte pass initialises end_db = -1 (:118)
-                    res.q_start = -1;
-                    res.t_start = -1;
-                    res.word = (score + qbias >= 255) ? 1 : 0;
-                    *o = res;
-                    if (marked) *half_flag = 1;
-                } else {
-                    const int end = half ? endB : endA;
-                    const int cols = half ? colsB : colsA;
-                    if (cols > 0) {
-                        // column index counts backwards from t_end; row is an index into the reversed query
-                        // score 0: no strip reached the forward score - "Score of forward/backward SW differ" (:1191-1201)
-                        o->t_start = (score == o->score) ? end - col : -2;
-                        o->q_start = (score == o->score) ? qlen - 1 - row : -2;
-                    }
-                }
-            }
+            if (vA) sw_write_result<REV, HALF>(L, Q, bestA, hA, endA, colsA);
+            if (vB) sw_write_result<REV, HALF>(L, Q, bestB, hB, endB, colsB);
         }
     }
 }
@@ -691,25 +749,25 @@ __device__ __forceinline__ void sw_body(const SwLaunch &L, const SwJob job) {
 // with grids from 50 to 3000 workgroups on side streams) left the chip underfilled - the runtime maps streams onto
 // four hardware queues, and the long multi-tile jobs of the few long queries ran nearly alone at the end.  Shapes
 // are grouped by register need instead (a kernel gets the registers of its largest body, which sets the occupancy of
-// all of them): S = R <= 12 (forward 80 / reverse 119 VGPRs), M = R 14..24 (140 / 212), L = R >= 26 and every
-// multi-tile shape (212 / 256).  Each group is one grid, longest job first; the three run concurrently.
+// all of them): S (forward 80 / reverse 119 VGPRs), M (140 / 212), L and every multi-tile shape (212 / 256) - sw_group_of,
+// mmgpu_internal.h, has the bounds.  Each group is one grid, longest job first; the three run concurrently.
 // BOTH = false: forward scan only (MMGPU_SW_SCORE_END).  BOTH = true: the workgroup runs the reverse scan of its own
 // pairs right after their forward scan - no grid-wide barrier between the passes, so the batch has one tail, not two.
 // W = 32: the wide single-tile bodies (queries of 16 * SW_MAX_R + 1 .. 32 * SW_MAX_R residues); only the R such a query can have exist.
+// the prefetch goes where it costs no wavefront and no wait states: not into the forward-only kernel of the largest single tiles,
+// R = 25 .. 28 (183 registers, two wavefronts instead of three) and not into the multi-tile bodies (with it the compiler puts a
+// wait state into every row of phase 2 again, profiles/sw_isa_audit.txt)
+template <int R, bool MULTI, bool BOTH>
+constexpr bool SW_PREFETCHES = MMGPU_SW_PREFETCH && !MULTI && (BOTH || sw_group_of(false, R) < 2);
 template <int R, bool MULTI, bool BOTH, int W = GROUP>
 __device__ __forceinline__ void sw_passes(const SwLaunch &L, const SwJob &job) {
-    if constexpr (R <= SW_MAX_R && (W == GROUP || R >= SW_WIDE_MIN_R)) {
-        // the prefetch goes where it costs no wavefront and no wait states: not into the forward-only kernel of R = 25 .. 28
-        // (183 registers, two wavefronts instead of three) and not into the multi-tile bodies (with it the compiler puts a
-        // wait state into every row of phase 2 again, profiles/sw_isa_audit.txt)
-        constexpr bool PF = MMGPU_SW_PREFETCH && !MULTI && (BOTH || R <= 24);
-        if (!(BOTH && L.rev_only)) sw_body<R, MULTI, false, PF, false, false, W>(L, job);
-        // multi-tile queries get their reverse scan from sw_rev_multi_kernel (below), per query instead of per job
-        if constexpr (BOTH && !MULTI) {
-            __threadfence_block();   // the forward results of this job, written by other waves of the workgroup
-            __syncthreads();
-            sw_body<R, MULTI, true, PF, false, false, W>(L, job);
-        }
+    constexpr bool PF = SW_PREFETCHES<R, MULTI, BOTH>;
+    if (!(BOTH && L.rev_only)) sw_body<R, MULTI, false, PF, false, false, W>(L, job);
+    // multi-tile queries get their reverse scan from sw_rev_multi_kernel (sw_kernel.hip), per query instead of per job
+    if constexpr (BOTH && !MULTI) {
+        __threadfence_block();   // the forward results of this job, written by other waves of the workgroup
+        __syncthreads();
+        sw_body<R, MULTI, true, PF, false, false, W>(L, job);
     }
 }
 
@@ -728,6 +786,78 @@ __device__ __forceinline__ void sw_passes(const SwLaunch &L, const SwJob &job) {
 #ifndef MMGPU_SW_WAVES_G1B
 #define MMGPU_SW_WAVES_G1B 2
 #endif
+// the two arguments of amdgpu_waves_per_eu of sw_kernel<G, BOTH> and its f16 twin sw_half_kernel<G, BOTH>
+constexpr int sw_waves_floor(int G, bool BOTH) {
+    return G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_SW_WAVES_G0F) : (G == 1 ? (BOTH ? MMGPU_SW_WAVES_G1B : MMGPU_SW_WAVES_G1F) : SW_MIN_WAVES);
+}
+// upper bound: the forward + reverse kernel of the middle group is at the edge of a third wavefront per
+// SIMD (168 - 170 registers) and runs slower with it (83.4 against 78.7 ms for the stage, round 6) - pinned.
+// Re-measured with the wait states out of phase 2 and the rows fetched a column ahead (183 registers at
+// two wavefronts): 75.41 ms for the stage at 2, 74.57 ms at 3 (profiles/sw_column_loop_bench.txt) - but at 3
+// the compiler fits 168 registers only with 44 bytes of scratch per lane (spills around, not inside, the
+// column loops).  Kept at 2: no kernel of this file uses scratch (tests/test_sw_isa_audit.py); the 0.8 ms
+// are there for whoever gets this kernel to 168 registers without spilling.
+constexpr int sw_waves_cap(int G, bool BOTH) { return G == 1 && BOTH ? MMGPU_SW_WAVES_G1B : 8; }
+
+// ---- what the kernels do around the bodies: job, scratch slot, shape dispatch ------------------------------------------------
+// fused prefilter -> align hand-over: the list length of the query is only known on the device.  False: nothing left of the job.
+__device__ __forceinline__ bool sw_clip_job(const SwLaunch &L, SwJob &job) {
+    if (L.q_hit_count) {
+        const uint32_t lim = job.query * L.hit_stride + L.q_hit_count[job.query];
+        job.hit_end = job.hit_end < lim ? job.hit_end : lim;
+        if (job.hit_end <= job.hit_begin) return false;
+    }
+    return true;
+}
+
+// multi-tile jobs: claim a slot of the column-scratch pool.  The pool has at least as many slots as workgroups of the claiming
+// kernels can be resident at once, so the search always ends; a slot is only ever read after its owner wrote it (tile t writes
+// what tile t + 1 reads), so stale content is harmless.  The slot rides in the job's shape word above the shape code.
+__device__ __forceinline__ void sw_claim_scratch(const SwLaunch &L, SwJob &job) {
+    __shared__ uint32_t scratch_slot;
+    if (threadIdx.x == 0) {
+        uint32_t s = blockIdx.x % L.scratch_slots;
+        while (atomicCAS(&L.scratch_busy[s], 0u, 1u) != 0u) s = s + 1 == L.scratch_slots ? 0u : s + 1;
+        scratch_slot = s;
+    }
+    __syncthreads();
+    job.shape = (job.shape & 0xFFu) | (scratch_slot << 8);
+}
+__device__ __forceinline__ void sw_release_scratch(const SwLaunch &L, const SwJob &job) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        atomicExch(&L.scratch_busy[job.shape >> 8], 0u);
+    }
+}
+
+// The one list of rows per lane, and the one switch over a job's shape code: f(R, kind) for the shapes of kernel group G, both
+// as compile-time values (std::integral_constant).  A shape exists for R <= SW_MAX_R; multi-tile from R = 8 (a query cut into
+// tiles gets at least ceil(SW_MAX_R / 2) rows per lane: 8 .. 32 covers every SW_MAX_R the header allows), wide from the R of the
+// shortest wide query.  Workgroup-uniform.
+enum SwKind { SW_SINGLE, SW_MULTI, SW_WIDE };
+constexpr bool sw_shape_exists(SwKind kind, int R) {
+    return R <= SW_MAX_R && (kind != SW_MULTI || R >= 8) && (kind != SW_WIDE || R >= SW_WIDE_MIN_R);
+}
+#define MMGPU_SW_EACH_R(X)                                                                                                          \
+    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) \
+    X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
+template <int G, typename F>
+__device__ __forceinline__ void sw_dispatch_shape(uint32_t shape, F f) {
+    static_assert(GROUP == 16 && SW_SHAPE_MULTI == 32 && SW_SHAPE_WIDE == 64, "the shape codes of the dispatch: 16-lane groups, + 32 multi-tile, + 64 wide");
+#define MMGPU_SW_CASE(R, KIND, BASE)                                                                                                \
+    case BASE + (R) - 1:                                                                                                            \
+        if constexpr (sw_shape_exists(KIND, R) && sw_group_of(KIND == SW_MULTI, R) == G)                                            \
+            f(std::integral_constant<int, R>(), std::integral_constant<SwKind, KIND>());                                            \
+        break;
+#define MMGPU_SW_CASES(R) MMGPU_SW_CASE(R, SW_SINGLE, 0) MMGPU_SW_CASE(R, SW_MULTI, SW_SHAPE_MULTI) MMGPU_SW_CASE(R, SW_WIDE, SW_SHAPE_WIDE)
+    switch (shape & 0xFFu) {
+        MMGPU_SW_EACH_R(MMGPU_SW_CASES)
+        default: break;
+    }
+#undef MMGPU_SW_CASES
+#undef MMGPU_SW_CASE
+}
 
 }  // namespace
 

@@ -24,24 +24,22 @@ namespace {
 // column loop of sw_kernel<G, BOTH> in the same grid as the f16 scans of the 16-lane bodies, with no second set of bodies.
 template <int R, bool BOTH, int W = GROUP>
 __device__ __forceinline__ void sw_half_passes(const SwLaunch &L, const SwJob &job) {
-    if constexpr (R <= SW_MAX_R && (W == GROUP || R >= SW_WIDE_MIN_R)) {
-        constexpr bool PF = MMGPU_SW_PREFETCH && (BOTH || R <= 24);   // as sw_passes
-        const bool f16 = W == GROUP || L.half_wide;   // workgroup-uniform
-        if (f16) {
-            sw_body<R, false, false, PF, true, false, W>(L, job);
-        } else {
-            for (uint32_t h = job.hit_begin + threadIdx.x; h < job.hit_end; h += blockDim.x) L.out[L.hit_out[h]].score = SW_HALF_MARK;
-        }
-        // the results and marks of this job, written by other waves of the workgroup; and every wave is done with the f16 profile
+    constexpr bool PF = SW_PREFETCHES<R, false, BOTH>;   // as sw_passes
+    const bool f16 = W == GROUP || L.half_wide;   // workgroup-uniform
+    if (f16) {
+        sw_body<R, false, false, PF, true, false, W>(L, job);
+    } else {
+        for (uint32_t h = job.hit_begin + threadIdx.x; h < job.hit_end; h += blockDim.x) L.out[L.hit_out[h]].score = SW_HALF_MARK;
+    }
+    // the results and marks of this job, written by other waves of the workgroup; and every wave is done with the f16 profile
+    __threadfence_block();
+    __syncthreads();
+    if (!f16 || sw_half_any_marked()) {   // workgroup-uniform
+        sw_body<R, false, false, PF, false, true, W>(L, job);
         __threadfence_block();
         __syncthreads();
-        if (!f16 || sw_half_any_marked()) {   // workgroup-uniform
-            sw_body<R, false, false, PF, false, true, W>(L, job);
-            __threadfence_block();
-            __syncthreads();
-        }
-        if constexpr (BOTH) sw_body<R, false, true, PF, false, false, W>(L, job);
     }
+    if constexpr (BOTH) sw_body<R, false, true, PF, false, false, W>(L, job);
 }
 
 // which forward-only groups have an f16 kernel (the others: launch_sw_half declines, launch_sw stays with int16)
@@ -49,43 +47,13 @@ constexpr bool SW_HALF_FORWARD_ONLY[3] = {false, false, false};
 
 template <int G, bool BOTH>
 __global__ __launch_bounds__(WAVES * 64)
-__attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_SW_WAVES_G0F)
-                                           : (G == 1 ? (BOTH ? MMGPU_SW_WAVES_G1B : MMGPU_SW_WAVES_G1F) : SW_MIN_WAVES),
-                                   G == 1 && BOTH ? MMGPU_SW_WAVES_G1B : 8))) void sw_half_kernel(SwLaunch L) {   // (sw_kernel's floors)
+__attribute__((amdgpu_waves_per_eu(sw_waves_floor(G, BOTH), sw_waves_cap(G, BOTH)))) void sw_half_kernel(SwLaunch L) {   // (sw_kernel's floors)
     SwJob job = L.jobs[blockIdx.x];
-    if (L.q_hit_count) {   // fused prefilter -> align hand-over: the list length of the query is only known on the device
-        const uint32_t lim = job.query * L.hit_stride + L.q_hit_count[job.query];
-        job.hit_end = job.hit_end < lim ? job.hit_end : lim;
-        if (job.hit_end <= job.hit_begin) return;
-    }
-#define MMGPU_SW_SINGLE(R) case (R) - 1: sw_half_passes<R, BOTH>(L, job); break;
-#define MMGPU_SW_WIDE(R) case 64 + (R) - 1: sw_half_passes<R, BOTH, 2 * GROUP>(L, job); break;   // (only the R a wide query can have)
-    if constexpr (G == 0) {
-        switch (job.shape & 0xFFu) {   // workgroup-uniform
-            MMGPU_SW_SINGLE(1) MMGPU_SW_SINGLE(2) MMGPU_SW_SINGLE(3) MMGPU_SW_SINGLE(4) MMGPU_SW_SINGLE(5) MMGPU_SW_SINGLE(6)
-            MMGPU_SW_SINGLE(7) MMGPU_SW_SINGLE(8) MMGPU_SW_SINGLE(9) MMGPU_SW_SINGLE(10) MMGPU_SW_SINGLE(11) MMGPU_SW_SINGLE(12)
-            default: break;
-        }
-    } else if constexpr (G == 1) {
-        switch (job.shape & 0xFFu) {
-            MMGPU_SW_SINGLE(13) MMGPU_SW_SINGLE(14) MMGPU_SW_SINGLE(15) MMGPU_SW_SINGLE(16) MMGPU_SW_SINGLE(17) MMGPU_SW_SINGLE(18)
-            MMGPU_SW_SINGLE(19) MMGPU_SW_SINGLE(20) MMGPU_SW_SINGLE(21) MMGPU_SW_SINGLE(22) MMGPU_SW_SINGLE(23) MMGPU_SW_SINGLE(24)
-            MMGPU_SW_WIDE(8) MMGPU_SW_WIDE(9) MMGPU_SW_WIDE(10) MMGPU_SW_WIDE(11) MMGPU_SW_WIDE(12) MMGPU_SW_WIDE(13) MMGPU_SW_WIDE(14)
-            MMGPU_SW_WIDE(15) MMGPU_SW_WIDE(16) MMGPU_SW_WIDE(17) MMGPU_SW_WIDE(18) MMGPU_SW_WIDE(19) MMGPU_SW_WIDE(20) MMGPU_SW_WIDE(21)
-            MMGPU_SW_WIDE(22) MMGPU_SW_WIDE(23) MMGPU_SW_WIDE(24)
-            default: break;
-        }
-    } else {
-        switch (job.shape & 0xFFu) {
-            MMGPU_SW_SINGLE(25) MMGPU_SW_SINGLE(26) MMGPU_SW_SINGLE(27) MMGPU_SW_SINGLE(28) MMGPU_SW_SINGLE(29) MMGPU_SW_SINGLE(30)
-            MMGPU_SW_SINGLE(31) MMGPU_SW_SINGLE(32)
-            MMGPU_SW_WIDE(25) MMGPU_SW_WIDE(26) MMGPU_SW_WIDE(27) MMGPU_SW_WIDE(28) MMGPU_SW_WIDE(29) MMGPU_SW_WIDE(30) MMGPU_SW_WIDE(31)
-            MMGPU_SW_WIDE(32)
-            default: break;
-        }
-    }
-#undef MMGPU_SW_SINGLE
-#undef MMGPU_SW_WIDE
+    if (!sw_clip_job(L, job)) return;
+    sw_dispatch_shape<G>(job.shape, [&](auto r, auto kind) __attribute__((always_inline)) {
+        if constexpr (decltype(kind)::value != SW_MULTI)
+            sw_half_passes<decltype(r)::value, BOTH, decltype(kind)::value == SW_WIDE ? 2 * GROUP : GROUP>(L, job);
+    });
 }
 
 // the forward-only kernels no launch uses, for the audit that decides SW_HALF_FORWARD_ONLY (scripts/sw_isa_audit.py -D ...)

@@ -10,7 +10,10 @@
 // every score the uint8 pass can represent, and saturating at 32767 exactly like sw_sse2_word), and the
 // `word` flag reports which pass the reference would have ended in (score + bias >= 255, :238-242).
 // The single-tile groups have twins in sw_half_kernel.hip whose forward scan runs in packed f16 first and in int16 only for
-// the pairs that score past 1792 - same results; launch_sw (below) picks.  The body of both is sw_body.h.
+// the pairs that score past 1792 - same results; launch_sw (below) picks.  The body of both is sw_body.h:
+// sw_body runs a job as named steps (sw_query, sw_profiles / sw_build_profiles, sw_pack_live, sw_claim_chunk, then - inline - the
+// pair setup, the tile scan with the column step, and the fold, then sw_write_result); the kernels here add the job prologue
+// (sw_clip_job, sw_claim_scratch / sw_release_scratch) and pick the body with sw_dispatch_shape.
 //
 // How it is mapped to CDNA4 (this is not the striped/lazy-F formulation of the CPU code):
 //  * integer DP => VALU, no MFMA.  All cell arithmetic is packed 2 x int16 (v_pk_add_i16 clamp,
@@ -47,111 +50,30 @@
 //    hand-off crosses the row boundary with one more move per value, v_mov_b32_dpp wave_shr:1 row_mask:0xa bank_mask:0x1 behind the
 //    row_shr:1 (lanes 16 - 19 and 48 - 51 are rewritten: lane 16 gets lane 15's value, the others what they had): 14 instead of 11
 //    instructions beside the rows, still no LDS and no bpermute (profiles/sw_wide_isa_audit.txt).  Shape codes 64 + R - 1, served
-//    by the grids of groups 1 (R <= 24) and 2 by register need; MMGPU_SW_WIDE=0 in the environment restores the two tiles.
+//    by the grids of groups 1 and 2 by register need (sw_group_of, mmgpu_internal.h); MMGPU_SW_WIDE=0 in the environment restores the two tiles.
 //
 // Bytes per cell that ever touch HBM: (tlen + 28) / (qlen * tlen) ~ 0.003 - this kernel
 // is bound by VALU issue, not by HBM.
 #include "mmgpu_internal.h"
 #include "pf_device.h"
-#include "sw_body.h"   // sw_body, build_profile, sw_passes and the helpers: shared with sw_half_kernel.hip
+#include "sw_body.h"   // sw_body and its steps, sw_passes, the job prologue and the shape dispatch: shared with sw_half_kernel.hip
 
 namespace mmgpu {
 
 namespace {
 
-// (a query cut into tiles gets at least ceil(SW_MAX_R / 2) rows per lane: R = 8 .. 32 covers every SW_MAX_R the header allows)
-#define MMGPU_SW_MULTI_ALL                                                                                                          \
-    MMGPU_SW_MULTI(8) MMGPU_SW_MULTI(9) MMGPU_SW_MULTI(10) MMGPU_SW_MULTI(11) MMGPU_SW_MULTI(12) MMGPU_SW_MULTI(13) MMGPU_SW_MULTI(14) \
-    MMGPU_SW_MULTI(15) MMGPU_SW_MULTI(16) MMGPU_SW_MULTI(17) MMGPU_SW_MULTI(18) MMGPU_SW_MULTI(19) MMGPU_SW_MULTI(20) MMGPU_SW_MULTI(21) \
-    MMGPU_SW_MULTI(22) MMGPU_SW_MULTI(23) MMGPU_SW_MULTI(24) MMGPU_SW_MULTI(25) MMGPU_SW_MULTI(26) MMGPU_SW_MULTI(27) MMGPU_SW_MULTI(28) \
-    MMGPU_SW_MULTI(29) MMGPU_SW_MULTI(30) MMGPU_SW_MULTI(31) MMGPU_SW_MULTI(32)
 template <int G, bool BOTH>
 __global__ __launch_bounds__(WAVES * 64)
-__attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_SW_WAVES_G0F)
-                                           : (G == 1 ? (BOTH ? MMGPU_SW_WAVES_G1B : MMGPU_SW_WAVES_G1F) : SW_MIN_WAVES),
-                                   // upper bound: the forward + reverse kernel of the middle group is at the edge of a third wavefront per
-                                   // SIMD (168 - 170 registers) and runs slower with it (83.4 against 78.7 ms for the stage, round 6) - pinned.
-                                   // Re-measured with the wait states out of phase 2 and the rows fetched a column ahead (183 registers at
-                                   // two wavefronts): 75.41 ms for the stage at 2, 74.57 ms at 3 (profiles/sw_column_loop_bench.txt) - but at 3
-                                   // the compiler fits 168 registers only with 44 bytes of scratch per lane (spills around, not inside, the
-                                   // column loops).  Kept at 2: no kernel of this file uses scratch (tests/test_sw_isa_audit.py); the 0.8 ms
-                                   // are there for whoever gets this kernel to 168 registers without spilling.
-                                   G == 1 && BOTH ? MMGPU_SW_WAVES_G1B : 8))) void sw_kernel(SwLaunch L) {
+__attribute__((amdgpu_waves_per_eu(sw_waves_floor(G, BOTH), sw_waves_cap(G, BOTH)))) void sw_kernel(SwLaunch L) {
     SwJob job = L.jobs[blockIdx.x];
-    if (L.q_hit_count) {   // fused prefilter -> align hand-over: the list length of the query is only known on the device
-        const uint32_t lim = job.query * L.hit_stride + L.q_hit_count[job.query];
-        job.hit_end = job.hit_end < lim ? job.hit_end : lim;
-        if (job.hit_end <= job.hit_begin) return;
-    }
-    // multi-tile jobs (group 2 only): claim a slot of the column-scratch pool.  The pool has at least as many slots as
-    // workgroups of this kernel can be resident at once, so the search always ends; a slot is only ever read after its
-    // owner wrote it (tile t writes what tile t + 1 reads), so stale content is harmless.
-    __shared__ uint32_t scratch_slot;
+    if (!sw_clip_job(L, job)) return;
+    // multi-tile jobs (the last group only) run with a slot of the column-scratch pool
     const bool claims = G == SW_GROUPS - 1 && (job.shape & 0xFFu) >= SW_SHAPE_MULTI && (job.shape & 0xFFu) < SW_SHAPE_WIDE;
-    if (claims) {
-        if (threadIdx.x == 0) {
-            uint32_t s = blockIdx.x % L.scratch_slots;
-            while (atomicCAS(&L.scratch_busy[s], 0u, 1u) != 0u) s = s + 1 == L.scratch_slots ? 0u : s + 1;
-            scratch_slot = s;
-        }
-        __syncthreads();
-        job.shape = (job.shape & 0xFFu) | (scratch_slot << 8);
-    }
-#define MMGPU_SW_SINGLE(R) case (R) - 1: sw_passes<R, false, BOTH>(L, job); break;
-#define MMGPU_SW_MULTI(R) case 32 + (R) - 1: sw_passes<R, true, BOTH>(L, job); break;
-#define MMGPU_SW_WIDE(R) case 64 + (R) - 1: sw_passes<R, false, BOTH, 2 * GROUP>(L, job); break;   // (sw_passes: only the R a wide query can have)
-#define MMGPU_SW_WIDE_M MMGPU_SW_WIDE(8) MMGPU_SW_WIDE(9) MMGPU_SW_WIDE(10) MMGPU_SW_WIDE(11) MMGPU_SW_WIDE(12) MMGPU_SW_WIDE(13)                \
-    MMGPU_SW_WIDE(14) MMGPU_SW_WIDE(15) MMGPU_SW_WIDE(16) MMGPU_SW_WIDE(17) MMGPU_SW_WIDE(18) MMGPU_SW_WIDE(19) MMGPU_SW_WIDE(20)               \
-    MMGPU_SW_WIDE(21) MMGPU_SW_WIDE(22) MMGPU_SW_WIDE(23) MMGPU_SW_WIDE(24)
-#define MMGPU_SW_WIDE_L MMGPU_SW_WIDE(25) MMGPU_SW_WIDE(26) MMGPU_SW_WIDE(27) MMGPU_SW_WIDE(28) MMGPU_SW_WIDE(29) MMGPU_SW_WIDE(30)            \
-    MMGPU_SW_WIDE(31) MMGPU_SW_WIDE(32)
-    if constexpr (G == 0) {
-        switch (job.shape & 0xFFu) {   // workgroup-uniform
-            MMGPU_SW_SINGLE(1) MMGPU_SW_SINGLE(2) MMGPU_SW_SINGLE(3) MMGPU_SW_SINGLE(4) MMGPU_SW_SINGLE(5) MMGPU_SW_SINGLE(6)
-            MMGPU_SW_SINGLE(7) MMGPU_SW_SINGLE(8) MMGPU_SW_SINGLE(9) MMGPU_SW_SINGLE(10) MMGPU_SW_SINGLE(11) MMGPU_SW_SINGLE(12)
-            default: break;
-        }
-    } else if constexpr (G == 1) {
-        switch (job.shape & 0xFFu) {
-            MMGPU_SW_SINGLE(13) MMGPU_SW_SINGLE(14) MMGPU_SW_SINGLE(15) MMGPU_SW_SINGLE(16) MMGPU_SW_SINGLE(17) MMGPU_SW_SINGLE(18)
-            MMGPU_SW_SINGLE(19) MMGPU_SW_SINGLE(20) MMGPU_SW_SINGLE(21) MMGPU_SW_SINGLE(22) MMGPU_SW_SINGLE(23) MMGPU_SW_SINGLE(24)
-            MMGPU_SW_WIDE_M
-            default: break;
-        }
-    } else if constexpr (SW_GROUPS == 4 && G == 2) {
-        switch (job.shape & 0xFFu) {
-            MMGPU_SW_SINGLE(25) MMGPU_SW_SINGLE(26) MMGPU_SW_SINGLE(27) MMGPU_SW_SINGLE(28) MMGPU_SW_SINGLE(29) MMGPU_SW_SINGLE(30)
-            MMGPU_SW_SINGLE(31) MMGPU_SW_SINGLE(32)
-            MMGPU_SW_WIDE_L
-            default: break;
-        }
-    } else if constexpr (SW_GROUPS == 4) {
-        switch (job.shape & 0xFFu) {
-            MMGPU_SW_MULTI_ALL
-            default: break;
-        }
-    } else {
-        switch (job.shape & 0xFFu) {
-            MMGPU_SW_SINGLE(25) MMGPU_SW_SINGLE(26) MMGPU_SW_SINGLE(27) MMGPU_SW_SINGLE(28) MMGPU_SW_SINGLE(29) MMGPU_SW_SINGLE(30)
-            MMGPU_SW_SINGLE(31) MMGPU_SW_SINGLE(32)
-            MMGPU_SW_WIDE_L
-            MMGPU_SW_MULTI_ALL
-            default: break;
-        }
-    }
-#undef MMGPU_SW_SINGLE
-#undef MMGPU_SW_MULTI
-#undef MMGPU_SW_MULTI_ALL
-#undef MMGPU_SW_WIDE
-#undef MMGPU_SW_WIDE_M
-#undef MMGPU_SW_WIDE_L
-    if (claims) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __threadfence();
-            atomicExch(&L.scratch_busy[scratch_slot], 0u);
-        }
-    }
+    if (claims) sw_claim_scratch(L, job);
+    sw_dispatch_shape<G>(job.shape, [&](auto r, auto kind) __attribute__((always_inline)) {
+        sw_passes<decltype(r)::value, decltype(kind)::value == SW_MULTI, BOTH, decltype(kind)::value == SW_WIDE ? 2 * GROUP : GROUP>(L, job);
+    });
+    if (claims) sw_release_scratch(L, job);
 }
 
 // Reverse scan of the multi-tile queries.  A forward job of a long query holds few hits (8 or 16 per workgroup for
@@ -162,33 +84,12 @@ __attribute__((amdgpu_waves_per_eu(G == 0 ? (BOTH ? MMGPU_SW_WAVES_G0B : MMGPU_S
 // Launched behind the group-2 kernel on the same stream (it reads that kernel's forward results).
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(SW_MIN_WAVES))) void sw_rev_multi_kernel(SwLaunch L) {
     SwJob job = L.jobs[blockIdx.x];
-    if (L.q_hit_count) {
-        const uint32_t lim = job.query * L.hit_stride + L.q_hit_count[job.query];
-        job.hit_end = job.hit_end < lim ? job.hit_end : lim;
-        if (job.hit_end <= job.hit_begin) return;
-    }
-    __shared__ uint32_t scratch_slot;
-    if (threadIdx.x == 0) {
-        uint32_t s = blockIdx.x % L.scratch_slots;
-        while (atomicCAS(&L.scratch_busy[s], 0u, 1u) != 0u) s = s + 1 == L.scratch_slots ? 0u : s + 1;
-        scratch_slot = s;
-    }
-    __syncthreads();
-    job.shape = (job.shape & 0xFFu) | (scratch_slot << 8);
-#define MMGPU_SW_REV(R) case 32 + (R) - 1: if constexpr ((R) <= SW_MAX_R) sw_body<R, true, true, false>(L, job); break;
-    switch (job.shape & 0xFFu) {
-        MMGPU_SW_REV(8) MMGPU_SW_REV(9) MMGPU_SW_REV(10) MMGPU_SW_REV(11) MMGPU_SW_REV(12) MMGPU_SW_REV(13) MMGPU_SW_REV(14) MMGPU_SW_REV(15)
-        MMGPU_SW_REV(16) MMGPU_SW_REV(17) MMGPU_SW_REV(18) MMGPU_SW_REV(19) MMGPU_SW_REV(20) MMGPU_SW_REV(21) MMGPU_SW_REV(22) MMGPU_SW_REV(23)
-        MMGPU_SW_REV(24) MMGPU_SW_REV(25) MMGPU_SW_REV(26) MMGPU_SW_REV(27) MMGPU_SW_REV(28) MMGPU_SW_REV(29) MMGPU_SW_REV(30) MMGPU_SW_REV(31)
-        MMGPU_SW_REV(32)
-        default: break;
-    }
-#undef MMGPU_SW_REV
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicExch(&L.scratch_busy[scratch_slot], 0u);
-    }
+    if (!sw_clip_job(L, job)) return;
+    sw_claim_scratch(L, job);
+    sw_dispatch_shape<SW_GROUPS - 1>(job.shape, [&](auto r, auto kind) __attribute__((always_inline)) {
+        if constexpr (decltype(kind)::value == SW_MULTI) sw_body<decltype(r)::value, true, true, false>(L, job);
+    });
+    sw_release_scratch(L, job);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -292,12 +193,10 @@ hipError_t launch_sw_rev_multi(const SwLaunch &L, size_t lds_bytes, hipStream_t 
     return hipGetLastError();
 }
 
-// by register need: a wide body has the registers of the 16-lane single-tile body of its R
+// by register need (sw_group_of): the shape code is kind + R - 1
 int sw_shape_group(uint32_t shape) {
-    if (shape >= SW_SHAPE_WIDE) return (int)(shape - SW_SHAPE_WIDE) + 1 <= 24 ? 1 : 2;
-    if (shape >= SW_SHAPE_MULTI) return SW_GROUPS - 1;
-    const int R = (int)shape + 1;
-    return R <= 12 ? 0 : (R <= 24 ? 1 : 2);
+    const uint32_t kind = shape >= SW_SHAPE_WIDE ? SW_SHAPE_WIDE : (shape >= SW_SHAPE_MULTI ? SW_SHAPE_MULTI : 0u);
+    return sw_group_of(kind == SW_SHAPE_MULTI, (int)(shape - kind) + 1);
 }
 
 static bool env_switch(const char *name, bool unset) {
@@ -323,7 +222,6 @@ static bool sw_half_eligible(const SwLaunch &L) {
 }
 
 hipError_t launch_sw(const SwLaunch &L, int group, size_t lds_bytes, bool both_passes, hipStream_t stream) {
-    static_assert(GROUP == 16 && SW_SHAPE_MULTI == 32 && SW_SHAPE_WIDE == 64, "the shape codes of the dispatch: 16-lane groups, + 32 multi-tile, + 64 wide");
     if (L.n_jobs == 0) return hipSuccess;
     if (sw_half_eligible(L) && launch_sw_half(L, group, lds_bytes, both_passes, stream)) return hipGetLastError();
     dim3 grid(L.n_jobs), block(WAVES * 64);
