@@ -15,11 +15,10 @@
 // per-group scratch in HBM and are walked back by lane 0.  Work per alignment ~ (qlen + tlen) x 7 blocks, three
 // passes at most; bounded by the dependent chain over the anti-diagonals (LDS latency), not by HBM or VALU peak -
 // parallelism comes from the alignments (4 per wavefront, pulled from a length-sorted queue).
-#ifndef NUCL_NG
+// The loop over the pairs and the pieces of ksw_extz2_sse are nucl_core.h's (align_pairs<LdsForm>), shared with the default
+// kernel (nucl_wave_kernel.hip); this form is the cross-check behind MMGPU_NUCL_LANES=16.
 #define NUCL_NG 16
 #define NUCL_NS nucl16
-#define NUCL_LAUNCH launch_nucl_align
-#endif
 #define NUCL_HD __device__ __forceinline__
 #define NUCL_LANE() ((int)(threadIdx.x & (unsigned)(NUCL_NG - 1)))
 #define NUCL_SHFL(v, src) __shfl((v), (src), NUCL_NG)
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void nucl_align_kernel(NuclLaunch L) {
 
 }  // namespace
 
-hipError_t NUCL_LAUNCH(const NuclLaunch &L, unsigned blocks, hipStream_t stream) {
+hipError_t launch_nucl_align(const NuclLaunch &L, unsigned blocks, hipStream_t stream) {
     if (L.n_pairs == 0) return hipSuccess;
     hipLaunchKernelGGL(nucl_align_kernel, dim3(blocks), dim3(256), 0, stream, L);
     return hipGetLastError();

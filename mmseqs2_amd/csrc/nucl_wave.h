@@ -1,5 +1,7 @@
 // Nucleotide alignment step, ONE WAVEFRONT PER ALIGNMENT with the DP state in registers (the default GPU kernel;
-// nucl_core.h's 16-lane LDS formulation stays as the cross-check, MMGPU_NUCL_LANES=16).
+// nucl_core.h's 16-lane LDS form stays as the cross-check, MMGPU_NUCL_LANES=16).  This file holds what depends on where the
+// state lives - ksw_extz2_wave, ksw_walk_wave, WaveForm; the loop over the pairs (align_pairs<WaveForm>), the seed and the
+// step of the walk are nucl_core.h's, shared with the LDS form.  ksw_extz2_wave keeps its own text of the ksw pieces: see there.
 //
 // ksw_extz2_sse (lib/ksw2/ksw2_extz2_sse.cpp:44-285) works on anti-diagonals: every cell of anti-diagonal r depends on
 // anti-diagonal r - 1 only (u, v, x, y are updated in place; cell t reads x[t-1], v[t-1] of the previous one), the band
@@ -15,14 +17,14 @@
 //   * sequence letters: 512-byte rings in LDS, refilled 256 letters at a time (the only global reads of the loop);
 //   * the exact band maximum with the reference's tie order: per-lane candidates of both slots, then a butterfly;
 //   * direction bytes go to the wave's scratch in HBM (96 B per anti-diagonal, coalesced); the backtrack reads them back
-//     through a 64-row LDS stage (lane 0 walks in LDS instead of one dependent HBM round trip per step);
-//   * identities are counted by all lanes (letter counts -> prefix -> per-chunk walk).
+//     through a 64-row LDS stage (lane 0 walks in LDS instead of one dependent HBM round trip per step).
 // The anti-diagonals of an alignment are a dependent chain (~150 wave instructions each); parallelism comes from one
 // alignment per wavefront x all wavefronts the chip holds.
 //
-// Included after nucl_core.h with NUCL_NG = 64 (SeqView, Ez, seeds, band_of come from there).  The includer supplies,
-// besides nucl_core.h's macros:  NUCL_ROR1_U32(v)  value of lane - 1 (lane 0: lane 63);  NUCL_READLANE(v, l)  value of
-// the (wave-uniform) lane l;  NUCL_WAVE_MAX_I32(v) / NUCL_WAVE_MIN_U32(v)  reduction over the wave, result in every lane.
+// Included after nucl_core.h with NUCL_NG = 64.  The includer supplies, besides nucl_core.h's macros:
+//   NUCL_ROR1_U32(v)                              value of lane - 1 (lane 0: lane 63)
+//   NUCL_READLANE(v, l)                           value of the (wave-uniform) lane l
+//   NUCL_WAVE_MAX_I32(v) / NUCL_WAVE_MIN_U32(v)   reduction over the wave, result in every lane
 #ifndef MMGPU_NUCL_WAVE_H
 #define MMGPU_NUCL_WAVE_H
 
@@ -33,7 +35,7 @@ using namespace NUCL_NS;
 
 constexpr int RING = 512;          // staged letters per sequence (two halves of 256)
 constexpr int PROWS = 64;          // rows of direction bytes staged for the walk
-constexpr int PROW_BYTES = 96;     // (min(65, n) + 15) / 16 + 1 <= 6 blocks of 16
+constexpr int PROW_BYTES = 96;     // ksw_n_col: (min(65, n) + 15) / 16 + 1 <= 6 blocks of 16
 
 struct WaveLds {
     uint8_t qring[RING], tring[RING];
@@ -50,6 +52,14 @@ NUCL_HD void stage_letters(const SeqView &v, int len, int hi, uint8_t *ring, int
     }
 }
 
+// ksw_extz2_sse with the state in registers.  This function stays spelled out - its own Ez initialisation, band, score blocks,
+// cell (NUCLW_CELL), tie order and z-drop step - although nucl_core.h has each of these as a function (ksw_begin ... ksw_zdrop_step),
+// which the LDS form and both walks use.  The kernel's time is the dependent chain of this loop, and what the compiler makes of it
+// depends on the whole text: written with the shared functions the loops came out 5 instructions shorter (694 / 715 / 725
+// against 699 / 720 / 729, same registers) and the kernel 0.4 - 1.2 ms of 49.5 slower in every one of five sessions of parent and
+// result in rotation; with only the cell, the scores and the z-drop step spelled out again 740 / 755 / 765 and 1 ms slower; this
+// text under the shared pair loop runs at the parent's time (profiles/nucl_steps_bench.txt).  A change to a piece in nucl_core.h is
+// made here too; tests/nucl_emu.cpp runs both forms against the same vectors.
 template <bool WITH_P>
 NUCL_HD void ksw_extz2_wave(const SeqView &qv, int qlen, const SeqView &tv, int tlen, const int8_t *mat, int q, int e, int zdrop,
                                WaveLds &S, uint8_t *p, Ez &ez) {
@@ -263,13 +273,11 @@ NUCL_HD void ksw_extz2_wave(const SeqView &qv, int qlen, const SeqView &tv, int 
     NUCL_SYNC();
 }
 
-// ksw_backtrack (is_rot, no introns) from cell (i0 = target, j0 = query): the wave stages 64 rows of direction bytes in
-// LDS, lane 0 walks through them; one letter per step, last column first, into w[]; returns the number of letters.
+// ksw_backtrack from cell (i0 = target, j0 = query): the wave stages 64 rows of direction bytes in LDS, lane 0 walks
+// through them; one letter per step, last column first, into w[]; returns the number of letters (in every lane).
 NUCL_HD int ksw_walk_wave(const uint8_t *p, int qlen, int tlen, int i0, int j0, char *w, WaveLds &S) {
     const int lane = NUCL_LANE();
-    int n_col_ = qlen < tlen ? qlen : tlen;
-    n_col_ = ((n_col_ < KSW_W + 1 ? n_col_ : KSW_W + 1) + 15) / 16 + 1;
-    const int n_col = n_col_ * 16;
+    const int n_col = ksw_n_col(qlen, tlen);
     int i = i0, j = j0, state = 0, n = 0;
     while (i >= 0 && j >= 0) {      // wave-uniform: i, j are broadcast at the end of every round
         const int r_hi = i + j;                       // rows [r_lo, r_hi] staged
@@ -279,17 +287,7 @@ NUCL_HD int ksw_walk_wave(const uint8_t *p, int qlen, int tlen, int i0, int j0, 
         NUCL_SYNC();
         if (lane == 0) {
             while (i >= 0 && j >= 0 && i + j >= r_lo) {
-                const int r = i + j;
-                int st, en;
-                band_of(r, qlen, tlen, st, en);
-                int force_state = -1;
-                if (i < st) force_state = 2;
-                if (i > en) force_state = 1;
-                const unsigned tmp = force_state < 0 ? S.prow[(r - r_lo) * n_col + (i - st)] : 0u;
-                if (state == 0) state = tmp & 7;
-                else if (!(tmp >> (state + 2) & 1)) state = 0;
-                if (state == 0) state = tmp & 7;
-                if (force_state >= 0) state = force_state;
+                state = ksw_walk_state(S.prow + (i + j - r_lo) * n_col, qlen, tlen, i, j, state);
                 if (state == 0) { w[n++] = 'M'; --i; --j; }
                 else if (state == 1 || state == 3) { w[n++] = 'D'; --i; }
                 else { w[n++] = 'I'; --j; }
@@ -307,121 +305,21 @@ NUCL_HD int ksw_walk_wave(const uint8_t *p, int qlen, int tlen, int i0, int j0, 
     return n;
 }
 
-// One wavefront: pulls pairs from the queue until it is empty.
-NUCL_HD void align_wave(const NuclLaunch &L, WaveLds &S, uint8_t *p, char *w) {
-    const int lane = NUCL_LANE();
-    for (;;) {
-        NUCL_SYNC();     // keeps the lanes together across the back edge (see nucl_core.h, align_group)
-        unsigned pi = NUCL_ATOMIC_ADD_U32(L.next_pair, lane == 0 ? 1u : 0u);
-        pi = (unsigned)NUCL_READLANE((int)pi, 0);
-        if (pi >= L.n_pairs) break;
-        const mmgpu_nucl_pair P = L.pairs[L.order[pi]];
-        const int qlen = (int)(L.q_off[P.query + 1] - L.q_off[P.query]);
-        const int tlen = (int)L.t_len[P.target];
-        SeqView qv, tv;
-        qv.base = L.q_res + L.q_off[P.query];
-        qv.rl = P.reverse ? L.rev_lookup : nullptr;
-        qv.L = qlen; qv.off = 0; qv.past = (P.past_end & 0x80u) ? (int)(P.past_end & 7u) : L.past_end_q; qv.reversed = false;
-        tv.base = L.t_res + (size_t)L.t_off4[P.target] * 4;
-        tv.rl = nullptr;
-        tv.L = tlen; tv.off = 0; tv.past = (P.past_end & 0x80u) ? (int)((P.past_end >> 3) & 7u) : L.past_end_t; tv.reversed = false;
-
-        // ---- ungapped seed (pick_seed); origQueryLen of the reference: half of a wrapped query
-        const bool wrapped = L.wrapped != 0;
-        const int orig = wrapped ? qlen / 2 : qlen;
-        const Seed best = pick_seed(qv, qlen, tv, tlen, (unsigned)P.diagonal, wrapped, L.mat);
-        int qs, qe_, ts, te;
-        if (best.diagonal >= 0) { qs = best.start + (int)best.dist; qe_ = best.end + (int)best.dist; ts = best.start; te = best.end; }
-        else { qs = best.start; qe_ = best.end; ts = best.start + (int)best.dist; te = best.end + (int)best.dist; }
-
-        mmgpu_nucl_hit res;
-        res.bt_off = 0;
-        res.status = MMGPU_NUCL_OK;
-        int n_bt = 0;
-        bool walk_reversed = false;     // w[] holds the letters last column first
-        if (qe_ - qs == orig - 1 && ts == 0 && te == tlen - 1) {
-            // the seed spans both sequences (:130-160)
-            res.score = (int32_t)best.score;
-            res.q_start = qs; res.q_end = qe_; res.t_start = ts; res.t_end = te;
-            for (int i = lane; i < orig; i += NG) w[i] = 'M';
-            n_bt = orig;
-        } else {
-            // left extension, score only, on the (shifted) reversed sequences from the seed's end backwards (:165-181)
-            const int q_start_rev = qlen - qe_ - 1, t_start_rev = tlen - te - 1;
-            SeqView qr = qv, tr = tv;
-            qr.reversed = true; qr.off = q_start_rev;
-            tr.reversed = true; tr.off = t_start_rev;
-            Ez ez, eza;
-            // (wrapped scoring: neither extension runs over more than the original query, :171-174,189-191)
-            const int q_rev_len = wrapped && qlen - q_start_rev > orig ? orig : qlen - q_start_rev;
-            ksw_extz2_wave<false>(qr, q_rev_len, tr, tlen - t_start_rev, L.mat, L.gapo, L.gape, L.zdrop, S, nullptr, ez);
-            const int q_start = qlen - (q_start_rev + ez.max_q) - 1, t_start = tlen - (t_start_rev + ez.max_t) - 1;
-            // right extension with directions from that start (:183-196)
-            SeqView qf = qv, tf = tv;
-            qf.off = q_start;
-            tf.off = t_start;
-            int wq = wrapped && qlen - q_start > orig ? orig : qlen - q_start, wt = tlen - t_start;
-            ksw_extz2_wave<true>(qf, wq, tf, wt, L.mat, L.gapo, L.gape, L.zdrop, S, p, eza);
-            if (ez.max_q > eza.max_q && ez.max_t > eza.max_t) {
-                // the forward pass fell short of the backward pass: the backward pass is redone with directions and
-                // its CIGAR reversed (:201-210)
-                wq = q_rev_len;
-                wt = tlen - t_start_rev;
-                ksw_extz2_wave<true>(qr, wq, tr, wt, L.mat, L.gapo, L.gape, L.zdrop, S, p, eza);
-                walk_reversed = true;
-            }
-            NUCL_SYNC_MEM();   // the direction bytes were written by all lanes
-            if (eza.max_t >= 0 && eza.max_q >= 0) n_bt = ksw_walk_wave(p, wq, wt, eza.max_t, eza.max_q, w, S);
-            NUCL_SYNC_MEM();
-            res.score = eza.max;
-            res.q_start = q_start;
-            res.q_end = q_start + eza.max_q;
-            res.t_start = t_start;
-            res.t_end = t_start + eza.max_t;
-            walk_reversed = !walk_reversed;
-        }
-        NUCL_SYNC_MEM();   // w[] was written by lane 0 (or all lanes), every lane reads it below
-        // ---- output: reserve space, copy the string in alignment order, count identities (:231-258)
-        unsigned long long off = NUCL_ATOMIC_ADD_U64(L.bt_cursor, lane == 0 ? (unsigned long long)n_bt + 1ull : 0ull);
-        off = NUCL_SHFL_U64(off, 0);
-        const bool fits = off + (unsigned long long)n_bt + 1ull <= L.bt_cap;
-        if (fits) {
-            for (int i = lane; i < n_bt; i += NG) L.bt[off + (unsigned long long)i] = walk_reversed ? w[n_bt - 1 - i] : w[i];
-            if (lane == 0) L.bt[off + (unsigned long long)n_bt] = 0;
-        }
-        // identities: every lane takes a contiguous chunk of the alignment; the letters before it say where it starts
-        const int chunk = (n_bt + NG - 1) / NG;
-        const int c0 = lane * chunk < n_bt ? lane * chunk : n_bt, c1 = c0 + chunk < n_bt ? c0 + chunk : n_bt;
-        int dq = 0, dt = 0;
-        for (int i = c0; i < c1; ++i) {
-            const char c = walk_reversed ? w[n_bt - 1 - i] : w[i];
-            dq += c != 'D';
-            dt += c != 'I';
-        }
-        int pq = dq, pt = dt;        // inclusive prefix over the lanes
-        for (int d = 1; d < NG; d <<= 1) {
-            const int oq = NUCL_SHFL(pq, lane - d), ot = NUCL_SHFL(pt, lane - d);
-            if (lane >= d) { pq += oq; pt += ot; }
-        }
-        int qp = res.q_start + pq - dq, tp = res.t_start + pt - dt;
-        unsigned ids = 0;
-        for (int i = c0; i < c1; ++i) {
-            const char c = walk_reversed ? w[n_bt - 1 - i] : w[i];
-            if (c == 'M') { ids += tv.strand(tp) == qv.strand(qp) ? 1u : 0u; ++qp; ++tp; }
-            else if (c == 'I') ++qp;
-            else ++tp;
-        }
-        for (int d = 1; d < NG; d <<= 1) ids += (unsigned)NUCL_SHFL_XOR((int)ids, d);
-        if (lane == 0) {
-            res.ident = ids;
-            res.bt_off = fits ? off : 0ull;
-            res.bt_len = (uint32_t)n_bt;
-            if (!fits) res.status = MMGPU_NUCL_BT_OVERFLOW;
-            L.out[L.order[pi]] = res;
-        }
-        NUCL_SYNC();
+struct WaveForm {
+    typedef WaveLds Lds;
+    template <bool WITH_P>
+    static NUCL_HD void extz2(const SeqView &qv, int qlen, const SeqView &tv, int tlen, const int8_t *mat, int q, int e, int zdrop,
+                                 Lds &S, uint8_t *p, Ez &ez) {
+        ksw_extz2_wave<WITH_P>(qv, qlen, tv, tlen, mat, q, e, zdrop, S, p, ez);
     }
-}
+    static NUCL_HD int lane0(int v) { return NUCL_READLANE(v, 0); }
+    static NUCL_HD int walk(const uint8_t *p, int qlen, int tlen, int i0, int j0, char *w, Lds &S) {
+        return ksw_walk_wave(p, qlen, tlen, i0, j0, w, S);
+    }
+};
+
+// One wavefront (nucl_wave_kernel.hip, tests/nucl_emu.cpp): pulls pairs from the queue until it is empty.
+NUCL_HD void align_wave(const NuclLaunch &L, WaveLds &S, uint8_t *p, char *w) { align_pairs<WaveForm>(L, S, p, w); }
 
 }  // namespace nuclw
 }  // namespace mmgpu

@@ -67,6 +67,38 @@ def test_kernel_source_on_emulated_lanes_matches_param_vectors(vectors, key, lan
                                                                                       npc.hit_tuple(h), c[6])
 
 
+def test_lengths_around_the_lane_counts_on_both_emulated_forms():
+    """Both forms count identities with every lane on a chunk of the string (nucl_core.h count_identities): queries and targets
+    of 1 ... 65 letters give strings shorter than, as long as and just longer than 16 and 64 lanes - a mutated copy (substitutions,
+    one deletion and one insertion, so that the chunks start behind gaps) and an unrelated sequence per pair of lengths, stock
+    settings, all six result fields and the string against the restatement (oracle/nucl_oracle.c)."""
+    from tests import nucl_common as nc
+    g = nc.golden()
+    mat, rl = np.asarray(g["mat"]).reshape(5, 5), np.asarray(g["reverse"])
+    lengths = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65]
+    rng = np.random.default_rng(77)
+    queries, targets = [], []
+    for qn in lengths:
+        for tn in lengths:
+            base = rng.integers(0, 4, size=max(qn, tn)).astype(np.uint8)
+            copy = np.where(rng.random(tn) < 0.08, rng.integers(0, 4, size=tn), base[:tn]).astype(np.uint8)
+            if tn >= 15:      # one letter out, one in: the length stays
+                copy = np.concatenate([copy[:tn // 3], copy[tn // 3 + 1:2 * tn // 3], rng.integers(0, 4, size=1), copy[2 * tn // 3:]]).astype(np.uint8)
+            for t in (copy, rng.integers(0, 4, size=tn).astype(np.uint8)):
+                queries.append(base[:qn].copy())
+                targets.append(t)
+    assert {(len(q), len(t)) for q, t in zip(queries, targets)} == {(a, b) for a in lengths for b in lengths}
+    pairs = [(i, i, 0, 0) for i in range(len(queries))]
+    orc = po.NuclOracle()
+    expected = [orc.align(q, t, mat.reshape(-1), rl, 5, 2, 40, 0, 0, 4, 4) for q, t in zip(queries, targets)]
+    assert {len(e[1]) for e in expected} >= {1, 2, 15, 16, 17, 63, 64, 65} and sum("I" in e[1] or "D" in e[1] for e in expected) >= 10
+    for lanes, wave in ((16, False), (64, True)):
+        hits, strs = te.emu_align(te._lib(lanes, wave), mat, rl, queries, targets, pairs, 4, 4)
+        for k, (e, h, s) in enumerate(zip(expected, hits, strs)):
+            assert h["status"] == 0 and npc.hit_tuple(h) == e[0][:6] and s == e[1], (lanes, k, len(queries[k]), len(targets[k]),
+                                                                                  npc.hit_tuple(h), e[0], s, e[1])
+
+
 def test_emulator_ucontext_fallback_matches_param_vectors(vectors):
     """tests/nucl_emu.cpp switches lanes with its own stack switch on x86-64 and with ucontext elsewhere (-DEMU_UCONTEXT forces
     it): the fallback is built here and gives the recorded results too (the short cases of one setting: it is ten times slower)"""
