@@ -81,7 +81,12 @@ int mmgpu_host_partition_targets(const uint64_t *offsets, uint32_t n_targets, ui
  * or equivalently Sequence::numSequence of every DBReader entry concatenated.  Replaces Marv::loadDb
  * (ungappedprefilter.cpp:153-158).  The copy in HBM is re-laid out (4-byte aligned starts, lengths,
  * length-sorted id list); ids in every later call are indices into this array (shard-local ids,
- * the reference's dbFrom convention, Prefiltering.cpp:879-881). */
+ * the reference's dbFrom convention, Prefiltering.cpp:879-881).
+ * A failed call: one refused for its arguments (NULL, alphabet range, offsets not ascending, a sequence over 65535 residues, more
+ * than 16 GiB of residues) leaves the context exactly as it was.  Every later failure (out of device memory, a residue code >=
+ * alphabet, which is only found while the residues are packed) leaves it EMPTY: the resident database has gone before the new one
+ * was allocated (both may not fit), with its masked view, its prefilter index and the shard flag; the next alignment call answers
+ * "no targets loaded". */
 int mmgpu_load_targets(mmgpu_ctx *ctx, const uint8_t *residues, const uint64_t *offsets, uint32_t n_targets,
                        int alphabet);
 /* Loading a database drops a resident prefilter index (it indexes the previous database): call mmgpu_pf_load_index /
@@ -382,7 +387,11 @@ typedef struct {
                                  * the k-mer index, 21^k offsets), its queries match exactly; windows containing X are skipped as ever */
 } mmgpu_pf_index;
 /* Copies the tables into HBM.  The SequenceLookup the ungapped scorer reads is the database given to
- * mmgpu_load_targets (call that first, with the - possibly masked - SequenceLookup residues). */
+ * mmgpu_load_targets (call that first, with the - possibly masked - SequenceLookup residues).
+ * A failed call: one refused for its arguments (every check of the descriptor and of the arrays it names: row sizes, score rows
+ * sorted by descending score, offsets monotone, entries naming loaded targets) leaves the resident index answering as before.  A
+ * later failure (device memory, upload) leaves the context without an index: the old one has gone before the new tables were
+ * allocated.  The targets are untouched either way. */
 int mmgpu_pf_load_index(mmgpu_ctx *ctx, const mmgpu_pf_index *index);
 
 /* Device-side index construction (GPU-resident DB): IndexBuilder::fillDatabase with masking
@@ -390,7 +399,8 @@ int mmgpu_pf_load_index(mmgpu_ctx *ctx, const mmgpu_pf_index *index);
  * mmgpu_host_index_build returns, built in HBM.  `tables` supplies the score matrices and the ungapped matrix as for
  * mmgpu_pf_load_index (its offsets / entries fields are ignored); kmer_submat is BaseMatrix::subMatrix of the k-mer
  * matrix (short, alphabet x alphabet), kmer_thr the k-mer threshold that also gates which target k-mers are indexed
- * (IndexTable.h:146-154). */
+ * (IndexTable.h:146-154).  A failed call leaves behind what a failed mmgpu_pf_load_index does: the resident index when the
+ * arguments were refused, no index when the device failed later. */
 int mmgpu_pf_build_index(mmgpu_ctx *ctx, const mmgpu_pf_index *tables, const int16_t *kmer_submat, int kmer_thr);
 /* optional: loads the kernels' code objects now instead of at their first launch (0.1 - 0.2 s otherwise paid inside the first
  * prefilter block / alignment batch of a process); thread-safe with respect to other calls on the context */
@@ -423,7 +433,9 @@ int mmgpu_pf_debug_index(mmgpu_ctx *ctx, uint64_t *offsets, uint32_t *ids, uint1
  * for mmgpu_pf_build_index (`tables`: offsets / entries fields ignored).  The two fingerprints are the caller's: of the source
  * database (the drop-in hashes the keys and lengths of the DBReader), and of everything else the index depends on (k, pattern,
  * k-mer threshold, matrices, mask parameters).  A file that does not match - or is not there - is answered MMGPU_ERR_STATE and
- * the caller builds as ever (and may save).  index_fingerprint == 0: save / load the targets only (the alignment module's view). */
+ * the caller builds as ever (and may save).  index_fingerprint == 0: save / load the targets only (the alignment module's view).
+ * A failed mmgpu_db_load - no file, another database, a damaged section of the targets or of the index, no device memory - leaves
+ * the context as it was, index included: it takes the file's content only when all of it has been uploaded and checked. */
 typedef struct mmgpu_db_info {
     uint64_t source_fingerprint, index_fingerprint;
     uint32_t n_targets, alphabet;

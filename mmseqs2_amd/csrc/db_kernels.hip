@@ -1,4 +1,4 @@
-// Persisted device layout (mmgpu_db_save / mmgpu_db_load, pf_api.hip): what protects the kernels
+// Persisted device layout (mmgpu_db_save / mmgpu_db_load, db_file.hip): what protects the kernels
 // from a damaged or foreign file.  A section's checksum is taken on the device where the section lies (at save time from the
 // resident arrays, at load time from what the copy engine delivered) and the layout is checked for the properties the kernels
 // rely on - a target's residues inside the residue block, offsets non-decreasing and ending at the entry count, entry ids below

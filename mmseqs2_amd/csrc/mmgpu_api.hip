@@ -1,4 +1,4 @@
-// Host side of libmmgpu: context, target database residency, batch scheduling, launches.
+// Host side of libmmgpu: context, host helpers, batch scheduling, launches.  (What a context holds resident: db_api.hip.)
 // Everything here is plumbing around the kernels in sw_kernel.hip; see include/mmgpu.h for the contract.
 #include <algorithm>
 #include <atomic>
@@ -39,13 +39,6 @@ extern "C" int mmgpu_init(mmgpu_ctx **out, int device_id) {
     return MMGPU_OK;
 }
 
-static void free_db(DeviceDb &db) {
-    dev_free(db.res);
-    dev_free(db.off4);
-    dev_free(db.len);
-    db = DeviceDb();
-}
-
 namespace mmgpu {
 // the context's pinned staging arena (mmgpu_ctx::pinned) for the length of a call.  acquire() grows the arena to `need`
 // bytes and returns it, or null - another thread's call holds it, or pinned memory cannot be had - and the caller copies from / to
@@ -72,23 +65,12 @@ void *PinnedLease::acquire(mmgpu_ctx *ctx, size_t need) {
     return ctx->pinned_cap >= need ? ctx->pinned : nullptr;
 }
 
-// what mmgpu_load_targets drops before it loads: the resident targets, their masked view, the index over them, the shard description
-void db_release(mmgpu_ctx *c) {
-    pf_index_free(c);
-    c->shard.on = false;
-    if (c->pf_masked_res) { dev_free(c->pf_masked_res); c->pf_masked_res = nullptr; }
-    free_db(c->db);
-    c->h_len.clear();
-    c->mean_len = 0;
-}
 }  // namespace mmgpu
 
 extern "C" void mmgpu_destroy(mmgpu_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    free_db(c->db);
-    if (c->pf_masked_res) { dev_free(c->pf_masked_res); c->pf_masked_res = nullptr; }
-    mmgpu::pf_index_free(c);
+    mmgpu::db_release(c);
     (void)hipDeviceSynchronize();
     mmgpu::comm_free(c);
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -134,98 +116,6 @@ extern "C" int mmgpu_device_memory(mmgpu_ctx *c, uint64_t *free_bytes, uint64_t 
     return MMGPU_OK;
 }
 
-extern "C" int mmgpu_load_targets(mmgpu_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n,
-                                  int alphabet) {
-    if (!c || !residues || !offsets) return fail(MMGPU_ERR_ARG, "mmgpu_load_targets: NULL argument");
-    if (alphabet < 2 || alphabet > 254) return fail(MMGPU_ERR_ARG, "mmgpu_load_targets: bad alphabet size");
-    HIP_TRY(hipSetDevice(c->device));
-    // a resident prefilter index belongs to the database it was built / loaded for: it goes with it
-    mmgpu::pf_index_free(c);
-    c->shard.on = false;
-    if (c->pf_masked_res) { dev_free(c->pf_masked_res); c->pf_masked_res = nullptr; }
-    free_db(c->db);
-    std::vector<uint32_t> off4(std::max<uint32_t>(n, 1)), len(std::max<uint32_t>(n, 1));
-    uint64_t cur4 = 16;      // 64 bytes of padding in front: the reverse scan reads up to 3 bytes before a target (sw_kernel.hip)
-    uint32_t max_len = 0;
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (offsets[i + 1] < offsets[i]) return fail(MMGPU_ERR_ARG, "mmgpu_load_targets: offsets not monotone");
-        uint64_t l = offsets[i + 1] - offsets[i];
-        if (l > 65535) return fail(MMGPU_ERR_ARG, "mmgpu_load_targets: sequence longer than 65535 (Parameters.h:271)");
-        if (cur4 > 0xFFFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_load_targets: more than 16 GiB of residues per shard");
-        off4[i] = (uint32_t)cur4;
-        len[i] = (uint32_t)l;
-        max_len = std::max<uint32_t>(max_len, (uint32_t)l);
-        total += l;
-        cur4 += (l + 3) / 4;
-    }
-    const size_t bytes = (size_t)cur4 * 4 + max_len + 64;
-    // Layout in HBM: 64 B of padding, every target at a 4-byte boundary (pad letters = the "no letter" code), max_len + 64 B of
-    // padding behind the last.  The device buffer is filled with the pad code, then the targets travel in chunks: the host threads
-    // pack chunk j + 1 into one of two pinned staging buffers while the copy engine moves chunk j (a pageable 280 MB buffer packed
-    // first and copied then cost 0.14 s for the 1 M targets of configs[2], 2 GB/s).
-    DbBuild nb;
-    UploadRing ring;      // (after nb: the stream has drained before a failure frees the buffers it copies into)
-    DeviceDb &db = nb.db;
-    HIP_TRY(dev_malloc_ctx(c, (void **)&db.res, bytes));
-    HIP_TRY(dev_malloc_ctx(c, (void **)&db.off4, off4.size() * sizeof(uint32_t)));
-    HIP_TRY(dev_malloc_ctx(c, (void **)&db.len, len.size() * sizeof(uint32_t)));
-    HIP_TRY(ring.open(2));
-    hipStream_t up = ring.up.s;
-    HIP_TRY(hipMemsetAsync(db.res, alphabet, bytes, up));
-    HIP_TRY(hipMemcpyAsync(db.off4, off4.data(), off4.size() * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-    HIP_TRY(hipMemcpyAsync(db.len, len.data(), len.size() * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-    const size_t chunk_bytes = (size_t)std::min<uint64_t>(32ull << 20, std::max<uint64_t>((uint64_t)(cur4 - 16) * 4, 4096));
-    std::atomic<bool> bad_res(false);
-    for (uint32_t first = 0, j = 0; first < n; j++) {
-        // targets [first, last): at most chunk_bytes of packed residues (one target alone may exceed it by < 64 KB: staged is sized for that)
-        const uint64_t base = (uint64_t)off4[first] * 4;
-        uint32_t last = first + 1;
-        {
-            uint32_t lo = first + 1, hi = n;        // largest last with packed end <= base + chunk_bytes
-            while (lo < hi) {
-                const uint32_t mid = lo + (hi - lo + 1) / 2;
-                const uint64_t end_mid = mid < n ? (uint64_t)off4[mid] * 4 : (uint64_t)cur4 * 4;
-                if (end_mid - base <= chunk_bytes) lo = mid; else hi = mid - 1;
-            }
-            last = lo;
-        }
-        const uint64_t end = last < n ? (uint64_t)off4[last] * 4 : (uint64_t)cur4 * 4;
-        const size_t k = j & 1;
-        if (!ring.slots[k].p) HIP_TRY(ring.slots[k].reserve(chunk_bytes + 65536 + 64));
-        else HIP_TRY(ring.wait(k));      // the copy out of this buffer two chunks ago
-        uint8_t *dst = ring.slots[k].p;
-        parallel_for((size_t)(last - first), [&, first, base, dst](size_t a, size_t b) {
-            for (size_t i = first + a; i < first + b; i++) {
-                const uint8_t *src = residues + offsets[i];
-                uint8_t *out = dst + ((uint64_t)off4[i] * 4 - base);
-                const uint32_t l = len[i];
-                uint8_t top = 0;
-                for (uint32_t x = 0; x < l; x++) top = std::max(top, src[x]);
-                if (top >= alphabet) bad_res = true;
-                memcpy(out, src, l);
-                for (uint32_t x = l; x < ((l + 3) & ~3u); x++) out[x] = (uint8_t)alphabet;
-            }
-        });
-        HIP_TRY(hipMemcpyAsync(db.res + base, dst, end - base, hipMemcpyHostToDevice, up));
-        HIP_TRY(ring.sent(k));
-        first = last;
-    }
-    HIP_TRY(hipStreamSynchronize(up));
-    if (bad_res) return fail(MMGPU_ERR_ARG, "mmgpu_load_targets: residue code >= alphabet");
-    db.n = n;
-    db.res_bytes = bytes;
-    db.max_len = max_len;
-    db.total_residues = total;
-    db.alphabet = alphabet;
-    c->db = nb.take_db();
-    c->h_len.assign(len.begin(), len.begin() + n);
-    uint64_t res_total = 0;
-    for (uint32_t i = 0; i < n; i++) res_total += len[i];
-    c->mean_len = n ? (uint32_t)(res_total / n) : 0;
-    return MMGPU_OK;
-}
-
 // Loads the code objects of the hot kernels now instead of at their first launch (the runtime loads a translation unit's code
 // object lazily: 0.1 - 0.2 s in total, paid inside the first prefilter block and the first alignment batch of a process).  A
 // caller that has something else to do meanwhile - the fused search masks / reads its databases on the host - calls this on a
@@ -243,138 +133,6 @@ extern "C" int mmgpu_warmup(mmgpu_ctx *c) {
     mmgpu::warm_scan();
     mmgpu::warm_gscan();
     mmgpu::warm_rescore();
-    return MMGPU_OK;
-}
-
-// tantan masking of the resident targets for the prefilter (tantan_kernel.hip): what IndexBuilder::fillDatabase does to every
-// target before it counts k-mers (IndexBuilder.cpp:148, Masker.cpp:14-57 with maskTantan only).  The alignment kernels keep
-// reading the unmasked residues.
-extern "C" int mmgpu_pf_mask_targets(mmgpu_ctx *c, const double *likelihood_ratios, int alphabet, double min_mask_prob, int mask_letter,
-                                     uint64_t *n_masked) {
-    if (!c) return fail(MMGPU_ERR_ARG, "mmgpu_pf_mask_targets: NULL argument");
-    if (!c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_pf_mask_targets: no targets loaded");
-    if (!likelihood_ratios) {      // back to the unmasked view (--mask 0 after --mask 1 on a resident database): the masked copy and its index go
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        mmgpu::pf_index_free(c);
-        if (c->pf_masked_res) dev_free(c->pf_masked_res);
-        c->pf_masked_res = nullptr;
-        if (n_masked) *n_masked = 0;
-        return MMGPU_OK;
-    }
-    if (alphabet != c->db.alphabet || alphabet > 32) return fail(MMGPU_ERR_ARG, "mmgpu_pf_mask_targets: alphabet differs from the loaded targets (or exceeds 32)");
-    if (mask_letter < 0 || mask_letter >= alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_pf_mask_targets: mask letter outside the alphabet");
-    HIP_TRY(hipSetDevice(c->device));
-    mmgpu::pf_index_free(c);      // an index built from the unmasked residues does not describe the masked ones
-    hipStream_t s = c->stream;
-    const uint32_t n = c->db.n;
-    if (!c->pf_masked_res) HIP_TRY(dev_malloc_ctx(c, (void **)&c->pf_masked_res, c->db.res_bytes));
-    HIP_TRY(hipMemcpyAsync(c->pf_masked_res, c->db.res, c->db.res_bytes, hipMemcpyDeviceToDevice, s));
-    // targets in order of length (longest first): 64 consecutive ones share a wavefront and end together; counting sort
-    std::vector<uint32_t> order(std::max<uint32_t>(n, 1));
-    {
-        std::vector<uint32_t> first(65536 + 2, 0);
-        for (uint32_t i = 0; i < n; i++) first[65535 - std::min<uint32_t>(c->h_len[i], 65535) + 1]++;
-        for (size_t k = 1; k < first.size(); k++) first[k] += first[k - 1];
-        for (uint32_t i = 0; i < n; i++) order[first[65535 - std::min<uint32_t>(c->h_len[i], 65535)]++] = i;
-    }
-    const uint32_t n_waves = (n + 63) / 64;
-    std::vector<uint64_t> pbase(std::max<uint32_t>(n_waves, 1)), sbase(std::max<uint32_t>(n_waves, 1));
-    uint64_t pcur = 0, scur = 0;
-    for (uint32_t w = 0; w < n_waves; w++) {
-        const uint64_t longest = c->h_len[order[(size_t)w * 64]];      // the first of a wavefront is its longest
-        pbase[w] = pcur;
-        sbase[w] = scur;
-        pcur += longest * 64;
-        scur += (longest / 16 + 1) * 64;
-    }
-    // Tantan's constructor (tantan.cpp:94-131) with the Masker's constants (Masker.cpp:22-31)
-    const double repeat_prob = 0.005, repeat_end_prob = 0.05, decay = 0.9;
-    const int max_offset = 50;
-    std::vector<double> b2f(max_offset);
-    {
-        const double first_prob = (decay < 1 || decay > 1) ? (1 - decay) / (1 - std::pow(decay, max_offset)) : 1.0 / max_offset;   // :38-44
-        double p = repeat_prob * first_prob;
-        for (int i = 0; i < max_offset; i++) {
-            b2f[i] = p;
-            p *= decay;
-        }
-    }
-    DevBuf d_order, d_pbase, d_sbase, d_lr, d_b2f, d_probs, d_scales, d_count;
-    for (DevBuf *d : {&d_order, &d_pbase, &d_sbase, &d_lr, &d_b2f, &d_probs, &d_scales, &d_count}) d->bind(c->cache);
-    HIP_TRY(upload(d_order, order, s));
-    HIP_TRY(upload(d_pbase, pbase, s));
-    HIP_TRY(upload(d_sbase, sbase, s));
-    std::vector<double> lr(likelihood_ratios, likelihood_ratios + (size_t)alphabet * alphabet);
-    HIP_TRY(upload(d_lr, lr, s));
-    HIP_TRY(upload(d_b2f, b2f, s));
-    // The forward probabilities (4 B per residue) and scale factors (0.5 B) are scratch: wavefronts run in chunks whose scratch stays
-    // below MMGPU_TANTAN_SCRATCH_MB (default 8 GB; a quarter of the free memory if that is less) - one chunk for 1 M targets, several
-    // for a shard near the 16 G-residue limit, which would otherwise ask for 70 GB on top of the masked copy.
-    uint64_t budget = (getenv("MMGPU_TANTAN_SCRATCH_MB") ? strtoull(getenv("MMGPU_TANTAN_SCRATCH_MB"), nullptr, 10) : 8192ull) << 20;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget = std::min<uint64_t>(budget, std::max<uint64_t>(mem_free / 4, 64ull << 20));
-    }
-    std::vector<uint32_t> chunk_first(1, 0);      // wavefronts [chunk_first[k], chunk_first[k + 1])
-    uint64_t chunk_p = 0, chunk_s = 0;            // the largest chunk's scratch (floats, doubles)
-    auto p_end = [&](uint32_t w) { return w < n_waves ? pbase[w] : pcur; };
-    auto s_end = [&](uint32_t w) { return w < n_waves ? sbase[w] : scur; };
-    for (uint32_t w0 = 0; w0 < n_waves;) {
-        uint32_t w1 = w0 + 1;      // (a single wavefront over the budget runs alone)
-        while (w1 < n_waves && (p_end(w1 + 1) - pbase[w0]) * 4 + (s_end(w1 + 1) - sbase[w0]) * 8 <= budget) w1++;
-        chunk_p = std::max(chunk_p, p_end(w1) - pbase[w0]);
-        chunk_s = std::max(chunk_s, s_end(w1) - sbase[w0]);
-        chunk_first.push_back(w1);
-        w0 = w1;
-    }
-    HIP_TRY(d_probs.alloc(std::max<uint64_t>(chunk_p, 1) * sizeof(float)));
-    HIP_TRY(d_scales.alloc(std::max<uint64_t>(chunk_s, 1) * sizeof(double)));
-    HIP_TRY(d_count.alloc(8));
-    HIP_TRY(hipMemsetAsync(d_count.p, 0, 8, s));
-    TantanArgs A;
-    A.t_res = c->db.res;
-    A.out_res = c->pf_masked_res;
-    A.t_off4 = c->db.off4;
-    A.t_len = c->db.len;
-    A.order = d_order.as<uint32_t>();
-    A.n = n;
-    A.lr = d_lr.as<double>();
-    A.b2f = d_b2f.as<double>();
-    A.alphabet = alphabet;
-    A.repeat_prob = repeat_prob;
-    A.repeat_end_prob = repeat_end_prob;
-    A.min_mask_prob = min_mask_prob;
-    A.mask_letter = (uint8_t)mask_letter;
-    A.n_masked = d_count.as<unsigned long long>();
-    for (size_t k = 0; k + 1 < chunk_first.size(); k++) {      // (same stream: a chunk's scratch is free again when the next one starts)
-        const uint32_t w0 = chunk_first[k], w1 = chunk_first[k + 1];
-        A.order = d_order.as<uint32_t>() + (size_t)w0 * 64;
-        A.n = std::min<uint32_t>(n - w0 * 64, (w1 - w0) * 64);
-        // the bases stay absolute: the scratch pointers are moved back by the chunk's first base instead
-        A.probs = d_probs.as<float>() - pbase[w0];
-        A.scales = d_scales.as<double>() - sbase[w0];
-        A.wave_prob_base = d_pbase.as<uint64_t>() + w0;
-        A.wave_scale_base = d_sbase.as<uint64_t>() + w0;
-        HIP_TRY(launch_tantan_mask(A, s));
-    }
-    unsigned long long masked = 0;
-    HIP_TRY(hipMemcpyAsync(&masked, d_count.p, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));      // the host vectors above die with this scope
-    if (n_masked) *n_masked = masked;
-    return MMGPU_OK;
-}
-
-// test hook: the prefilter's (masked) view of the resident targets back on the host, in the caller's layout
-extern "C" int mmgpu_pf_debug_masked_targets(mmgpu_ctx *c, const uint64_t *offsets, uint32_t n, uint8_t *residues) {
-    if (!c || !offsets || !residues) return fail(MMGPU_ERR_ARG, "mmgpu_pf_debug_masked_targets: NULL argument");
-    if (!c->db.res || n != c->db.n) return fail(MMGPU_ERR_STATE, "mmgpu_pf_debug_masked_targets: not the resident target set");
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<uint8_t> packed(c->db.res_bytes);
-    HIP_TRY(hipMemcpy(packed.data(), c->pf_res(), packed.size(), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> off4(std::max<uint32_t>(n, 1));
-    HIP_TRY(hipMemcpy(off4.data(), c->db.off4, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; i++) memcpy(residues + offsets[i], packed.data() + (size_t)off4[i] * 4, (size_t)(offsets[i + 1] - offsets[i]));
     return MMGPU_OK;
 }
 

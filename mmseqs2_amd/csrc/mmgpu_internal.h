@@ -924,7 +924,7 @@ inline void parallel_for(size_t n, F f) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// host-side plumbing shared by mmgpu_api.hip and pf_api.hip
+// host-side plumbing shared by the *_api.hip translation units
 extern thread_local std::string g_last_error;
 inline int fail(int code, const std::string &msg) {
     g_last_error = msg;
@@ -1088,18 +1088,6 @@ struct UploadRing {
     hipError_t sent(size_t k) const { return hipEventRecord(slots[k].moved, up.s); }
 };
 
-// A target database under construction (and the prefilter's masked view of it): freed unless the context takes it
-struct DbBuild {
-    DeviceDb db;
-    uint8_t *masked = nullptr;
-    DbBuild() = default;
-    DbBuild(const DbBuild &) = delete;
-    DbBuild &operator=(const DbBuild &) = delete;
-    ~DbBuild() { dev_free(db.res); dev_free(db.off4); dev_free(db.len); dev_free(masked); }
-    DeviceDb take_db() { DeviceDb d = db; db = DeviceDb(); return d; }
-    uint8_t *take_masked() { uint8_t *m = masked; masked = nullptr; return m; }
-};
-
 template <typename T>
 inline hipError_t upload(DevBuf &b, const std::vector<T> &v, hipStream_t s) {
     hipError_t e = b.alloc(std::max<size_t>(v.size(), 1) * sizeof(T));
@@ -1130,7 +1118,7 @@ hipError_t launch_nucl_align_wave(const NuclLaunch &L, unsigned blocks, hipStrea
 
 hipError_t launch_pf_order(const PfKmerArgs &A, uint32_t *order, const std::shared_ptr<BlockCache> &cache, hipStream_t s);   // pf_order.hip
 
-struct PfIndex;   // pf_api.hip
+struct PfIndex;   // pf_index.h
 
 }  // namespace mmgpu
 
@@ -1153,13 +1141,13 @@ struct mmgpu_ctx {
     uint32_t mean_len = 0;
     int compute_units = 0;
     std::string name;
-    mmgpu::PfIndex *pf = nullptr;  // prefilter index resident in HBM (pf_api.hip)
+    mmgpu::PfIndex *pf = nullptr;  // prefilter index resident in HBM (pf_index.h, pf_index_api.hip)
     // the prefilter's view of the targets when it differs from the alignment's: residues with tantan-masked letters replaced by
     // X (mmgpu_pf_mask_targets; same offsets / lengths as `db`).  null: the prefilter reads db.res (--mask 0, or a caller that
     // loaded an already masked SequenceLookup)
     uint8_t *pf_masked_res = nullptr;
     const uint8_t *pf_res() const { return pf_masked_res ? pf_masked_res : db.res; }
-    // shard of a multi-GPU run (mmgpu_pf_set_shard); reset by mmgpu_load_targets
+    // shard of a multi-GPU run (mmgpu_pf_set_shard); the flag goes with the resident database (db_release)
     struct Shard {
         bool on = false;
         uint32_t n_shards = 1, shard = 0, global_n = 0;
@@ -1233,8 +1221,8 @@ int sw_gather_overflowed(mmgpu_ctx *c, mmgpu_sw_batch_t *b, bool *overflowed);  
 int pf_batch_merged_flags(mmgpu_pf_batch_t *b, const void **d_flags);
 const int32_t *pf_batch_host_status(const mmgpu_pf_batch_t *b);
 bool pf_batch_merged_lists(mmgpu_pf_batch_t *b, const mmgpu_pf_hit **hits, const uint32_t **counts, uint32_t *stride, uint32_t *nq);
-void pf_index_free(mmgpu_ctx *c);
-void db_release(mmgpu_ctx *c);      // mmgpu_api.hip: targets, masked view, index and shard description of a context
+void pf_index_free(mmgpu_ctx *c);   // pf_index_api.hip
+void db_release(mmgpu_ctx *c);      // db_api.hip: the targets, masked view, index and shard flag of a context go (ResidentDb, pf_index.h)
 // device-resident results of a prefilter batch that has been run (false if it has not)
 bool pf_batch_device_lists(mmgpu_pf_batch_t *b, const mmgpu_pf_hit **hits, const uint32_t **counts, uint32_t *stride, uint32_t *nq);
 // mmgpu_api.hip, for gscan_api.hip: a MMGPU_SW_SCORE_END batch over dense lists (mmgpu_sw_prepare's checks, queries, job rules and

@@ -1,5 +1,5 @@
-// Host side of the prefilter half of libmmgpu: table builders, index residency, batch preparation and the
-// launch sequence around pf_kernels.hip.  See include/mmgpu.h for the contract.
+// Host side of the prefilter half of libmmgpu: batch preparation, the launch sequence around pf_kernels.hip, fetch, the shard
+// exchange and the debug fetch.  (The index the batches read: pf_index_api.hip.)  See include/mmgpu.h for the contract.
 #include <unistd.h>
 
 #include <atomic>
@@ -8,531 +8,11 @@
 #include <cstring>
 #include <thread>
 
-#include "mmgpu_internal.h"
+#include "pf_index.h"
 #include "sat_ties.h"
-
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 using namespace mmgpu;
 
-namespace mmgpu {
-
-struct PfIndex {
-    int k = 0, alphabet = 0, kalph = 0, spaced = 0;
-    int kbase = 0;               // base of the k-mer index (kalph, or the full alphabet for a handed-over index of profile targets)
-    uint8_t pat[16] = {0};
-    int pattern_len = 0;
-    bool has_tables = false;   // similar-k-mer score tables present (false: exact k-mer matching only)
-    uint32_t n3 = 0;
-    uint64_t table = 0, n_entries = 0;
-    DevBuf d_s3, d_i3, d_cum3, d_s2, d_i2, d_cum2, d_offsets, d_entries, d_mat;
-    DevBuf d_cofs;               // compact offset table (pf_cofs_kernel): what the similar-k-mer kernels look lists up in
-    bool use_cofs = false;
-    DevBuf d_nonempty;           // one bit per k-mer (pf_bitmap_kernel), used when the index is sparse
-    bool use_bitmap = false;
-    double nonempty_frac = 1.0;  // k-mers with a list / all k-mers
-    uint32_t cum_w = 0, cum2_w = 0;
-    int32_t score_min = 0, score2_min = 0;
-    std::vector<int8_t> h_mat;   // ungapped matrix (host copy for the self score)
-    // Large working buffers, shared by all batches of this context (grow-only; batches run one at a time on the
-    // context's stream): index lists, split tiles, candidates, survivors.
-    DevBuf w_lists, w_split, w_split_hi, w_bin_off, w_cand, w_surv, w_tile_q, w_tile_idx;
-    const void *w_owner = nullptr;   // batch whose last run the working buffers hold (debug fetch)
-};
-
-// The environment's test hooks of the prefilter, read in this one place, once per call that uses them (they are not part of
-// mmgpu_pf_params: that is the ABI and the server's wire format)
-struct PfEnv {
-    bool has_max_db_matches = false, has_sort_cap = false, has_stage_gb = false;
-    uint64_t max_db_matches = 0;   // MMGPU_PF_MAX_DB_MATCHES (at least 64): a small database reaches the overflow path / a shard its share
-    uint64_t sort_cap = 0;         // MMGPU_PF_SORT_CAP: a small database reaches the select kernel's candidate cap
-    double stage_gb = 0;           // MMGPU_PF_STAGE_GB: budget of the candidate + survivor arrays of a stage chunk
-    bool cofs_off = false;         // MMGPU_PF_COFS=0: the similar-k-mer kernels look lists up in the full offset table (A/B runs)
-};
-inline PfEnv pf_env() {
-    PfEnv E;
-    if (const char *e = getenv("MMGPU_PF_MAX_DB_MATCHES")) { E.has_max_db_matches = true; E.max_db_matches = std::max<uint64_t>(64, strtoull(e, nullptr, 10)); }
-    if (const char *e = getenv("MMGPU_PF_SORT_CAP")) { E.has_sort_cap = true; E.sort_cap = strtoull(e, nullptr, 10); }
-    if (const char *e = getenv("MMGPU_PF_STAGE_GB")) { E.has_stage_gb = true; E.stage_gb = atof(e); }
-    if (const char *e = getenv("MMGPU_PF_COFS")) E.cofs_off = e[0] == '0';
-    return E;
-}
-
-// Sparse indexes (a shard of a multi-GPU run holds 1/N of the entries over the same k-mer space; small databases): most similar
-// k-mers of a query have no list.  The bit table is consulted by pf_kmers_kernel when fewer than 60 % of the k-mers have one
-// similar-k-mer searches with k = 6 only (the table of k = 7 has 1.3e9 k-mers).
-static hipError_t pf_index_bitmap(mmgpu_ctx *c, PfIndex *P) {
-    P->use_bitmap = false;
-    if (!P->has_tables || P->k != 6 || P->table > (1ull << 28)) return hipSuccess;
-    hipStream_t s = c->stream;
-    DevBuf d_cnt;
-    hipError_t rc = P->d_nonempty.alloc(((P->table + 31) / 32 + 1) * 4);
-    if (rc == hipSuccess) rc = d_cnt.alloc(8);
-    if (rc == hipSuccess) rc = hipMemsetAsync(d_cnt.p, 0, 8, s);
-    if (rc == hipSuccess) rc = launch_pf_bitmap(P->d_offsets.as<uint32_t>(), P->table, P->d_nonempty.as<uint32_t>(), d_cnt.as<unsigned long long>(), s);
-    unsigned long long n = 0;
-    if (rc == hipSuccess) rc = hipMemcpyAsync(&n, d_cnt.p, 8, hipMemcpyDeviceToHost, s);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(s);
-    if (rc != hipSuccess) return rc;
-    P->nonempty_frac = P->table ? (double)n / (double)P->table : 1.0;
-    P->use_bitmap = P->nonempty_frac < 0.6;
-    if (!P->use_bitmap) P->d_nonempty.release();
-    return hipSuccess;
-}
-
-// the compact offset table of the similar-k-mer kernels (k = 6 and k = 7 with score tables; not for exact matching, whose one
-// look-up per window does not pay for it).  MMGPU_PF_COFS=0 keeps the look-ups on the full table (A/B runs).
-static hipError_t pf_index_cofs(mmgpu_ctx *c, PfIndex *P) {
-    P->use_cofs = false;
-    if (!P->has_tables || P->n_entries >= (1ull << 31) || P->table > (1ull << 31) || pf_env().cofs_off) return hipSuccess;
-    hipError_t rc = P->d_cofs.alloc(pf_cofs_bytes(P->table));
-    if (rc == hipSuccess) rc = launch_pf_cofs(P->d_offsets.as<uint32_t>(), P->table, P->d_cofs.p, c->stream);
-    if (rc == hipSuccess) P->use_cofs = true;
-    return rc;
-}
-
-void pf_index_free(mmgpu_ctx *c) {
-    if (c && c->pf) {
-        delete c->pf;
-        c->pf = nullptr;
-    }
-}
-
-}  // namespace mmgpu
-
-// spaced_seed_<k> of Sequence.h:20-50 as bit masks (bit i = pattern position i) and their lengths
-static const uint32_t SPACED_BITS[16] = {0, 0, 0, 0, 0x17u, 0xA13u, 0x32Bu, 0x66Bu, 0xCEBu, 0x366Bu, 0x6D6Bu, 0x1B66Bu, 0x6B66Bu, 0xD6CEBu,
-                                         0x1B6CEBu, 0x6D1BD7u};
-static const uint8_t SPACED_LEN[16] = {0, 0, 0, 0, 5, 12, 10, 11, 12, 14, 15, 17, 19, 20, 21, 23};
-
-static int window_pattern(int k, int spaced, uint8_t *pat) {     // k in [4, 15]
-    if (!spaced) {
-        for (int i = 0; i < k; i++) pat[i] = (uint8_t)i;
-        return k;
-    }
-    const int n = SPACED_LEN[k];
-    int c = 0;
-    for (int i = 0; i < n; i++)
-        if ((SPACED_BITS[k] >> i) & 1u) pat[c++] = (uint8_t)i;
-    return n;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// ExtendedSubstitutionMatrix::calcScoreMatrix (src/prefiltering/ExtendedSubstitutionMatrix.cpp:20-71).  Row r lists
-// every span-mer by descending score; the reference uses std::stable_sort over the cartesian-product enumeration
-// (first residue slowest, :103-128).  Scores are small integers, so a stable counting sort per row does the same.
-extern "C" int mmgpu_host_score_matrix(const int16_t *submat, int alphabet, int span, int16_t *score, uint32_t *index) {
-    return mmgpu_host_score_matrix_rows(submat, alphabet, span, 0, score, index);
-}
-
-// the same into rows of row_stride elements (ScoreMatrix::rowSize: the reference pads its rows for SIMD loads, :24-25; the
-// padding elements are the caller's); row_stride 0 = (alphabet - 1)^span, no padding
-extern "C" int mmgpu_host_score_matrix_rows(const int16_t *submat, int alphabet, int span, size_t row_stride, int16_t *score, uint32_t *index) {
-    if (!submat || !score || !index) return fail(MMGPU_ERR_ARG, "mmgpu_host_score_matrix: NULL argument");
-    if (alphabet < 3 || alphabet > 32 || span < 1 || span > 3) return fail(MMGPU_ERR_ARG, "mmgpu_host_score_matrix: bad alphabet/span");
-    const int ka = alphabet - 1;
-    size_t n = 1;
-    for (int i = 0; i < span; i++) n *= (size_t)ka;
-    const size_t stride = row_stride ? row_stride : n;
-    if (stride < n) return fail(MMGPU_ERR_ARG, "mmgpu_host_score_matrix_rows: row_stride smaller than the row");
-    // enumeration e -> (index in int2index order, residues)
-    std::vector<uint32_t> e2idx(n);
-    std::vector<uint8_t> e2res(n * (size_t)span);
-    for (size_t e = 0; e < n; e++) {
-        size_t t = e;
-        for (int p = span - 1; p >= 0; p--) {
-            e2res[e * span + p] = (uint8_t)(t % (size_t)ka);
-            t /= (size_t)ka;
-        }
-        size_t idx = 0, pw = 1;
-        for (int p = 0; p < span; p++) {
-            idx += e2res[e * span + p] * pw;
-            pw *= (size_t)ka;
-        }
-        e2idx[e] = (uint32_t)idx;
-    }
-    int lo = 0, hi = 0;
-    for (int a = 0; a < ka; a++)
-        for (int b = 0; b < ka; b++) {
-            lo = std::min<int>(lo, submat[a * alphabet + b]);
-            hi = std::max<int>(hi, submat[a * alphabet + b]);
-        }
-    const int smin = lo * span, smax = hi * span, range = smax - smin + 1;
-    parallel_for(n, [&](size_t r0, size_t r1) {
-        std::vector<int16_t> sc(n);
-        std::vector<uint32_t> cursor((size_t)range + 1);
-        for (size_t e = r0; e < r1; e++) {
-            const uint8_t *a = &e2res[e * span];
-            std::fill(cursor.begin(), cursor.end(), 0u);
-            for (size_t f = 0; f < n; f++) {
-                const uint8_t *b = &e2res[f * span];
-                int s = 0;
-                for (int p = 0; p < span; p++) s += submat[a[p] * alphabet + b[p]];
-                sc[f] = (int16_t)s;
-                cursor[(size_t)(smax - s) + 1]++;   // bucket 0 = highest score
-            }
-            for (int z = 0; z < range; z++) cursor[(size_t)z + 1] += cursor[z];
-            int16_t *srow = score + (size_t)e2idx[e] * stride;
-            uint32_t *irow = index + (size_t)e2idx[e] * stride;
-            for (size_t f = 0; f < n; f++) {
-                const uint32_t o = cursor[(size_t)(smax - sc[f])]++;
-                srow[o] = sc[f];
-                irow[o] = e2idx[f];
-            }
-        }
-    });
-    return MMGPU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// IndexTable::addKmerCount / addSequence / sortDBSeqLists (src/prefiltering/IndexTable.h:135-191,350-403) as
-// IndexBuilder::fillDatabase drives them with masking off (IndexBuilder.cpp:118-166,226-270).
-namespace {
-struct KmerWindows {
-    int k, ka, alphabet, plen, thr;
-    uint8_t pat[16];
-    int8_t self[32];   // (char) subMatrix[a][a], IndexBuilder.cpp:11-22
-    // unique k-mers of one target with their first position, sorted by k-mer; key = kmer << 16 | pos
-    void extract(const uint8_t *s, uint64_t len, std::vector<uint64_t> &buf) const {
-        buf.clear();
-        for (uint64_t i = 0; i + (uint64_t)plen <= len; i++) {
-            uint64_t idx = 0, pw = 1;
-            int sc = 0;
-            bool x = false;
-            for (int p = 0; p < k; p++) {
-                const uint8_t r = s[i + pat[p]];
-                if (r >= ka) { x = true; break; }
-                idx += r * pw;
-                pw *= (uint64_t)ka;
-                sc += self[r];
-            }
-            if (x || (thr > 0 && sc < thr)) continue;
-            buf.push_back((idx << 16) | (i & 0xFFFFu));
-        }
-        std::sort(buf.begin(), buf.end());
-        size_t w = 0;
-        uint64_t prev = ~0ull;
-        for (size_t z = 0; z < buf.size(); z++) {
-            if ((buf[z] >> 16) != prev) buf[w++] = buf[z];
-            prev = buf[z] >> 16;
-        }
-        buf.resize(w);
-    }
-};
-}  // namespace
-
-extern "C" int mmgpu_host_index_build(const uint8_t *residues, const uint64_t *seq_off, uint32_t n, const int16_t *kmer_submat,
-                                      int alphabet, int k, int spaced, int kmer_thr, uint64_t *offsets, uint32_t *ids,
-                                      uint16_t *pos, uint64_t *n_entries) {
-    if (!residues || !seq_off || !kmer_submat || !offsets || !n_entries)
-        return fail(MMGPU_ERR_ARG, "mmgpu_host_index_build: NULL argument");
-    if ((k < 5 || k > 7) || alphabet < 3 || alphabet > 32) return fail(MMGPU_ERR_ARG, "mmgpu_host_index_build: bad k/alphabet");
-    if ((ids == nullptr) != (pos == nullptr)) return fail(MMGPU_ERR_ARG, "mmgpu_host_index_build: ids and pos go together");
-    KmerWindows W;
-    W.k = k;
-    W.ka = alphabet - 1;
-    W.alphabet = alphabet;
-    W.thr = kmer_thr;
-    W.plen = window_pattern(k, spaced, W.pat);
-    for (int a = 0; a < alphabet; a++) W.self[a] = (int8_t)(char)kmer_submat[a * alphabet + a];
-    uint64_t table = 1;
-    for (int i = 0; i < k; i++) table *= (uint64_t)W.ka;
-    std::vector<std::atomic<uint32_t>> cnt(table);
-    for (auto &c : cnt) c.store(0, std::memory_order_relaxed);
-    parallel_for(n, [&](size_t a, size_t b) {
-        std::vector<uint64_t> buf;
-        for (size_t t = a; t < b; t++) {
-            W.extract(residues + seq_off[t], seq_off[t + 1] - seq_off[t], buf);
-            for (uint64_t v : buf) cnt[v >> 16].fetch_add(1, std::memory_order_relaxed);
-        }
-    });
-    uint64_t run = 0;
-    for (uint64_t z = 0; z < table; z++) {
-        offsets[z] = run;
-        run += cnt[z].load(std::memory_order_relaxed);
-    }
-    offsets[table] = run;
-    *n_entries = run;
-    if (!ids) return MMGPU_OK;
-    for (auto &c : cnt) c.store(0, std::memory_order_relaxed);
-    parallel_for(n, [&](size_t a, size_t b) {
-        std::vector<uint64_t> buf;
-        for (size_t t = a; t < b; t++) {
-            W.extract(residues + seq_off[t], seq_off[t + 1] - seq_off[t], buf);
-            for (uint64_t v : buf) {
-                const uint64_t o = offsets[v >> 16] + cnt[v >> 16].fetch_add(1, std::memory_order_relaxed);
-                ids[o] = (uint32_t)t;
-                pos[o] = (uint16_t)(v & 0xFFFFu);
-            }
-        }
-    });
-    // sortDBSeqLists: every list by (seqId, position); one entry per (k-mer, target), so seqId alone decides
-    parallel_for(table, [&](size_t a, size_t b) {
-        std::vector<uint64_t> tmp;
-        for (size_t z = a; z < b; z++) {
-            const uint64_t o0 = offsets[z], o1 = offsets[z + 1];
-            if (o1 - o0 < 2) continue;
-            tmp.resize(o1 - o0);
-            for (uint64_t e = o0; e < o1; e++) tmp[e - o0] = ((uint64_t)ids[e] << 16) | pos[e];
-            std::sort(tmp.begin(), tmp.end());
-            for (uint64_t e = o0; e < o1; e++) {
-                ids[e] = (uint32_t)(tmp[e - o0] >> 16);
-                pos[e] = (uint16_t)(tmp[e - o0] & 0xFFFFu);
-            }
-        }
-    });
-    return MMGPU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// tables every QueryMatcher gets (score matrices, cumulative counts, ungapped matrix): shared by the two ways of
-// obtaining the index (host arrays / built in HBM).  `from_host` = validate and copy the host index as well.
-static int pf_setup(mmgpu_ctx *c, const mmgpu_pf_index *ix, bool from_host, std::unique_ptr<PfIndex> &out) {
-    if (!c || !ix) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: NULL argument");
-    if (!c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_pf_load_index: load the targets (SequenceLookup) first");
-    const bool tables = ix->score3 != nullptr && ix->index3 != nullptr;    // without them: exact k-mer matching only
-    if (tables && (ix->kmer_size < 5 || ix->kmer_size > 7)) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_load_index: similar k-mers need k = 5, 6 or 7");
-    if (ix->kmer_size < 4 || ix->kmer_size > 15) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_load_index: k must be in [4, 15]");
-    if (tables && ix->kmer_size != 6 && (!ix->score2 || !ix->index2)) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: k = 5 and k = 7 need the 2-mer ScoreMatrix");
-    if (ix->alphabet != c->db.alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: alphabet differs from the loaded targets");
-    if (ix->alphabet < 2 || ix->alphabet > 32) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: alphabet must be in [2, 32]");
-    if (!ix->ungapped_mat) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: NULL table");
-    const int kbase = (from_host && ix->kmer_alphabet > 0) ? ix->kmer_alphabet : ix->alphabet - 1;
-    if (kbase < ix->alphabet - 1 || kbase > ix->alphabet) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: kmer_alphabet must be alphabet - 1 or alphabet");
-    {
-        double tb = 1;
-        for (int i = 0; i < ix->kmer_size; i++) tb *= (double)kbase;
-        if (tb > 2147483648.0) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_load_index: more than 2^31 k-mers");
-    }
-    if (from_host) {
-        if (!ix->offsets) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: NULL table");
-        if (!ix->entries6 && !(ix->entry_ids && ix->entry_pos) && ix->n_entries) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: no index entries");
-        if (ix->n_entries >= 0xFFFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_load_index: >= 2^32 index entries per shard");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    pf_index_free(c);
-    std::unique_ptr<PfIndex> P(new PfIndex());
-    P->k = ix->kmer_size;
-    P->alphabet = ix->alphabet;
-    P->kalph = ix->alphabet - 1;
-    P->kbase = kbase;
-    P->spaced = ix->spaced;
-    P->pattern_len = window_pattern(P->k, P->spaced, P->pat);
-    P->n3 = (uint32_t)(P->kalph * P->kalph * P->kalph);
-    P->table = 1;
-    for (int i = 0; i < P->k; i++) P->table *= (uint64_t)P->kbase;
-    P->n_entries = from_host ? ix->n_entries : 0;
-    P->has_tables = tables;
-    const size_t n3 = P->n3;
-    if (tables && ix->row3 < n3) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: row3 smaller than kalph^3");
-    if (tables) {
-        HIP_TRY(P->d_s3.alloc(n3 * n3 * sizeof(int16_t)));
-        HIP_TRY(P->d_i3.alloc(n3 * n3 * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy2D(P->d_s3.p, n3 * sizeof(int16_t), ix->score3, ix->row3 * sizeof(int16_t), n3 * sizeof(int16_t), n3, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy2D(P->d_i3.p, n3 * sizeof(uint32_t), ix->index3, ix->row3 * sizeof(uint32_t), n3 * sizeof(uint32_t), n3, hipMemcpyHostToDevice));
-    }
-    // cumulative counts per row: #entries with score >= c is one lookup instead of a binary search in the row
-    auto build_cum = [&](const int16_t *score, size_t row_stride, size_t n, DevBuf &dst, uint32_t *w_out, int32_t *min_out) -> int {
-        int lo = 32767, hi = -32768;
-        for (size_t r = 0; r < n; r++) {
-            lo = std::min<int>(lo, score[r * row_stride + n - 1]);
-            hi = std::max<int>(hi, score[r * row_stride]);
-        }
-        const uint32_t w = (uint32_t)(hi - lo + 2);
-        std::vector<uint16_t> cum(n * (size_t)w);
-        for (size_t r = 0; r < n; r++) {
-            const int16_t *row = score + r * row_stride;
-            for (size_t z = 1; z < n; z++)
-                if (row[z] > row[z - 1]) return 1;
-            size_t j = 0;   // rows are sorted descending: walk thresholds from high to low
-            for (int k = (int)w - 1; k >= 0; k--) {
-                const int c = lo + k;
-                while (j < n && row[j] >= c) j++;
-                cum[r * w + (size_t)k] = (uint16_t)j;
-            }
-        }
-        if (upload(dst, cum, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 2;
-        *w_out = w;
-        *min_out = lo;
-        return 0;
-    };
-    if (tables) {
-        const int rc = build_cum(ix->score3, ix->row3, n3, P->d_cum3, &P->cum_w, &P->score_min);
-        if (rc) return fail(rc == 1 ? MMGPU_ERR_ARG : MMGPU_ERR_HIP, rc == 1 ? "mmgpu_pf_load_index: score3 rows are not sorted by descending score" : "mmgpu_pf_load_index: upload failed");
-    }
-    if (tables && P->k != 6) {      // k = 5: (2, 3), k = 7: (2, 2, 3) - KmerGenerator::setDivideStrategy
-        const size_t n2 = (size_t)P->kalph * P->kalph;
-        if (ix->row2 < n2) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: row2 smaller than kalph^2");
-        HIP_TRY(P->d_s2.alloc(n2 * n2 * sizeof(int16_t)));
-        HIP_TRY(P->d_i2.alloc(n2 * n2 * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy2D(P->d_s2.p, n2 * sizeof(int16_t), ix->score2, ix->row2 * sizeof(int16_t), n2 * sizeof(int16_t), n2, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy2D(P->d_i2.p, n2 * sizeof(uint32_t), ix->index2, ix->row2 * sizeof(uint32_t), n2 * sizeof(uint32_t), n2, hipMemcpyHostToDevice));
-        const int rc = build_cum(ix->score2, ix->row2, n2, P->d_cum2, &P->cum2_w, &P->score2_min);
-        if (rc) return fail(rc == 1 ? MMGPU_ERR_ARG : MMGPU_ERR_HIP, rc == 1 ? "mmgpu_pf_load_index: score2 rows are not sorted by descending score" : "mmgpu_pf_load_index: upload failed");
-    }
-    if (from_host) {
-        {
-            std::vector<uint32_t> off32(P->table + 1);
-            std::atomic<bool> bad_off(false);
-            parallel_for((size_t)P->table + 1, [&](size_t a, size_t b) {
-                for (size_t z = a; z < b; z++) {
-                    if (ix->offsets[z] > ix->n_entries || (z && ix->offsets[z] < ix->offsets[z - 1])) bad_off = true;
-                    off32[z] = (uint32_t)ix->offsets[z];
-                }
-            });
-            if (bad_off) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: offsets not monotone / out of range");
-            HIP_TRY(upload(P->d_offsets, off32, nullptr));
-            HIP_TRY(hipDeviceSynchronize());
-        }
-        {
-            const size_t ne = (size_t)ix->n_entries;
-            std::vector<uint64_t> ent(std::max<size_t>(ne, 1));
-            const uint8_t *e6 = (const uint8_t *)ix->entries6;
-            std::atomic<bool> bad_ent(false);
-            const uint32_t ntargets = c->db.n;
-            parallel_for(ne, [&](size_t a, size_t b) {
-                for (size_t e = a; e < b; e++) {
-                    uint32_t id;
-                    uint16_t pj;
-                    if (ix->entry_ids) {
-                        id = ix->entry_ids[e];
-                        pj = ix->entry_pos[e];
-                    } else {
-                        memcpy(&id, e6 + e * 6, 4);
-                        memcpy(&pj, e6 + e * 6 + 4, 2);
-                    }
-                    if (id >= ntargets) bad_ent = true;
-                    ent[e] = (uint64_t)id | ((uint64_t)pj << 32);
-                }
-            });
-            if (bad_ent) return fail(MMGPU_ERR_ARG, "mmgpu_pf_load_index: index entry names a target that is not loaded");
-            HIP_TRY(upload(P->d_entries, ent, nullptr));
-            HIP_TRY(hipDeviceSynchronize());
-        }
-    }
-    P->h_mat.assign(ix->ungapped_mat, ix->ungapped_mat + ix->alphabet * ix->alphabet);
-    HIP_TRY(upload(P->d_mat, P->h_mat, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    out = std::move(P);
-    return MMGPU_OK;
-}
-
-
-extern "C" int mmgpu_pf_load_index(mmgpu_ctx *c, const mmgpu_pf_index *ix) {
-    std::unique_ptr<PfIndex> P;
-    const int rc = pf_setup(c, ix, true, P);
-    if (rc != MMGPU_OK) return rc;
-    HIP_TRY(pf_index_bitmap(c, P.get()));
-    HIP_TRY(pf_index_cofs(c, P.get()));
-    c->pf = P.release();
-    return MMGPU_OK;
-}
-
-// IndexBuilder::fillDatabase on the device (ix_kernels.hip): count, scan, scatter, sort every list by seqId.
-extern "C" int mmgpu_pf_build_index(mmgpu_ctx *c, const mmgpu_pf_index *ix, const int16_t *kmer_submat, int kmer_thr) {
-    if (!kmer_submat) return fail(MMGPU_ERR_ARG, "mmgpu_pf_build_index: NULL argument");
-    std::unique_ptr<PfIndex> P;
-    const int rc = pf_setup(c, ix, false, P);
-    if (rc != MMGPU_OK) return rc;
-    hipStream_t s = c->stream;
-    const uint64_t table = P->table;
-    if (table >= 0xFFFFFFF0ull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_build_index: k-mer table too large");
-    DevBuf d_counts, d_scratch, d_chunk_off, d_chunk_tot, d_chunk_base, d_tmp, d_long, d_nlong;
-    HIP_TRY(d_counts.alloc(table * 4));
-    HIP_TRY(P->d_offsets.alloc((table + 1) * 4));
-    HIP_TRY(hipMemsetAsync(d_counts.p, 0, table * 4, s));
-    IxArgs A;
-    memset(&A, 0, sizeof(A));
-    A.t_res = c->pf_res();
-    A.t_off4 = c->db.off4;
-    A.t_len = c->db.len;
-    A.n_targets = c->db.n;
-    A.k = P->k;
-    A.pattern_len = P->pattern_len;
-    A.kmer_thr = kmer_thr;
-    A.kalph = (uint32_t)P->kalph;
-    memcpy(A.pat, P->pat, sizeof(A.pat));
-    for (int a = 0; a < P->alphabet && a < 32; a++) A.self_score[a] = (int8_t)(char)kmer_submat[a * P->alphabet + a];
-    A.counts = d_counts.as<uint32_t>();
-    if ((int)c->db.max_len - P->pattern_len + 1 > 4096) {
-        // one uint32 per residue slot of the packed target array
-        uint64_t slots = 0;
-        for (uint32_t l : c->h_len) slots += ((uint64_t)l + 3) / 4 * 4;
-        HIP_TRY(d_scratch.alloc((slots + 64) * 4));
-    }
-    A.scratch = d_scratch.as<uint32_t>();
-    HIP_TRY(launch_ix_target(A, false, s));
-    // offsets = exclusive scan of the counts: 64 K chunks, chunk totals summed on the host
-    const uint32_t CH = 65536;
-    const uint32_t nch = (uint32_t)((table + CH - 1) / CH);
-    std::vector<uint32_t> choff(nch + 1);
-    for (uint32_t z = 0; z <= nch; z++) choff[z] = (uint32_t)std::min<uint64_t>((uint64_t)z * CH, table);
-    std::vector<uint64_t> chtot(nch), chbase(nch);
-    HIP_TRY(upload(d_chunk_off, choff, s));
-    HIP_TRY(d_chunk_tot.alloc((size_t)nch * 8));
-    HIP_TRY(d_chunk_base.alloc((size_t)nch * 8));
-    HIP_TRY(launch_pf_scan(d_counts.as<uint32_t>(), d_chunk_off.as<uint32_t>(), nch, nullptr, nullptr, d_chunk_tot.as<uint64_t>(), s));
-    HIP_TRY(hipMemcpyAsync(chtot.data(), d_chunk_tot.p, (size_t)nch * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    uint64_t run = 0;
-    for (uint32_t z = 0; z < nch; z++) { chbase[z] = run; run += chtot[z]; }
-    if (run >= 0xFFFFFFFFull) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_pf_build_index: >= 2^32 index entries per shard");
-    P->n_entries = run;
-    HIP_TRY(hipMemcpyAsync(d_chunk_base.p, chbase.data(), (size_t)nch * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_pf_scan(d_counts.as<uint32_t>(), d_chunk_off.as<uint32_t>(), nch, d_chunk_base.as<uint64_t>(), P->d_offsets.as<uint32_t>(), nullptr, s));
-    HIP_TRY(d_tmp.alloc(std::max<uint64_t>(run, 1) * 8));
-    HIP_TRY(P->d_entries.alloc(std::max<uint64_t>(run, 1) * 8));
-    HIP_TRY(hipMemsetAsync(d_counts.p, 0, table * 4, s));
-    A.offsets = P->d_offsets.as<uint32_t>();
-    A.entries = d_tmp.as<uint64_t>();
-    HIP_TRY(launch_ix_target(A, true, s));
-    IxSortArgs S;
-    S.table = table;
-    S.offsets = P->d_offsets.as<uint32_t>();
-    S.src = d_tmp.as<uint64_t>();
-    S.dst = P->d_entries.as<uint64_t>();
-    S.long_cap = (uint32_t)(run / 17 + 1);
-    HIP_TRY(d_long.alloc((size_t)S.long_cap * 4));
-    HIP_TRY(d_nlong.alloc(4));
-    HIP_TRY(hipMemsetAsync(d_nlong.p, 0, 4, s));
-    S.long_lists = d_long.as<uint32_t>();
-    S.n_long = d_nlong.as<uint32_t>();
-    HIP_TRY(launch_ix_sort_short(S, s));
-    uint32_t n_long = 0;
-    HIP_TRY(hipMemcpyAsync(&n_long, d_nlong.p, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(launch_ix_sort_long(S, std::min(n_long, S.long_cap), s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(pf_index_bitmap(c, P.get()));
-    HIP_TRY(pf_index_cofs(c, P.get()));
-    c->pf = P.release();
-    return MMGPU_OK;
-}
-
-// test hook: the resident index as the host builder would return it
-extern "C" int mmgpu_pf_debug_index(mmgpu_ctx *c, uint64_t *offsets, uint32_t *ids, uint16_t *pos, uint64_t *n_entries) {
-    if (!c || !c->pf || !n_entries) return fail(MMGPU_ERR_ARG, "mmgpu_pf_debug_index: no index");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const PfIndex &P = *c->pf;
-    *n_entries = P.n_entries;
-    if (offsets) {
-        std::vector<uint32_t> o(P.table + 1);
-        HIP_TRY(hipMemcpy(o.data(), P.d_offsets.p, (P.table + 1) * 4, hipMemcpyDeviceToHost));
-        for (uint64_t z = 0; z <= P.table; z++) offsets[z] = o[z];
-    }
-    if (ids && pos && P.n_entries) {
-        std::vector<uint64_t> e(P.n_entries);
-        HIP_TRY(hipMemcpy(e.data(), P.d_entries.p, P.n_entries * 8, hipMemcpyDeviceToHost));
-        for (uint64_t z = 0; z < P.n_entries; z++) { ids[z] = (uint32_t)e[z]; pos[z] = (uint16_t)(e[z] >> 32); }
-    }
-    return MMGPU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
 struct mmgpu_pf_batch_t {
     mmgpu_pf_params par;
     uint32_t nq = 0, n_pos = 0;
@@ -1845,308 +1325,6 @@ extern "C" int mmgpu_pf_debug_fetch(mmgpu_ctx *c, mmgpu_pf_batch_t *b, int what,
     *bytes = n;
     const size_t m = std::min(n, cap);
     if (dst && m) HIP_TRY(hipMemcpy(dst, src, m, hipMemcpyDeviceToHost));
-    return MMGPU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Persisted device layout.  The reference prepares a database for its GPU path ahead of time
-// (`makepaddedseqdb`, src/util/makepaddedseqdb.cpp: sequences padded and ordered for the device) and keeps precomputed prefilter
-// indexes on disk (`createindex`; PrefilteringIndexReader.cpp reads them back).  Here it is ONE file with what a context has
-// resident, in the layout it has on the device: targets (4-byte aligned residues, offsets, lengths), the prefilter's masked view
-// when there is one, and the k-mer index (uint32 offsets, 8-byte entries).  mmgpu_db_load brings it back without the host
-// touching a sequence: no SequenceLookup fill, no masking, no index build.  What is NOT in the file: the similar-k-mer score
-// tables (they belong to the matrix, the caller hands them over as for mmgpu_pf_build_index) and anything derived on the device in
-// milliseconds (compact offset table, non-empty bit table).
-namespace {
-
-struct DbFileHeader {
-    char magic[8];                 // "MMGPUDB1"
-    uint32_t version, header_bytes;
-    uint64_t source_fp, index_fp;  // the caller's fingerprints: of the source database; of what the index depends on beyond it
-    uint32_t n, alphabet, max_len, mean_len;
-    uint64_t total_residues, res_bytes;
-    uint32_t has_masked, has_index;
-    int32_t k, spaced, kbase, pad0;
-    uint64_t table, n_entries;
-    uint64_t at_off4, at_len, at_res, at_masked, at_offsets, at_entries, file_bytes;
-    uint64_t sum[6];               // version 2: checksum of every section (db_kernels.hip), in the order of the at_ fields
-};
-constexpr uint32_t DB_VERSION = 2;
-static const char DB_MAGIC[8] = {'M', 'M', 'G', 'P', 'U', 'D', 'B', '1'};
-
-static uint64_t align4k(uint64_t x) { return (x + 4095ull) & ~4095ull; }
-
-// device -> file, through a pinned staging buffer
-static int write_section(FILE *f, uint64_t at, const void *dev, size_t bytes) {
-    if (fseeko(f, (off_t)at, SEEK_SET) != 0) return fail(MMGPU_ERR_ARG, "mmgpu_db_save: seek failed");
-    const size_t chunk = 64ull << 20;
-    PinnedStage stage;
-    HIP_TRY(stage.reserve(std::min(chunk, std::max<size_t>(bytes, 1)), false));
-    for (size_t o = 0; o < bytes; o += chunk) {
-        const size_t m = std::min(chunk, bytes - o);
-        if (hipMemcpy(stage.p, static_cast<const uint8_t *>(dev) + o, m, hipMemcpyDeviceToHost) != hipSuccess) return fail(MMGPU_ERR_HIP, "mmgpu_db_save: device read failed");
-        if (fwrite(stage.p, 1, m, f) != m) return fail(MMGPU_ERR_ARG, "mmgpu_db_save: write failed (disk full?)");
-    }
-    return MMGPU_OK;
-}
-
-// file -> device: DB_READERS host threads, each with a pinned buffer of its own, take the chunks of a section in turn - pread (the
-// kernel copies out of the page cache, no fault per page as through a mapping), then the copy engine moves the chunk while the
-// thread reads its next one.  (One thread per chunk, not all threads on every chunk: starting 64 threads for each 32 MB chunk was
-// most of the 0.24 s the 2.97 GB of a 1 M-target database took.)
-constexpr int DB_READERS = 8;
-constexpr size_t DB_CHUNK = 16ull << 20;
-static int upload_section(int device, void *dev, int fd, uint64_t at, size_t bytes, const UploadRing &ring) {
-    const size_t n_chunks = (bytes + DB_CHUNK - 1) / DB_CHUNK;
-    std::atomic<int> bad{0};
-    auto reader = [&](int t) {
-        if (hipSetDevice(device) != hipSuccess) { bad = 2; return; }
-        for (size_t j = (size_t)t; j < n_chunks && !bad; j += DB_READERS) {
-            const size_t o = j * DB_CHUNK, m = std::min(DB_CHUNK, bytes - o);
-            if (ring.wait((size_t)t) != hipSuccess) { bad = 2; return; }
-            uint8_t *stage = ring.slots[(size_t)t].p;
-            for (size_t a = 0; a < m;) {
-                const ssize_t got = pread(fd, stage + a, m - a, (off_t)(at + o + a));
-                if (got <= 0) { bad = 1; return; }
-                a += (size_t)got;
-            }
-            if (hipMemcpyAsync(static_cast<uint8_t *>(dev) + o, stage, m, hipMemcpyHostToDevice, ring.up.s) != hipSuccess ||
-                ring.sent((size_t)t) != hipSuccess) { bad = 2; return; }
-        }
-    };
-    const int nt = (int)std::min<size_t>(DB_READERS, n_chunks);
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(reader, t);
-    if (nt > 0) reader(0);
-    for (auto &x : th) x.join();
-    if (bad == 1) return fail(MMGPU_ERR_STATE, "mmgpu_db_load: short read (file truncated?)");
-    if (bad) return fail(MMGPU_ERR_HIP, "mmgpu_db_load: upload failed");
-    return MMGPU_OK;
-}
-
-}  // namespace
-
-extern "C" int mmgpu_db_save(mmgpu_ctx *c, const char *path, uint64_t source_fingerprint, uint64_t index_fingerprint) {
-    if (!c || !path) return fail(MMGPU_ERR_ARG, "mmgpu_db_save: NULL argument");
-    if (!c->db.res) return fail(MMGPU_ERR_STATE, "mmgpu_db_save: no targets loaded");
-    if (c->shard.on) return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_db_save: the context holds a shard of a multi-GPU run (save the unsplit database)");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const PfIndex *P = c->pf;
-    const bool with_index = P != nullptr && index_fingerprint != 0 && P->d_offsets.p && P->kbase == P->kalph;
-    DbFileHeader h;
-    memset(&h, 0, sizeof(h));
-    memcpy(h.magic, DB_MAGIC, 8);
-    h.version = DB_VERSION;
-    h.header_bytes = (uint32_t)sizeof(h);
-    h.source_fp = source_fingerprint;
-    h.index_fp = with_index ? index_fingerprint : 0;
-    h.n = c->db.n;
-    h.alphabet = (uint32_t)c->db.alphabet;
-    h.max_len = c->db.max_len;
-    h.mean_len = c->mean_len;
-    h.total_residues = c->db.total_residues;
-    h.res_bytes = c->db.res_bytes;
-    h.has_masked = c->pf_masked_res ? 1u : 0u;
-    h.has_index = with_index ? 1u : 0u;
-    const size_t nn = std::max<uint32_t>(c->db.n, 1);
-    uint64_t at = align4k(sizeof(h));
-    h.at_off4 = at; at = align4k(at + nn * 4);
-    h.at_len = at; at = align4k(at + nn * 4);
-    h.at_res = at; at = align4k(at + h.res_bytes);
-    if (h.has_masked) { h.at_masked = at; at = align4k(at + h.res_bytes); }
-    if (with_index) {
-        h.k = P->k; h.spaced = P->spaced; h.kbase = P->kbase;
-        h.table = P->table; h.n_entries = P->n_entries;
-        h.at_offsets = at; at = align4k(at + (P->table + 1) * 4);
-        h.at_entries = at; at = align4k(at + std::max<uint64_t>(P->n_entries, 1) * 8);
-    }
-    h.file_bytes = at;
-    {   // the sections' checksums, taken where they lie
-        DevBuf d_sum;
-        HIP_TRY(d_sum.alloc(8));
-        unsigned long long *sc = d_sum.as<unsigned long long>();
-        HIP_TRY(db_section_checksum(c->db.off4, nn * 4, sc, &h.sum[0], c->stream));
-        HIP_TRY(db_section_checksum(c->db.len, nn * 4, sc, &h.sum[1], c->stream));
-        HIP_TRY(db_section_checksum(c->db.res, h.res_bytes, sc, &h.sum[2], c->stream));
-        if (h.has_masked) HIP_TRY(db_section_checksum(c->pf_masked_res, h.res_bytes, sc, &h.sum[3], c->stream));
-        if (with_index) {
-            HIP_TRY(db_section_checksum(P->d_offsets.p, (P->table + 1) * 4, sc, &h.sum[4], c->stream));
-            HIP_TRY(db_section_checksum(P->d_entries.p, P->n_entries * 8, sc, &h.sum[5], c->stream));
-        }
-    }
-    const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) return fail(MMGPU_ERR_ARG, std::string("mmgpu_db_save: cannot create ") + tmp);
-    int rc = MMGPU_OK;
-    if (fwrite(&h, sizeof(h), 1, f) != 1) rc = fail(MMGPU_ERR_ARG, "mmgpu_db_save: write failed");
-    if (rc == MMGPU_OK) rc = write_section(f, h.at_off4, c->db.off4, nn * 4);
-    if (rc == MMGPU_OK) rc = write_section(f, h.at_len, c->db.len, nn * 4);
-    if (rc == MMGPU_OK) rc = write_section(f, h.at_res, c->db.res, h.res_bytes);
-    if (rc == MMGPU_OK && h.has_masked) rc = write_section(f, h.at_masked, c->pf_masked_res, h.res_bytes);
-    if (rc == MMGPU_OK && with_index) rc = write_section(f, h.at_offsets, P->d_offsets.p, (P->table + 1) * 4);
-    if (rc == MMGPU_OK && with_index && P->n_entries) rc = write_section(f, h.at_entries, P->d_entries.p, P->n_entries * 8);
-    if (rc == MMGPU_OK && (ftruncate(fileno(f), (off_t)h.file_bytes) != 0)) rc = fail(MMGPU_ERR_ARG, "mmgpu_db_save: cannot size the file");
-    if (fclose(f) != 0 && rc == MMGPU_OK) rc = fail(MMGPU_ERR_ARG, "mmgpu_db_save: close failed");
-    if (rc == MMGPU_OK && rename(tmp.c_str(), path) != 0) rc = fail(MMGPU_ERR_ARG, std::string("mmgpu_db_save: cannot rename to ") + path);
-    if (rc != MMGPU_OK) (void)remove(tmp.c_str());
-    return rc;
-}
-
-static int db_read_header(const char *path, DbFileHeader *h, int *fd_out) {
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return fail(MMGPU_ERR_STATE, std::string("mmgpu_db: cannot open ") + path);
-    struct stat st;
-    bool ok = read(fd, h, sizeof(*h)) == (ssize_t)sizeof(*h) && memcmp(h->magic, DB_MAGIC, 8) == 0 && h->version == DB_VERSION &&
-              h->header_bytes == sizeof(*h) && fstat(fd, &st) == 0 && (uint64_t)st.st_size >= h->file_bytes;
-    // every section inside the file (sizes that cannot overflow the sums first)
-    auto inside = [&](uint64_t at, uint64_t bytes) { return at >= sizeof(*h) && bytes <= h->file_bytes && at <= h->file_bytes - bytes; };
-    if (ok) {
-        const uint64_t nn = std::max<uint32_t>(h->n, 1);
-        ok = h->table < (1ull << 40) && h->n_entries < (1ull << 40) && h->alphabet >= 1 && h->alphabet <= 255 &&
-             inside(h->at_off4, nn * 4) && inside(h->at_len, nn * 4) && inside(h->at_res, h->res_bytes) &&
-             (!h->has_masked || inside(h->at_masked, h->res_bytes)) &&
-             (!h->has_index || (inside(h->at_offsets, (h->table + 1) * 4) && inside(h->at_entries, h->n_entries * 8)));
-    }
-    if (!ok) {
-        close(fd);
-        return fail(MMGPU_ERR_STATE, std::string("mmgpu_db: not a database file of this library version: ") + path);
-    }
-    if (fd_out) *fd_out = fd; else close(fd);
-    return MMGPU_OK;
-}
-
-extern "C" int mmgpu_db_probe(const char *path, mmgpu_db_info *info) {
-    if (!path || !info) return fail(MMGPU_ERR_ARG, "mmgpu_db_probe: NULL argument");
-    DbFileHeader h;
-    const int rc = db_read_header(path, &h, nullptr);
-    if (rc != MMGPU_OK) return rc;
-    memset(info, 0, sizeof(*info));
-    info->source_fingerprint = h.source_fp;
-    info->index_fingerprint = h.index_fp;
-    info->n_targets = h.n;
-    info->alphabet = h.alphabet;
-    info->total_residues = h.total_residues;
-    info->has_masked_view = (int32_t)h.has_masked;
-    info->has_index = (int32_t)h.has_index;
-    info->kmer_size = h.k;
-    info->spaced = h.spaced;
-    info->n_entries = h.n_entries;
-    info->file_bytes = h.file_bytes;
-    return MMGPU_OK;
-}
-
-extern "C" int mmgpu_db_load(mmgpu_ctx *c, const char *path, uint64_t source_fingerprint, uint64_t index_fingerprint, const mmgpu_pf_index *tables) {
-    if (!c || !path) return fail(MMGPU_ERR_ARG, "mmgpu_db_load: NULL argument");
-    DbFileHeader h;
-    int fd = -1;
-    int rc = db_read_header(path, &h, &fd);
-    if (rc != MMGPU_OK) return rc;
-    if (h.source_fp != source_fingerprint) { close(fd); return fail(MMGPU_ERR_STATE, "mmgpu_db_load: the file was made from another database (source fingerprint differs)"); }
-    const bool want_index = index_fingerprint != 0;
-    if (want_index && (!h.has_index || h.index_fp != index_fingerprint)) { close(fd); return fail(MMGPU_ERR_STATE, "mmgpu_db_load: the file holds no index built with these parameters (index fingerprint differs)"); }
-    if (want_index && !tables) { close(fd); return fail(MMGPU_ERR_ARG, "mmgpu_db_load: the index needs the caller's score tables"); }
-    if (want_index && (tables->kmer_size != h.k || tables->spaced != h.spaced || tables->alphabet != (int)h.alphabet)) { close(fd); return fail(MMGPU_ERR_STATE, "mmgpu_db_load: k-mer size / pattern / alphabet differ from the file's index"); }
-    struct CloseFd { int fd; ~CloseFd() { close(fd); } } closer{fd};
-    HIP_TRY(hipSetDevice(c->device));
-    // (what the context holds stays until the file's content has been uploaded and checked: a file that turns out damaged leaves
-    // the context as it was)
-    const size_t nn = std::max<uint32_t>(h.n, 1);
-    DbBuild nb;
-    std::unique_ptr<PfIndex> P;
-    UploadRing ring;      // (last: its stream has drained before a failure frees what it copies into)
-    DeviceDb &db = nb.db;
-    HIP_TRY(ring.open(DB_READERS));
-    for (PinnedStage &x : ring.slots) HIP_TRY(x.reserve(DB_CHUNK));
-    hipStream_t up = ring.up.s;
-    HIP_TRY(dev_malloc_ctx(c, (void **)&db.res, (size_t)h.res_bytes));
-    HIP_TRY(dev_malloc_ctx(c, (void **)&db.off4, nn * 4));
-    HIP_TRY(dev_malloc_ctx(c, (void **)&db.len, nn * 4));
-    if (int e = upload_section(c->device, db.off4, fd, h.at_off4, nn * 4, ring)) return e;
-    if (int e = upload_section(c->device, db.len, fd, h.at_len, nn * 4, ring)) return e;
-    if (int e = upload_section(c->device, db.res, fd, h.at_res, (size_t)h.res_bytes, ring)) return e;
-    if (h.has_masked && want_index) {      // (the masked view serves the prefilter only: a caller that asks for the targets alone gets them alone)
-        HIP_TRY(dev_malloc_ctx(c, (void **)&nb.masked, (size_t)h.res_bytes));
-        if (int e = upload_section(c->device, nb.masked, fd, h.at_masked, (size_t)h.res_bytes, ring)) return e;
-    }
-    db.n = h.n;
-    db.res_bytes = (size_t)h.res_bytes;
-    db.max_len = h.max_len;
-    db.total_residues = h.total_residues;
-    db.alphabet = (int)h.alphabet;
-    std::vector<uint32_t> hlen(h.n);
-    if (h.n && pread(fd, hlen.data(), (size_t)h.n * 4, (off_t)h.at_len) != (ssize_t)((size_t)h.n * 4)) return fail(MMGPU_ERR_STATE, "mmgpu_db_load: short read (file truncated?)");
-    HIP_TRY(hipStreamSynchronize(up));
-    // what arrived is what was saved, and it has the properties the kernels rely on
-    DevBuf d_chk;
-    HIP_TRY(d_chk.alloc(8));
-    auto section_ok = [&](const void *dev, size_t bytes, int which) {
-        uint64_t sum = 0;
-        return db_section_checksum(dev, bytes, d_chk.as<unsigned long long>(), &sum, up) == hipSuccess && sum == h.sum[which];
-    };
-    if (!section_ok(db.off4, nn * 4, 0) || !section_ok(db.len, nn * 4, 1) || !section_ok(db.res, (size_t)h.res_bytes, 2) ||
-        (nb.masked && !section_ok(nb.masked, (size_t)h.res_bytes, 3)))
-        return fail(MMGPU_ERR_STATE, "mmgpu_db_load: a section's checksum differs from the one in the header (damaged file)");
-    {
-        uint32_t bad = 0;
-        HIP_TRY(db_validate_layout(db.off4, db.len, h.n, h.res_bytes, h.max_len, nullptr, 0, nullptr, 0, d_chk.as<uint32_t>(), &bad, up));
-        if (bad) return fail(MMGPU_ERR_STATE, "mmgpu_db_load: a target of the file lies outside its residue block");
-    }
-    // the context takes the new database (pf_setup checks the alphabet against it); the old one is kept aside until the index is in
-    DeviceDb old_db = c->db;
-    uint8_t *old_masked = c->pf_masked_res;
-    PfIndex *old_pf = c->pf;
-    std::vector<uint32_t> old_hlen;
-    old_hlen.swap(c->h_len);
-    const uint32_t old_mean = c->mean_len;
-    const bool old_shard = c->shard.on;
-    c->pf = nullptr;
-    c->shard.on = false;
-    c->db = nb.take_db();
-    c->pf_masked_res = nb.take_masked();
-    c->h_len.swap(hlen);
-    c->mean_len = h.mean_len;
-    auto back_to_old = [&](int rc) {      // (the index failed: the new database goes, the old one is the context's again)
-        (void)hipStreamSynchronize(up);   // (an upload of the index that failed half-way may have copies in flight)
-        db_release(c);
-        c->db = old_db;
-        c->pf_masked_res = old_masked;
-        c->pf = old_pf;
-        c->h_len.swap(old_hlen);
-        c->mean_len = old_mean;
-        c->shard.on = old_shard;
-        return rc;
-    };
-    if (want_index) {
-        int rc2 = pf_setup(c, tables, false, P);
-        if (rc2 == MMGPU_OK && (P->table != h.table || P->kbase != h.kbase)) rc2 = fail(MMGPU_ERR_STATE, "mmgpu_db_load: k-mer table size differs from the file's index");
-        if (rc2 != MMGPU_OK) return back_to_old(rc2);
-        P->n_entries = h.n_entries;
-        hipError_t e = P->d_offsets.alloc((P->table + 1) * 4);
-        if (e == hipSuccess) e = P->d_entries.alloc(std::max<uint64_t>(P->n_entries, 1) * 8);
-        int rc3 = e == hipSuccess ? MMGPU_OK : fail(MMGPU_ERR_HIP, "mmgpu_db_load: out of device memory for the index");
-        if (rc3 == MMGPU_OK) rc3 = upload_section(c->device, P->d_offsets.p, fd, h.at_offsets, (P->table + 1) * 4, ring);
-        if (rc3 == MMGPU_OK && P->n_entries) rc3 = upload_section(c->device, P->d_entries.p, fd, h.at_entries, P->n_entries * 8, ring);
-        if (rc3 == MMGPU_OK && hipStreamSynchronize(up) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: upload failed");
-        if (rc3 == MMGPU_OK && (!section_ok(P->d_offsets.p, (P->table + 1) * 4, 4) || !section_ok(P->d_entries.p, P->n_entries * 8, 5)))
-            rc3 = fail(MMGPU_ERR_STATE, "mmgpu_db_load: the index's checksum differs from the one in the header (damaged file)");
-        if (rc3 == MMGPU_OK) {
-            uint32_t bad = 0;
-            if (db_validate_layout(c->db.off4, c->db.len, h.n, h.res_bytes, h.max_len, P->d_offsets.as<uint32_t>(), P->table, P->d_entries.as<uint64_t>(),
-                                   P->n_entries, d_chk.as<uint32_t>(), &bad, up) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: layout check failed");
-            else if (bad) rc3 = fail(MMGPU_ERR_STATE, "mmgpu_db_load: the file's index is not a k-mer index over these targets (offsets not monotone / entry out of range)");
-        }
-        if (rc3 == MMGPU_OK && pf_index_bitmap(c, P.get()) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: bit table failed");
-        if (rc3 == MMGPU_OK && pf_index_cofs(c, P.get()) != hipSuccess) rc3 = fail(MMGPU_ERR_HIP, "mmgpu_db_load: compact offset table failed");
-        if (rc3 != MMGPU_OK) return back_to_old(rc3);
-        c->pf = P.release();
-    }
-    {   // the old database goes
-        (void)hipStreamSynchronize(c->stream);
-        dev_free(old_db.res); dev_free(old_db.off4); dev_free(old_db.len);
-        if (old_masked) dev_free(old_masked);
-        delete old_pf;
-    }
     return MMGPU_OK;
 }
 

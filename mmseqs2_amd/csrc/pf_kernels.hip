@@ -56,7 +56,7 @@ struct __attribute__((packed, aligned(4))) U32Quad {
 // One aligned request answers (start, length); what matters is the footprint of a work group's look-ups (pf_order.hip): a stretch
 // of 8000 k-mers is ~10 KB instead of 32 KB, ~90 stretches per 3-mer group fit an XCD's L2 several groups over.  A block with a
 // list of 255 entries or more has bit 31 of its base set: its k-mers are answered by the full table (databases of 2^31 index
-// entries or more keep to the full table altogether, pf_api.hip).  Block size: 16 bytes = base + 12 lengths - ONE dwordx4 load
+// entries or more keep to the full table altogether, pf_index_api.hip).  Block size: 16 bytes = base + 12 lengths - ONE dwordx4 load
 // per look-up (a wavefront's 64 look-ups are 64 different lines: the address unit takes a clock per lane and instruction, so the
 // 32-byte form - base + 28 lengths, two loads, MMGPU_PF_COFS32 - pays that twice for 15 % less footprint;
 // profiles/r05_exp_pf_cofs_block.txt).

@@ -97,13 +97,6 @@ def test_saved_database_answers_like_the_resident_one(gpu, matrices, oracle, tmp
         for k in (0, 7, 39):
             r = oracle.sw_align(q, None, tl[k], mat, 11, 1, need_start=True)
             assert (int(b[k]["score"]), int(b[k]["q_end"]), int(b[k]["t_end"])) == (r["score"], r["q_end"], r["t_end"])
-        # targets only (what an alignment module asks for): no index afterwards
-        assert other.db_load(path, 0x1234, 0) is True
-        assert np.array_equal(other.sw_batch(mat, 11, 1, sw_q, mode=1), a)
-        with pytest.raises(capi.MMGpuError):
-            other.pf_batch(qs[:1], thr, max_hits=300, ref_bins=2)
-        # damaged files are refused and leave the context as it was: a flipped byte in the offset table, in the residues, a
-        # truncated file, a header whose section lies outside the file (the resident targets keep answering)
         import struct
         raw = bytearray(path.read_bytes())
         fields = struct.unpack_from("<8sIIQQIIIIQQIIiiiiQQ7Q6Q", raw, 0)
@@ -122,6 +115,23 @@ def test_saved_database_answers_like_the_resident_one(gpu, matrices, oracle, tmp
         cases = {"offsets": flip(at_offsets + 4 * 1000 + 1), "residues": flip(at_res + 777), "entries": flip(at_entries + 8 * 50),
                  "lengths": flip(at_len + 9), "truncated": lambda bb: bb[:at_entries + 100],
                  "section_outside": lambda bb: struct.pack_into("<Q", bb, 8 + 8 + 16 + 16 + 16 + 8 + 16 + 16 + 4 * 8, len(raw) + 4096)}
+        # with the file's index resident, a file whose index is damaged is refused and the resident index keeps answering (the loop
+        # below runs after the index has been dropped)
+        assert other.db_load(damaged("entries_with_index.mmgpu", cases["entries"]), 0x1234, 0x77, 6, 21, True, s3, i3, um8) is False
+        off_c, ids_c, pos_c = other.pf_debug_index(6, 21)
+        assert np.array_equal(off_a, off_c) and np.array_equal(ids_a, ids_c) and np.array_equal(pos_a, pos_c)
+        hits_c, counts_c, status_c, _ = other.pf_batch(qs, thr, max_hits=300, ref_bins=2)
+        assert np.array_equal(counts_a, counts_c) and np.array_equal(status_a, status_c)
+        for qi in range(len(qs)):
+            n = int(counts_a[qi])
+            assert np.array_equal(hits_a[qi][:n], hits_c[qi][:n])
+        # targets only (what an alignment module asks for): no index afterwards
+        assert other.db_load(path, 0x1234, 0) is True
+        assert np.array_equal(other.sw_batch(mat, 11, 1, sw_q, mode=1), a)
+        with pytest.raises(capi.MMGpuError):
+            other.pf_batch(qs[:1], thr, max_hits=300, ref_bins=2)
+        # damaged files are refused and leave the context as it was: a flipped byte in the offset table, in the residues, a
+        # truncated file, a header whose section lies outside the file (the resident targets keep answering)
         for name, change in cases.items():
             q = damaged(name + ".mmgpu", change)
             assert other.db_load(q, 0x1234, 0x77, 6, 21, True, s3, i3, um8) is False, name
