@@ -931,7 +931,7 @@ int mmgpu_host_rescore_accept(const mmgpu_rescore_hit *rec, uint32_t qlen, uint3
  * The parameters carry no defaults: the caller passes what setKmerLengthAndAlphabet (:2043-2071) would have chosen, and the reduction
  * table of its ReducedMatrix (the identity for alph_size 21).
  * MMGPU_ERR_STATE: no targets loaded; a batch used after the targets were reloaded; fetch before run.  MMGPU_ERR_UNSUPPORTED: a
- * nucleotide or profile database, a context that holds a shard, a sequence of 32 767 residues or more, (alph_size - 1)^k >= 2^63,
+ * nucleotide database (that is mmgpu_nuclmatch_* below) or a profile database, a context that holds a shard, a sequence of 32 767 residues or more, (alph_size - 1)^k >= 2^63,
  * cov_mode outside 0 .. 5, 2^31 records or more.  MMGPU_ERR_ARG: NULL arguments, k outside 1 .. 32, alph_size outside 3 .. 21,
  * kmers_per_seq < 1, a negative scale, a reduce entry >= alph_size.  MMGPU_ERR_HIP (out of memory) before any kernel runs when the
  * records, bounded as computeKmerCount (:1100-1108) bounds them, do not fit in free device memory.
@@ -974,6 +974,55 @@ void mmgpu_kmermatch_free(mmgpu_ctx *ctx, mmgpu_kmermatch_batch_t *batch);
  * Errors as mmgpu_rescore_prepare and as a fetch of the k-mer matching batch. */
 int mmgpu_kmermatch_rescore_prepare(mmgpu_ctx *ctx, const mmgpu_rescore_params *params, mmgpu_kmermatch_batch_t *kmermatch,
                                          mmgpu_rescore_batch_t **batch);
+
+/* ---- linclust's k-mer matching stage, nucleotides (kmermatcher.cpp's DBTYPE_NUCLEOTIDES branch), both strands ------------------------
+ * Over the resident nucleotide database (alphabet 5: A C T G N = 0 .. 4), the four steps of the stage above with these differences:
+ *   extract  every window of k residues without an N; index = 2 bits a residue, the first residue in the highest bits
+ *            (Indexer::computeKmerIdx); its reverse complement (Util::revComplement: the 2-bit groups in reverse order, each XOR 2);
+ *            a window equal to its reverse complement is dropped (:175); the smaller of the two is the k-mer, hashed and selected as
+ *            above with kmers_per_seq_scale the nucleotide value of --kmer-per-seq-scale.  The stored k-mer carries the strand in bit
+ *            63: set for a window taken as it stands, clear for one taken as its reverse complement, whose stored position is the one
+ *            on the other strand, L - position - k.  The record of the sequence as a whole is XXH64(Util::hash(residues)) as it comes:
+ *            its bit 63 is read as a strand like any other's.
+ *   sort     by (k-mer without bit 63, length descending, id, stored position)
+ *   group    groups are equal k-mers without bit 63.  With the representative's and the member's strand (bit 63 clear = reverse):
+ *            the diagonal is representative's position - member's when the member is forward, and
+ *            (qLen - 1 - qPos) - (tLen - 1 - tPos) when it is reverse; the representative has to be reverse-complemented when the two
+ *            strands differ.  The acceptance rule is the one above, on that diagonal.
+ *   vote     per (representative, member), entries ordered by diagonal, as writeKmerMatcherResult (:1588-1656) does it: a run whose
+ *            first entry needs no reverse complement gets score 0 and that entry's diagonal; otherwise the run's leading entries
+ *            that need one are voted (diagonal with the most entries, the largest on a tie) and score = -(their number); entries
+ *            behind the first change of orientation are not looked at.
+ * The result is the CSR of the stage above; score < 0: the representative has to be reverse-complemented for this member.
+ * Ties: the reference's comparators ignore bit 63 and its sorts are not stable, so its order between two records (or two emitted
+ * entries) that differ in the strand only is unspecified.  Both sorts here are stable: such records keep the order they were born in,
+ * id, then window position.  tests/nuclmatch_cases.py implements the same rule and names the ties (`strand_ties`).
+ * MMGPU_ERR_STATE: as above.  MMGPU_ERR_UNSUPPORTED: a database whose alphabet is not 5, a context that holds a shard, a sequence of
+ * 32 767 residues or more, cov_mode 1 (the reference's target-coverage swap stores the pair without its strand) or outside 0 .. 5,
+ * 2^31 records or more.  MMGPU_ERR_ARG: NULL arguments, k outside 1 .. 31 (the 2k bits of a window stay below bit 63),
+ * kmers_per_seq < 1, a negative scale.  Out of memory as above, with the bound of computeKmerCount under the nucleotide scale.
+ * The parameters are judged before the context.  run synchronises three times and ends synchronised.
+ * Not here: --adjust-kmer-len, --ignore-multi-kmer, masking, spaced k-mers; no hand-over to the ungapped rescoring yet (nucleotide
+ * rescorediagonal writes reverse-strand results). */
+typedef struct {
+    int k;                          /* par.kmerSize, 1 .. 31 */
+    int kmers_per_seq;              /* par.kmersPerSequence */
+    float kmers_per_seq_scale;      /* par.kmersPerSequenceScale (nucleotides) */
+    int hash_shift;                 /* par.hashShift: the XXH64 seed */
+    float cov_thr;                  /* -c */
+    int cov_mode;                   /* --cov-mode: 0, 2 .. 5 */
+    int include_only_extendable;    /* --include-only-extendable */
+} mmgpu_nuclmatch_params;
+typedef struct mmgpu_nuclmatch_batch_t mmgpu_nuclmatch_batch_t;
+
+int mmgpu_nuclmatch_prepare(mmgpu_ctx *ctx, const mmgpu_nuclmatch_params *params, mmgpu_nuclmatch_batch_t **batch);
+int mmgpu_nuclmatch_run(mmgpu_ctx *ctx, mmgpu_nuclmatch_batch_t *batch);
+/* as mmgpu_kmermatch_fetch: counts first, then offsets[n_seqs + 1] and records[n_entries]; the score is signed */
+int mmgpu_nuclmatch_fetch(mmgpu_ctx *ctx, mmgpu_nuclmatch_batch_t *batch, mmgpu_kmermatch_counts *counts, uint64_t *offsets, mmgpu_pf_hit *records);
+int mmgpu_nuclmatch_fetch_device(mmgpu_ctx *ctx, mmgpu_nuclmatch_batch_t *batch, void *d_offsets, void *d_records);
+/* ms[6] of the last run: the whole run, then extract, sort 1, group, sort 2, vote */
+int mmgpu_nuclmatch_last_kernel_ms(mmgpu_ctx *ctx, mmgpu_nuclmatch_batch_t *batch, float *ms);
+void mmgpu_nuclmatch_free(mmgpu_ctx *ctx, mmgpu_nuclmatch_batch_t *batch);
 
 #ifdef __cplusplus
 }

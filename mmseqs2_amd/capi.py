@@ -96,6 +96,8 @@ EXPORTED_SYMBOLS = [
     "mmgpu_rescore_free", "mmgpu_rescore_batch", "mmgpu_host_rescore_accept",
     "mmgpu_kmermatch_prepare", "mmgpu_kmermatch_run", "mmgpu_kmermatch_fetch", "mmgpu_kmermatch_fetch_device", "mmgpu_kmermatch_last_kernel_ms",
     "mmgpu_kmermatch_free", "mmgpu_kmermatch_rescore_prepare",
+    "mmgpu_nuclmatch_prepare", "mmgpu_nuclmatch_run", "mmgpu_nuclmatch_fetch", "mmgpu_nuclmatch_fetch_device", "mmgpu_nuclmatch_last_kernel_ms",
+    "mmgpu_nuclmatch_free",
 ]
 
 
@@ -182,6 +184,11 @@ class KmermatchParams(ctypes.Structure):      # mmgpu_kmermatch_params
 
 class KmermatchCounts(ctypes.Structure):      # mmgpu_kmermatch_counts
     _fields_ = [("n_seqs", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("n_records", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64)]
+
+
+class NuclmatchParams(ctypes.Structure):      # mmgpu_nuclmatch_params
+    _fields_ = [("k", ctypes.c_int), ("kmers_per_seq", ctypes.c_int), ("kmers_per_seq_scale", ctypes.c_float), ("hash_shift", ctypes.c_int),
+                ("cov_thr", ctypes.c_float), ("cov_mode", ctypes.c_int), ("include_only_extendable", ctypes.c_int)]
 
 
 KMERMATCH_STAGES = ("extract", "sort1", "group", "sort2", "vote")      # mmgpu_kmermatch_last_kernel_ms: ms[0] the whole run, ms[1 + i] stage i
@@ -336,6 +343,13 @@ def load_library():
     L.mmgpu_kmermatch_free.argtypes = [c_p, c_p]
     L.mmgpu_kmermatch_free.restype = None
     L.mmgpu_kmermatch_rescore_prepare.argtypes = [c_p, ctypes.POINTER(RescoreParams), c_p, ctypes.POINTER(c_p)]
+    L.mmgpu_nuclmatch_prepare.argtypes = [c_p, ctypes.POINTER(NuclmatchParams), ctypes.POINTER(c_p)]
+    L.mmgpu_nuclmatch_run.argtypes = [c_p, c_p]
+    L.mmgpu_nuclmatch_fetch.argtypes = [c_p, c_p, ctypes.POINTER(KmermatchCounts), c_p, c_p]
+    L.mmgpu_nuclmatch_fetch_device.argtypes = [c_p, c_p, c_p, c_p]
+    L.mmgpu_nuclmatch_last_kernel_ms.argtypes = [c_p, c_p, ctypes.POINTER(ctypes.c_float)]
+    L.mmgpu_nuclmatch_free.argtypes = [c_p, c_p]
+    L.mmgpu_nuclmatch_free.restype = None
     L.mmgpu_host_rescore_accept.argtypes = [c_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_double,
                                             ctypes.POINTER(RescoreAcceptParams), ctypes.POINTER(RescoreVerdict)]
     return L
@@ -667,6 +681,52 @@ class RescoreBatch:
     def free(self):
         if self.handle is not None:
             self.gpu.L.mmgpu_rescore_free(self.gpu.ctx, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class NuclmatchBatch:
+    """A prepared k-mer matching stage of linclust over the resident nucleotide database (mmgpu_nuclmatch_*)."""
+
+    def __init__(self, gpu, handle):
+        self.gpu, self.handle = gpu, handle
+
+    def run(self):
+        self.gpu._check(self.gpu.L.mmgpu_nuclmatch_run(self.gpu.ctx, self.handle))
+
+    def counts(self):
+        """-> dict n_seqs, n_entries (of the result), n_records (extracted), n_pairs (emitted by the grouping)"""
+        c = KmermatchCounts()
+        self.gpu._check(self.gpu.L.mmgpu_nuclmatch_fetch(self.gpu.ctx, self.handle, ctypes.byref(c), None, None))
+        return {k: int(getattr(c, k)) for k, _ in KmermatchCounts._fields_}
+
+    def fetch(self):
+        """-> (offsets uint64[n + 1], records PF_HIT_DTYPE[offsets[n]]): per sequence {id, 0, 0}, then its members in id order; a
+        negative score: the representative has to be reverse-complemented"""
+        c = self.counts()
+        off = np.zeros(c["n_seqs"] + 1, np.uint64)
+        rec = np.zeros(max(c["n_entries"], 1), PF_HIT_DTYPE)
+        self.gpu._check(self.gpu.L.mmgpu_nuclmatch_fetch(self.gpu.ctx, self.handle, None, _ptr(off), _ptr(rec)))
+        return off, rec[:c["n_entries"]]
+
+    def fetch_device(self, d_offsets_ptr, d_records_ptr):
+        """D2D copy of the CSR into caller-owned device memory (raw pointers), on the context's stream"""
+        self.gpu._check(self.gpu.L.mmgpu_nuclmatch_fetch_device(self.gpu.ctx, self.handle, c_p(d_offsets_ptr), c_p(d_records_ptr)))
+
+    def stage_ms(self):
+        """-> (ms of the whole last run, dict stage -> ms)"""
+        ms = (ctypes.c_float * (1 + len(KMERMATCH_STAGES)))()
+        self.gpu._check(self.gpu.L.mmgpu_nuclmatch_last_kernel_ms(self.gpu.ctx, self.handle, ms))
+        return ms[0], {name: ms[1 + i] for i, name in enumerate(KMERMATCH_STAGES)}
+
+    def free(self):
+        if self.handle is not None:
+            self.gpu.L.mmgpu_nuclmatch_free(self.gpu.ctx, self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1344,6 +1404,21 @@ class MMGpu:
         finally:
             b.free()
 
+    def nuclmatch_prepare(self, params):
+        """mmgpu_nuclmatch_prepare: params = NuclmatchParams, or a dict of its fields -> NuclmatchBatch"""
+        h = c_p()
+        self._check(self.L.mmgpu_nuclmatch_prepare(self.ctx, ctypes.byref(nuclmatch_params(params)), ctypes.byref(h)))
+        return NuclmatchBatch(self, h)
+
+    def nuclmatch(self, params):
+        """linclust's k-mer matching stage over the resident nucleotide database, both strands -> (offsets, records)"""
+        b = self.nuclmatch_prepare(params)
+        try:
+            b.run()
+            return b.fetch()
+        finally:
+            b.free()
+
     def pf_set_shard(self, n_shards, shard, global_db_size, global_ids, shard_of, local_id):
         """this context holds shard `shard` of a database of global_db_size targets (None-like: pf_clear_shard)"""
         g = np.ascontiguousarray(global_ids, np.uint32)
@@ -1479,6 +1554,20 @@ def kmermatch_defaults(min_seq_id, n_residues):
     if thr >= 0.9:
         return 14, 13
     return max(10, int(float(np.log(np.float32(n_residues))) / float(np.log(8.7)))), 13
+
+
+def nuclmatch_params(p):
+    """a dict of mmgpu_nuclmatch_params' fields -> NuclmatchParams (a NuclmatchParams passes through)"""
+    if isinstance(p, NuclmatchParams):
+        return p
+    return NuclmatchParams(int(p["k"]), int(p["kmers_per_seq"]), float(p["kmers_per_seq_scale"]), int(p["hash_shift"]), float(p["cov_thr"]),
+                           int(p["cov_mode"]), int(bool(p["include_only_extendable"])))
+
+
+def nuclmatch_defaults(n_residues):
+    """setKmerLengthAndAlphabet (kmermatcher.cpp:2044-2052) for a nucleotide database of n_residues residues when -k is not given
+    -> k (60 k-mers per sequence go with it).  The logarithm of the float database size is divided by the double log(4)"""
+    return max(17, int(float(np.log(np.float32(n_residues))) / float(np.log(4))))
 
 
 def linclust_prefilter(gpu, mat, params, rescore_mode, e=0.001, min_seq_id=0.0, seq_id_mode=0, cov=0.0, cov_mode=0, min_aln_len=0,

@@ -51,13 +51,6 @@ int kmm_check_db(const char *who, const mmgpu_ctx *c) {
     return MMGPU_OK;
 }
 
-int kmm_check_batch(const char *who, const mmgpu_ctx *c, const mmgpu_kmermatch_batch_t *b, bool must_have_run) {
-    if (!c || !b) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
-    if (b->db_res != c->db.res || b->n != c->db.n) return fail(MMGPU_ERR_STATE, std::string(who) + ": the targets were reloaded since the batch was prepared");
-    if (must_have_run && !b->ran) return fail(MMGPU_ERR_STATE, std::string(who) + ": the batch has not been run");
-    return MMGPU_OK;
-}
-
 // bytes of device memory a run holds at its peak for `bound` records of n sequences: four uint64 and two uint32 arrays per record (keys
 // and values of both sorts, each with its double; group starts and compaction offsets), two uint16 (the diagonals and their double),
 // the result (at most one entry per sequence and per record), the per-sequence rule / count / offset, and rocprim's scratch, which is
@@ -75,6 +68,7 @@ uint64_t kmm_capacity(const mmgpu_kmermatch_batch_t *b) { return b->bound + b->n
 
 // everything a run allocates beside the result; the blocks go back to the context's cache when the run ends (it ends synchronised)
 struct KmmRun {
+    const char *who;                                  // the entry point, for the messages
     mmgpu_ctx *c;
     mmgpu_kmermatch_batch_t *b;
     hipStream_t s;
@@ -106,8 +100,44 @@ int kmm_alloc(KmmRun &R) {
     return MMGPU_OK;
 }
 
+// the record count of the extraction, between its two passes
+int kmm_read_n_records(KmmRun &R) {
+    const int rc = kmm_read_u32(R, R.rec_off.as<uint32_t>() + R.b->n, &R.n_records);
+    if (rc != MMGPU_OK) return rc;
+    if (R.n_records > kmm_capacity(R.b)) return fail(MMGPU_ERR_HIP, std::string(R.who) + ": more records than computeKmerCount bounds");      // (cannot happen)
+    return MMGPU_OK;
+}
+
+// stage 1 over nucleotides: the same three steps with nuclmatch_kernel.hip's two passes, the sequences longest first
+int kmm_extract_nucl(KmmRun &R) {
+    mmgpu_ctx *c = R.c;
+    const mmgpu_kmermatch_params &p = R.b->par;
+    NuclExtractArgs A{};
+    A.res = c->db.res;
+    A.off4 = c->db.off4;
+    A.len = c->db.len;
+    A.order = R.b->d_order.as<uint32_t>();
+    A.n = R.b->n;
+    A.k = p.k;
+    A.kmers_per_seq = p.kmers_per_seq;
+    A.kmers_per_seq_scale = p.kmers_per_seq_scale;
+    A.seed = (unsigned long long)(long long)p.hash_shift;
+    A.rule = R.rule.as<uint4>();
+    A.count = R.count.as<uint32_t>();
+    A.rec_off = R.rec_off.as<uint32_t>();
+    A.rec_kmer = R.cc.as<unsigned long long>();
+    A.rec_val = R.a.as<unsigned long long>();
+    HIP_TRY(launch_nuclmatch_extract_count(A, R.s));
+    HIP_TRY(launch_kmm_record_offsets(A.count, A.n, R.tile_sum.as<uint32_t>(), R.rec_off.as<uint32_t>(), R.s));
+    const int rc = kmm_read_n_records(R);
+    if (rc != MMGPU_OK) return rc;
+    HIP_TRY(launch_nuclmatch_extract_write(A, R.s));
+    return MMGPU_OK;
+}
+
 // stage 1: count, offsets, write -> records (k-mer in cc, value in a), n_records
 int kmm_extract(KmmRun &R) {
+    if (R.b->nucl) return kmm_extract_nucl(R);
     mmgpu_ctx *c = R.c;
     const mmgpu_kmermatch_params &p = R.b->par;
     KmmExtractArgs A{};
@@ -128,9 +158,8 @@ int kmm_extract(KmmRun &R) {
     A.rec_val = R.a.as<unsigned long long>();
     HIP_TRY(launch_kmm_extract_count(A, R.s));
     HIP_TRY(launch_kmm_record_offsets(A.count, A.n, R.tile_sum.as<uint32_t>(), R.rec_off.as<uint32_t>(), R.s));
-    const int rc = kmm_read_u32(R, R.rec_off.as<uint32_t>() + A.n, &R.n_records);
+    const int rc = kmm_read_n_records(R);
     if (rc != MMGPU_OK) return rc;
-    if (R.n_records > kmm_capacity(R.b)) return fail(MMGPU_ERR_HIP, "mmgpu_kmermatch_run: more records than computeKmerCount bounds");      // (cannot happen)
     HIP_TRY(launch_kmm_extract_write(A, R.s));
     return MMGPU_OK;
 }
@@ -140,14 +169,47 @@ int kmm_sort_pairs(KmmRun &R, const char *what, hipError_t (*call)(KmmRun &, voi
     hipError_t e = call(R, nullptr, bytes);
     if (e == hipSuccess) e = R.tmp.reserve(std::max<size_t>(bytes, 16));
     if (e == hipSuccess) e = call(R, R.tmp.p, bytes);
-    if (e != hipSuccess) return fail(MMGPU_ERR_HIP, std::string("mmgpu_kmermatch_run: ") + what + ": " + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MMGPU_ERR_HIP, std::string(R.who) + ": " + what + ": " + hipGetErrorString(e));
     return MMGPU_OK;
+}
+
+// ids of n sequences fit in this many bits
+unsigned kmm_id_bits(uint32_t n) {
+    unsigned bits = 1;
+    while (bits < 32 && (1ull << bits) < n) bits++;
+    return bits;
+}
+
+// sort 1 over nucleotides: (k-mer without its strand bit, value) ascending in three stable passes.  The records of a sequence are born
+// in window order, but a window taken as its reverse complement stores its position on the other strand, so the (id, position)
+// bits of the value are sorted too; then the length bits, then bits 0 .. 62 of the k-mer (begin_bit 0: the merge-path hazard
+// mmgpu_internal.h records needs a begin_bit above 0).  Records that agree in all of that keep the order they were born in.
+// In: k-mer cc, value a.  Out: k-mer cc, value a.
+int kmm_sort_records_nucl(KmmRun &R) {
+    int rc = kmm_sort_pairs(R, "sort by id and position", [](KmmRun &r, void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, r.a.as<unsigned long long>(), r.bb.as<unsigned long long>(), r.cc.as<unsigned long long>(),
+                                         r.dd.as<unsigned long long>(), (size_t)r.n_records, 0u, KMM_ID_SHIFT + kmm_id_bits(r.b->n), r.s);
+    });
+    if (rc != MMGPU_OK) return rc;
+    rc = kmm_sort_pairs(R, "sort by length", [](KmmRun &r, void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, r.bb.as<unsigned long long>(), r.a.as<unsigned long long>(), r.dd.as<unsigned long long>(),
+                                         r.cc.as<unsigned long long>(), (size_t)r.n_records, KMM_LEN_SHIFT, KMM_LEN_END, r.s);
+    });
+    if (rc != MMGPU_OK) return rc;
+    rc = kmm_sort_pairs(R, "sort by k-mer", [](KmmRun &r, void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, r.cc.as<unsigned long long>(), r.dd.as<unsigned long long>(), r.a.as<unsigned long long>(),
+                                         r.bb.as<unsigned long long>(), (size_t)r.n_records, 0u, 63u, r.s);
+    });
+    std::swap(R.cc, R.dd);      // the k-mers are in dd and the values in bb now: the names follow the contents
+    std::swap(R.a, R.bb);
+    return rc;
 }
 
 // sort 1: (k-mer, value) ascending in two stable passes - by the value's length bits (the records are in (id, position) order
 // already), then by the k-mer.  In: k-mer cc, value a.  Out: k-mer cc, value a.
 int kmm_sort_records(KmmRun &R) {
     if (R.n_records == 0) return MMGPU_OK;
+    if (R.b->nucl) return kmm_sort_records_nucl(R);
     int rc = kmm_sort_pairs(R, "sort by length", [](KmmRun &r, void *tmp, size_t &bytes) {
         return rocprim::radix_sort_pairs(tmp, bytes, r.a.as<unsigned long long>(), r.bb.as<unsigned long long>(), r.cc.as<unsigned long long>(),
                                          r.dd.as<unsigned long long>(), (size_t)r.n_records, KMM_LEN_SHIFT, KMM_LEN_END, r.s);
@@ -170,6 +232,7 @@ int kmm_group(KmmRun &R) {
     G.cov_thr = p.cov_thr;
     G.cov_mode = p.cov_mode;
     G.only_extendable = p.include_only_extendable ? 1 : 0;
+    G.nucl = R.b->nucl ? 1 : 0;
     HIP_TRY(launch_kmm_group_scan(G, R.tile_sum.as<uint32_t>(), R.u2.as<uint32_t>(), R.s));
     const int rc = kmm_read_u32(R, R.u2.as<uint32_t>() + R.n_records, &R.n_pairs);
     if (rc != MMGPU_OK) return rc;
@@ -178,7 +241,8 @@ int kmm_group(KmmRun &R) {
 }
 
 // sort 2: (representative, member, diagonal) in two stable passes - by the diagonal, then by the pair, whose bits above the ids of
-// n sequences are 0.  In: pair bb, diagonal h1.  Out: pair bb, diagonal h1.
+// n sequences are 0 (a nucleotide pair's bit 63, the representative's orientation, lies above them too and is not ordered).
+// In: pair bb, diagonal h1.  Out: pair bb, diagonal h1.
 int kmm_sort_emitted(KmmRun &R) {
     if (R.n_pairs == 0) return MMGPU_OK;
     int rc = kmm_sort_pairs(R, "sort by diagonal", [](KmmRun &r, void *tmp, size_t &bytes) {
@@ -187,34 +251,59 @@ int kmm_sort_emitted(KmmRun &R) {
     });
     if (rc != MMGPU_OK) return rc;
     return kmm_sort_pairs(R, "sort by pair", [](KmmRun &r, void *tmp, size_t &bytes) {
-        unsigned id_bits = 1;
-        while (id_bits < 32 && (1ull << id_bits) < r.b->n) id_bits++;
         return rocprim::radix_sort_pairs(tmp, bytes, r.dd.as<unsigned long long>(), r.bb.as<unsigned long long>(), r.h2.as<uint16_t>(), r.h1.as<uint16_t>(),
-                                         (size_t)r.n_pairs, 0u, 32u + id_bits, r.s);
+                                         (size_t)r.n_pairs, 0u, 32u + kmm_id_bits(r.b->n), r.s);
     });
 }
 
 // vote: the kept runs (u1: their offsets, u2: their representatives), the result
 int kmm_vote(KmmRun &R) {
     mmgpu_kmermatch_batch_t *b = R.b;
-    HIP_TRY(launch_kmm_vote_scan(R.bb.as<unsigned long long>(), R.n_pairs, R.tile_sum.as<uint32_t>(), R.u1.as<uint32_t>(), R.s));
+    HIP_TRY(launch_kmm_vote_scan(R.bb.as<unsigned long long>(), R.n_pairs, b->nucl, R.tile_sum.as<uint32_t>(), R.u1.as<uint32_t>(), R.s));
     const int rc = kmm_read_u32(R, R.u1.as<uint32_t>() + R.n_pairs, &R.n_kept);
     if (rc != MMGPU_OK) return rc;
     HIP_TRY(b->d_offsets.reserve(((size_t)b->n + 1) * 8));
     HIP_TRY(b->d_records.reserve(((size_t)b->n + R.n_kept) * sizeof(mmgpu_pf_hit)));
-    HIP_TRY(launch_kmm_vote(R.bb.as<unsigned long long>(), R.h1.as<uint16_t>(), R.n_pairs, R.u1.as<uint32_t>(), R.n_kept, b->n, R.u2.as<uint32_t>(),
+    HIP_TRY(launch_kmm_vote(R.bb.as<unsigned long long>(), R.h1.as<uint16_t>(), R.n_pairs, b->nucl, R.u1.as<uint32_t>(), R.n_kept, b->n, R.u2.as<uint32_t>(),
                             b->d_offsets.as<unsigned long long>(), b->d_records.as<mmgpu_pf_hit>(), R.s));
     return MMGPU_OK;
 }
 
-int kmm_run_impl(mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b) {
+}  // namespace
+
+namespace mmgpu {
+
+int kmm_check_batch(const char *who, const mmgpu_ctx *c, const mmgpu_kmermatch_batch_t *b, bool must_have_run) {
+    if (!c || !b) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
+    if (b->db_res != c->db.res || b->n != c->db.n) return fail(MMGPU_ERR_STATE, std::string(who) + ": the targets were reloaded since the batch was prepared");
+    if (must_have_run && !b->ran) return fail(MMGPU_ERR_STATE, std::string(who) + ": the batch has not been run");
+    return MMGPU_OK;
+}
+
+// a checked parameter set and its record bound -> a batch over the resident database
+int kmm_new_batch(const char *who, mmgpu_ctx *c, const mmgpu_kmermatch_params &par, bool nucl, uint64_t bound, mmgpu_kmermatch_batch_t *b) {
+    if (bound >= (1ull << 31)) return fail(MMGPU_ERR_UNSUPPORTED, std::string(who) + ": 2^31 records or more");
+    HIP_TRY(hipSetDevice(c->device));
+    b->par = par;
+    b->nucl = nucl;
+    b->n = c->db.n;
+    b->bound = bound;
+    b->db_res = c->db.res;
+    b->d_offsets.bind(c->cache);
+    b->d_records.bind(c->cache);
+    b->d_order.bind(c->cache);
+    for (hipEvent_t &e : b->ev) HIP_TRY(hipEventCreate(&e));
+    return MMGPU_OK;
+}
+
+int kmm_run_impl(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b) {
     HIP_TRY(hipSetDevice(c->device));
     // the bound before any kernel: what does not fit is refused with the runtime's out-of-memory error
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     if (kmm_bytes_needed(kmm_capacity(b), b->n) > (uint64_t)free_b + c->cache->cached)
-        return fail(MMGPU_ERR_HIP, std::string("mmgpu_kmermatch_run: ") + hipGetErrorString(hipErrorOutOfMemory) + ": the records of this database do not fit in free device memory");
-    KmmRun R{c, b, c->stream};
+        return fail(MMGPU_ERR_HIP, std::string(who) + ": " + hipGetErrorString(hipErrorOutOfMemory) + ": the records of this database do not fit in free device memory");
+    KmmRun R{who, c, b, c->stream};
     b->ran = false;
     int rc = kmm_alloc(R);
     int (*const steps[KMM_STAGES])(KmmRun &) = {kmm_extract, kmm_sort_records, kmm_group, kmm_sort_emitted, kmm_vote};
@@ -234,39 +323,7 @@ int kmm_run_impl(mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b) {
     return MMGPU_OK;
 }
 
-}  // namespace
-
-extern "C" int mmgpu_kmermatch_prepare(mmgpu_ctx *c, const mmgpu_kmermatch_params *par, mmgpu_kmermatch_batch_t **out) {
-    const char *who = "mmgpu_kmermatch_prepare";
-    if (out) *out = nullptr;
-    if (!out) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
-    int rc = kmm_check_params(who, par);
-    if (rc != MMGPU_OK) return rc;
-    if (!c) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
-    rc = kmm_check_db(who, c);
-    if (rc != MMGPU_OK) return rc;
-    const uint64_t bound = kmm_record_bound(c->h_len, *par);
-    if (bound >= (1ull << 31)) return fail(MMGPU_ERR_UNSUPPORTED, std::string(who) + ": 2^31 records or more");
-    HIP_TRY(hipSetDevice(c->device));
-    std::unique_ptr<mmgpu_kmermatch_batch_t> b(new mmgpu_kmermatch_batch_t());
-    b->par = *par;
-    b->n = c->db.n;
-    b->bound = bound;
-    b->db_res = c->db.res;
-    b->d_offsets.bind(c->cache);
-    b->d_records.bind(c->cache);
-    for (hipEvent_t &e : b->ev) HIP_TRY(hipEventCreate(&e));
-    *out = b.release();
-    return MMGPU_OK;
-}
-
-extern "C" int mmgpu_kmermatch_run(mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b) {
-    const int rc = kmm_check_batch("mmgpu_kmermatch_run", c, b, false);
-    if (rc != MMGPU_OK) return rc;
-    return kmm_run_impl(c, b);
-}
-
-static int kmm_fetch(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, mmgpu_kmermatch_counts *counts, void *offsets, void *records, hipMemcpyKind kind) {
+int kmm_fetch(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, mmgpu_kmermatch_counts *counts, void *offsets, void *records, hipMemcpyKind kind) {
     const int rc = kmm_check_batch(who, c, b, true);
     if (rc != MMGPU_OK) return rc;
     if (counts) {
@@ -283,6 +340,41 @@ static int kmm_fetch(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, 
     return MMGPU_OK;
 }
 
+int kmm_kernel_ms(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, float *ms) {
+    const int rc = kmm_check_batch(who, c, b, true);
+    if (rc != MMGPU_OK) return rc;
+    if (!ms) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(b->ev[KMM_STAGES]));
+    HIP_TRY(hipEventElapsedTime(&ms[0], b->ev[0], b->ev[KMM_STAGES]));
+    for (int i = 0; i < KMM_STAGES; i++) HIP_TRY(hipEventElapsedTime(&ms[1 + i], b->ev[i], b->ev[i + 1]));
+    return MMGPU_OK;
+}
+
+}  // namespace mmgpu
+
+extern "C" int mmgpu_kmermatch_prepare(mmgpu_ctx *c, const mmgpu_kmermatch_params *par, mmgpu_kmermatch_batch_t **out) {
+    const char *who = "mmgpu_kmermatch_prepare";
+    if (out) *out = nullptr;
+    if (!out) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
+    int rc = kmm_check_params(who, par);
+    if (rc != MMGPU_OK) return rc;
+    if (!c) return fail(MMGPU_ERR_ARG, std::string(who) + ": NULL argument");
+    rc = kmm_check_db(who, c);
+    if (rc != MMGPU_OK) return rc;
+    std::unique_ptr<mmgpu_kmermatch_batch_t> b(new mmgpu_kmermatch_batch_t());
+    rc = kmm_new_batch(who, c, *par, false, kmm_record_bound(c->h_len, *par), b.get());
+    if (rc != MMGPU_OK) return rc;
+    *out = b.release();
+    return MMGPU_OK;
+}
+
+extern "C" int mmgpu_kmermatch_run(mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b) {
+    const int rc = kmm_check_batch("mmgpu_kmermatch_run", c, b, false);
+    if (rc != MMGPU_OK) return rc;
+    return kmm_run_impl("mmgpu_kmermatch_run", c, b);
+}
+
 extern "C" int mmgpu_kmermatch_fetch(mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, mmgpu_kmermatch_counts *counts, uint64_t *offsets, mmgpu_pf_hit *records) {
     return kmm_fetch("mmgpu_kmermatch_fetch", c, b, counts, offsets, records, hipMemcpyDeviceToHost);
 }
@@ -293,14 +385,7 @@ extern "C" int mmgpu_kmermatch_fetch_device(mmgpu_ctx *c, mmgpu_kmermatch_batch_
 }
 
 extern "C" int mmgpu_kmermatch_last_kernel_ms(mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, float *ms) {
-    const int rc = kmm_check_batch("mmgpu_kmermatch_last_kernel_ms", c, b, true);
-    if (rc != MMGPU_OK) return rc;
-    if (!ms) return fail(MMGPU_ERR_ARG, "mmgpu_kmermatch_last_kernel_ms: NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(b->ev[KMM_STAGES]));
-    HIP_TRY(hipEventElapsedTime(&ms[0], b->ev[0], b->ev[KMM_STAGES]));
-    for (int i = 0; i < KMM_STAGES; i++) HIP_TRY(hipEventElapsedTime(&ms[1 + i], b->ev[i], b->ev[i + 1]));
-    return MMGPU_OK;
+    return kmm_kernel_ms("mmgpu_kmermatch_last_kernel_ms", c, b, ms);
 }
 
 extern "C" void mmgpu_kmermatch_free(mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b) {

@@ -13,99 +13,51 @@
 //                read through a functor, for the record offsets, the group starts (a maximum scan) and the three compactions.
 //   group, vote  one thread per record / per (representative, member) run.
 // The two sorts are rocprim::radix_sort_pairs (kmermatch_api.hip), each as two stable passes over parts of the key.
-#include "mmgpu_internal.h"
+#include "kmm_device.h"
 
 namespace mmgpu {
 
 namespace {
 
-constexpr unsigned long long XXH_P1 = 11400714785074694791ull, XXH_P2 = 14029467366897019727ull, XXH_P3 = 1609587929392839161ull,
-                             XXH_P4 = 9650029242287828579ull, XXH_P5 = 2870177450012600261ull;
-
-__device__ __forceinline__ unsigned long long rotl64(unsigned long long x, int r) { return (x << r) | (x >> (64 - r)); }
-
-// XXH64 of one 8-byte little-endian word (xxHash specification: inputs below 32 bytes start from seed + PRIME5, one 8-byte lane,
-// the avalanche)
-__device__ __forceinline__ unsigned long long xxh64_u64(unsigned long long v, unsigned long long seed) {
-    unsigned long long h = seed + XXH_P5 + 8ull;
-    h ^= rotl64(v * XXH_P2, 31) * XXH_P1;
-    h = rotl64(h, 27) * XXH_P1 + XXH_P4;
-    h ^= h >> 33;
-    h *= XXH_P2;
-    h ^= h >> 29;
-    h *= XXH_P3;
-    h ^= h >> 32;
-    return h;
-}
-
-__device__ __forceinline__ unsigned long long pow31(uint32_t e) {
-    unsigned long long r = 1, b = 31;
-    for (; e; e >>= 1, b *= b)
-        if (e & 1u) r *= b;
-    return r;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask, uint32_t lane) {
-    return (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
-// What one wavefront holds of its sequence while it walks the windows in rounds of 64
+// What one wavefront holds of its sequence while it walks the windows in rounds of 64 (the Walk of kmm_device.h)
 struct KmmWalk {
     const uint8_t *res;      // the sequence's residues
     uint32_t L, n_win;       // n_win: windows with or without X
     int k;
     uint32_t base, x;        // alph_size - 1: the radix of the index and the reduced X
     unsigned long long seed;
+    const uint8_t *red_tab;  // LDS: the reduction table
+    uint8_t *st;             // LDS [96]: the staged round
+
+    // st[0 .. 64 + k - 1): the reduced residues of round `c` and of the k - 1 behind it (KMM_MAX_K <= 32), X behind the sequence's end
+    __device__ __forceinline__ void stage(uint32_t c, uint32_t lane) {
+        const uint32_t p = c * 64u + lane;
+        st[lane] = p < L ? red_tab[res[p] < 21u ? res[p] : 20u] : (uint8_t)x;
+        if (lane < 32u) {
+            const uint32_t q = c * 64u + 64u + lane;
+            st[64u + lane] = q < L ? red_tab[res[q] < 21u ? res[q] : 20u] : (uint8_t)x;
+        }
+    }
+
+    // the window at position c * 64 + lane: false when there is none or it holds an X
+    __device__ __forceinline__ bool window(uint32_t c, uint32_t lane, unsigned long long &idx, uint32_t &pos, uint32_t &score) const {
+        pos = c * 64u + lane;
+        bool ok = pos < n_win;
+        unsigned long long v = 0;
+        for (int i = k - 1; i >= 0; i--) {      // Indexer::int2index: sum r[i] * base^i
+            const uint32_t r = st[lane + i];
+            ok = ok && r != x;
+            v = v * base + r;
+        }
+        idx = v;
+        score = (uint32_t)(xxh64_u64(v, seed) & 0xFFFFull);
+        return ok;
+    }
+
+    __device__ __forceinline__ uint32_t residue(uint32_t lane) const { return st[lane]; }
 };
 
-// stage[0 .. 64 + k - 1): the reduced residues of round `c` and of the k - 1 behind it (KMM_MAX_K <= 32), X behind the sequence's end
-__device__ __forceinline__ void kmm_stage(const KmmWalk &W, uint32_t c, const uint8_t *red_tab, uint8_t *stage, uint32_t lane) {
-    const uint32_t p = c * 64u + lane;
-    stage[lane] = p < W.L ? red_tab[W.res[p] < 21u ? W.res[p] : 20u] : (uint8_t)W.x;
-    if (lane < 32u) {
-        const uint32_t q = c * 64u + 64u + lane;
-        stage[64u + lane] = q < W.L ? red_tab[W.res[q] < 21u ? W.res[q] : 20u] : (uint8_t)W.x;
-    }
-}
-
-// the window at position c * 64 + lane: false when there is none or it holds an X
-__device__ __forceinline__ bool kmm_window(const KmmWalk &W, uint32_t c, const uint8_t *stage, uint32_t lane, unsigned long long &idx, uint32_t &score) {
-    const uint32_t p = c * 64u + lane;
-    bool ok = p < W.n_win;
-    unsigned long long v = 0;
-    for (int i = W.k - 1; i >= 0; i--) {      // Indexer::int2index: sum r[i] * base^i
-        const uint32_t r = stage[lane + i];
-        ok = ok && r != W.x;
-        v = v * W.base + r;
-    }
-    idx = v;
-    score = (uint32_t)(xxh64_u64(v, W.seed) & 0xFFFFull);
-    return ok;
-}
-
-// hist[256] (LDS, complete): the bin that holds the `want`-th smallest element (1-based, want <= sum of hist) and the elements below
-// that bin.  Uniform over the wavefront.
-__device__ __forceinline__ uint32_t kmm_find_bin(const uint32_t *hist, uint32_t want, uint32_t lane, uint32_t &below) {
-    const uint32_t h0 = hist[4u * lane], h1 = hist[4u * lane + 1u], h2 = hist[4u * lane + 2u], h3 = hist[4u * lane + 3u];
-    uint32_t incl = h0 + h1 + h2 + h3;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d);
-        if ((int)lane >= d) incl += up;
-    }
-    const unsigned long long reached = __ballot(incl >= want);
-    const uint32_t first = (uint32_t)__ffsll((long long)reached) - 1u;      // (reached != 0: want <= the total)
-    const uint32_t excl = incl - (h0 + h1 + h2 + h3);
-    uint32_t b = __shfl(excl, first);
-    const uint32_t g0 = __shfl(h0, first), g1 = __shfl(h1, first), g2 = __shfl(h2, first);
-    uint32_t bin = 4u * first;
-    if (b + g0 < want) { b += g0; bin++;
-        if (b + g1 < want) { b += g1; bin++;
-            if (b + g2 < want) { b += g2; bin++; } } }
-    below = b;
-    return bin;
-}
-
-__device__ __forceinline__ KmmWalk kmm_walk_of(const KmmExtractArgs &A, uint32_t sid) {
+__device__ __forceinline__ KmmWalk kmm_walk_of(const KmmExtractArgs &A, uint32_t sid, const uint8_t *red_tab, uint8_t *stage) {
     KmmWalk W;
     W.res = A.res + (size_t)A.off4[sid] * 4u;
     W.L = A.len[sid];
@@ -114,6 +66,8 @@ __device__ __forceinline__ KmmWalk kmm_walk_of(const KmmExtractArgs &A, uint32_t
     W.base = (uint32_t)A.alph_size - 1u;
     W.x = W.base;
     W.seed = A.seed;
+    W.red_tab = red_tab;
+    W.st = stage;
     return W;
 }
 
@@ -124,55 +78,9 @@ __global__ __launch_bounds__(64) void kmm_count_kernel(KmmExtractArgs A) {
     __shared__ uint8_t stage[96];
     const uint32_t sid = blockIdx.x, lane = threadIdx.x;
     if (sid >= A.n) return;
-    const KmmWalk W = kmm_walk_of(A, sid);
+    KmmWalk W = kmm_walk_of(A, sid, red_tab, stage);
     if (lane < 21u) red_tab[lane] = A.reduce[lane];
-    for (uint32_t i = lane; i < 256u; i += 64u) hist[i] = 0;
-    __syncthreads();
-    const uint32_t rounds = (W.n_win + 63u) / 64u;
-    uint32_t count = 0;
-    unsigned long long idx;
-    uint32_t score;
-    for (uint32_t c = 0; c < rounds; c++) {
-        kmm_stage(W, c, red_tab, stage, lane);
-        __syncthreads();
-        const bool ok = kmm_window(W, c, stage, lane, idx, score);
-        if (ok) atomicAdd(&hist[score >> 8], 1u);
-        count += (uint32_t)__popcll(__ballot(ok));
-        __syncthreads();
-    }
-    // kmermatcher.cpp:239: an int plus a float product, in float (no fused multiply-add), cut to a size_t
-    const float want_f = __fadd_rn((float)(A.kmers_per_seq - 1), __fmul_rn(A.kmers_per_seq_scale, (float)W.L));
-    const unsigned long long want_ll = (unsigned long long)want_f;
-    const uint32_t considered = want_ll < (unsigned long long)count ? (uint32_t)want_ll : count;
-    uint32_t t = 0, surplus = 0, n_sel = 0;
-    if (considered == count) {      // every window is taken: the largest score is the threshold bin and it has no surplus
-        t = 0xFFFFu;
-        n_sel = count;
-    } else if (considered > 0) {
-        uint32_t below_hi = 0, below_lo = 0;
-        const uint32_t hi = kmm_find_bin(hist, considered, lane, below_hi);
-        __syncthreads();
-        for (uint32_t i = lane; i < 256u; i += 64u) hist[i] = 0;
-        __syncthreads();
-        for (uint32_t c = 0; c < rounds; c++) {
-            kmm_stage(W, c, red_tab, stage, lane);
-            __syncthreads();
-            const bool ok = kmm_window(W, c, stage, lane, idx, score);
-            if (ok && (score >> 8) == hi) atomicAdd(&hist[score & 255u], 1u);
-            __syncthreads();
-        }
-        const uint32_t lo = kmm_find_bin(hist, considered - below_hi, lane, below_lo);
-        const uint32_t in_bin = hist[lo];
-        t = (hi << 8) | lo;
-        surplus = below_hi + below_lo + in_bin - considered;      // tooMuchElemInLastBin
-        // windows below t, plus the first `surplus` of bin t (all of it without a surplus), cut at `considered`
-        const uint32_t flagged = surplus == 0 ? considered : considered + 2u * surplus - in_bin;
-        n_sel = flagged < considered ? flagged : considered;
-    }
-    if (lane == 0) {
-        A.rule[sid] = make_uint4(t, surplus, considered, 0u);
-        A.count[sid] = 1u + n_sel;      // the identity record
-    }
+    kmm_count_body(W, hist, A.kmers_per_seq, A.kmers_per_seq_scale, lane, &A.rule[sid], &A.count[sid]);
 }
 
 // Pass 2: the records, at rec_off[sid]: the identity record, then the selected windows in position order
@@ -181,46 +89,10 @@ __global__ __launch_bounds__(64) void kmm_write_kernel(KmmExtractArgs A) {
     __shared__ uint8_t stage[96];
     const uint32_t sid = blockIdx.x, lane = threadIdx.x;
     if (sid >= A.n) return;
-    const KmmWalk W = kmm_walk_of(A, sid);
+    KmmWalk W = kmm_walk_of(A, sid, red_tab, stage);
     if (lane < 21u) red_tab[lane] = A.reduce[lane];
     __syncthreads();
-    const uint4 rule = A.rule[sid];
-    const uint32_t t = rule.x, surplus = rule.y, considered = rule.z;
-    const uint32_t base = A.rec_off[sid];
-    const unsigned long long tag = ((unsigned long long)(KMM_LEN_MASK - W.L) << KMM_LEN_SHIFT) | ((unsigned long long)sid << KMM_ID_SHIFT);
-    const uint32_t rounds = (W.L + 63u) / 64u;      // every residue passes through stage[lane] once: the sequence hash rides along
-    unsigned long long seq_hash = 0;
-    uint32_t eq_seen = 0, sel_seen = 0;
-    for (uint32_t c = 0; c < rounds; c++) {
-        kmm_stage(W, c, red_tab, stage, lane);
-        __syncthreads();
-        // Util::hash: h = h * 31 + r over the residues of this round
-        const uint32_t m = W.L - c * 64u < 64u ? W.L - c * 64u : 64u;
-        unsigned long long part = lane < m ? (unsigned long long)stage[lane] * pow31(m - 1u - lane) : 0ull;
-        for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-        seq_hash = seq_hash * pow31(m) + part;
-        if (sel_seen < considered) {
-            unsigned long long idx;
-            uint32_t score;
-            const bool ok = kmm_window(W, c, stage, lane, idx, score);
-            const bool eq = ok && score == t;
-            const unsigned long long eq_mask = __ballot(eq);
-            const bool take = ok && (score < t || (eq && (surplus == 0 || eq_seen + lanes_below(eq_mask, lane) < surplus)));
-            const unsigned long long take_mask = __ballot(take);
-            const uint32_t rank = sel_seen + lanes_below(take_mask, lane);
-            if (take && rank < considered) {
-                A.rec_kmer[base + 1u + rank] = idx;
-                A.rec_val[base + 1u + rank] = tag | (unsigned long long)(c * 64u + lane);
-            }
-            eq_seen += (uint32_t)__popcll(eq_mask);
-            sel_seen += (uint32_t)__popcll(take_mask);
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        A.rec_kmer[base] = xxh64_u64(seq_hash, W.seed);
-        A.rec_val[base] = tag;
-    }
+    kmm_write_body(W, A.rule[sid], sid, A.rec_off[sid], lane, A.rec_kmer, A.rec_val);
 }
 
 // ---- scans ---------------------------------------------------------------------------------------------------------------------------
@@ -328,10 +200,33 @@ __device__ __forceinline__ uint32_t val_len(unsigned long long v) { return KMM_L
 __device__ __forceinline__ uint32_t val_id(unsigned long long v) { return (uint32_t)(v >> KMM_ID_SHIFT); }
 __device__ __forceinline__ int val_pos(unsigned long long v) { return (int)(v & KMM_LEN_MASK); }
 
+// NUCL (nuclmatch_api.hip): bit 63 of a k-mer is the strand its window was taken on and bit 63 of an emitted pair says whether the
+// representative is aligned as it stands; neither takes part in a comparison
+constexpr unsigned long long KMM_STRAND = 1ull << 63;
+template <bool NUCL>
+__device__ __forceinline__ bool same_key(unsigned long long a, unsigned long long b) { return NUCL ? ((a ^ b) & ~KMM_STRAND) == 0 : a == b; }
+
+template <bool NUCL>
 struct GroupHead {      // i where a k-mer's records begin, else 0: its maximum scan is every record's group start
     const unsigned long long *kmer;
-    __device__ uint32_t operator()(uint32_t i) const { return i > 0 && kmer[i] != kmer[i - 1] ? i : 0u; }
+    __device__ uint32_t operator()(uint32_t i) const { return i > 0 && !same_key<NUCL>(kmer[i], kmer[i - 1]) ? i : 0u; }
 };
+
+// the diagonal of member record `me` against its representative's (kmermatcher.cpp:636-663).  NUCL: a window taken as its reverse
+// complement stores its position on the reverse strand, so both positions are counted from the far end when the member's is one;
+// the representative stays as it is when both windows were taken on the same strand.  The reference computes in `short`: lengths
+// and positions are below 32 767 here and nothing wraps
+template <bool NUCL>
+__device__ __forceinline__ int kmm_diagonal(const KmmGroupArgs &A, uint32_t g, uint32_t i, bool &as_it_is) {
+    const unsigned long long rep = A.val[g], me = A.val[i];
+    as_it_is = true;
+    if (NUCL) {
+        const bool rep_reverse = !(A.kmer[g] & KMM_STRAND), me_reverse = !(A.kmer[i] & KMM_STRAND);
+        as_it_is = rep_reverse == me_reverse;
+        if (me_reverse) return ((int)val_len(rep) - 1 - val_pos(rep)) - ((int)val_len(me) - 1 - val_pos(me));
+    }
+    return val_pos(rep) - val_pos(me);
+}
 
 // Util::canBeCovered (Util.cpp:542-559), float32 with IEEE division
 __device__ __forceinline__ bool can_be_covered(float thr, int mode, float q, float t) {
@@ -346,54 +241,62 @@ __device__ __forceinline__ bool can_be_covered(float thr, int mode, float q, flo
     }
 }
 
+template <bool NUCL>
 struct GroupEmit {      // 1 when record i emits a (representative, member, diagonal), kmermatcher.cpp:633-672
     KmmGroupArgs A;
     __device__ uint32_t operator()(uint32_t i) const {
         const uint32_t g = A.group_start[i];
-        if (g == i && (i + 1u == A.n_records || A.kmer[i + 1u] != A.kmer[i])) return 0u;      // a group of one
-        const unsigned long long rep = A.val[g], me = A.val[i];
-        const int q_len = (int)val_len(rep), t_len = (int)val_len(me);
-        const int diagonal = val_pos(rep) - val_pos(me);
+        if (g == i && (i + 1u == A.n_records || !same_key<NUCL>(A.kmer[i + 1u], A.kmer[i]))) return 0u;      // a group of one
+        const int q_len = (int)val_len(A.val[g]), t_len = (int)val_len(A.val[i]);
+        bool as_it_is;
+        const int diagonal = kmm_diagonal<NUCL>(A, g, i, as_it_is);
         const bool extendable = diagonal < 0 || diagonal > q_len - t_len;
         const bool coverable = can_be_covered(A.cov_thr, A.cov_mode, (float)q_len, (float)t_len);
         return ((!A.only_extendable && coverable) || (A.only_extendable && extendable)) ? 1u : 0u;
     }
 };
 
+template <bool NUCL>
 __global__ __launch_bounds__(256) void kmm_emit_kernel(KmmGroupArgs A, const uint32_t *emit_at, unsigned long long *pair, uint16_t *diag) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= A.n_records) return;
-    const GroupEmit E{A};
+    const GroupEmit<NUCL> E{A};
     if (!E(i)) return;
     const unsigned long long rep = A.val[A.group_start[i]], me = A.val[i];
-    int diagonal = val_pos(rep) - val_pos(me);
+    bool as_it_is;
+    int diagonal = kmm_diagonal<NUCL>(A, A.group_start[i], i, as_it_is);
     uint32_t a = val_id(rep), b = val_id(me);
-    if (val_len(rep) < val_len(me) && A.cov_mode == 1) {      // :679-683
+    if (!NUCL && val_len(rep) < val_len(me) && A.cov_mode == 1) {      // :679-683 (refused on nucleotides: the swap loses the strand)
         const uint32_t s = a; a = b; b = s;
         diagonal = -diagonal;
     }
     const uint32_t at = emit_at[i];
-    pair[at] = ((unsigned long long)a << 32) | b;
+    pair[at] = ((unsigned long long)a << 32) | b | (NUCL && as_it_is ? KMM_STRAND : 0ull);      // (ids are below 2^31: a sequence has a record)
     diag[at] = (uint16_t)((uint32_t)diagonal ^ 0x8000u);      // the short, biased: the radix sort orders it as a signed value
 }
 
 // ---- vote --------------------------------------------------------------------------------------------------------------------------
+template <bool NUCL>
 struct PairKept {      // 1 where a (representative, member) run with member != representative begins
     const unsigned long long *pair;
     __device__ uint32_t operator()(uint32_t i) const {
-        const unsigned long long p = pair[i];
-        return (i == 0 || pair[i - 1] != p) && (uint32_t)(p >> 32) != (uint32_t)p ? 1u : 0u;
+        const unsigned long long p = NUCL ? pair[i] & ~KMM_STRAND : pair[i];
+        return (i == 0 || !same_key<NUCL>(pair[i - 1], p)) && (uint32_t)(p >> 32) != (uint32_t)p ? 1u : 0u;
     }
 };
 
-// writeKmerMatcherResult (:1614-1655) per kept run: score = its length, diagonal = the value with the longest run, the last on a tie
+// writeKmerMatcherResult (:1614-1655) per kept run: score = its length, diagonal = the value with the longest run, the last on a tie.
+// NUCL: the reference's walk compares every entry with the representative's id, whose bit 63 it has cleared, so it covers the run's
+// leading entries with a reverse-complemented representative only and the score is minus their number; a run that begins with an
+// as-it-is entry is not walked at all: score 0 and that entry's diagonal, the smallest
+template <bool NUCL>
 __global__ __launch_bounds__(256) void kmm_vote_kernel(const unsigned long long *pair, const uint16_t *diag, uint32_t n_pairs, const uint32_t *kept_at,
                                                         mmgpu_pf_hit *records, uint32_t *kept_rep) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_pairs) return;
-    const PairKept K{pair};
+    const PairKept<NUCL> K{pair};
     if (!K(i)) return;
-    const unsigned long long p = pair[i];
+    const unsigned long long p = NUCL ? pair[i] & ~KMM_STRAND : pair[i];
     uint32_t score = 0, best_cnt = 0, cnt = 0;
     uint16_t best = diag[i], prev = diag[i];
     for (uint32_t j = i; j < n_pairs && pair[j] == p; j++) {
@@ -406,7 +309,7 @@ __global__ __launch_bounds__(256) void kmm_vote_kernel(const unsigned long long 
     const uint32_t rep = (uint32_t)(p >> 32), at = kept_at[i];
     mmgpu_pf_hit h;
     h.id = (uint32_t)p;
-    h.score = (int32_t)score;
+    h.score = NUCL ? -(int32_t)score : (int32_t)score;
     h.diagonal = (uint16_t)(best ^ 0x8000u);
     h.reserved = 0;
     records[(size_t)rep + 1u + at] = h;      // `rep + 1` lists' first entries and `at` kept runs lie before it
@@ -473,25 +376,28 @@ hipError_t launch_kmm_extract_write(const KmmExtractArgs &A, hipStream_t s) {
 
 // group_start[n_records], emit_at[n_records + 1] (emit_at[n_records] = the number of emitted records)
 hipError_t launch_kmm_group_scan(const KmmGroupArgs &A, uint32_t *tile_sum, uint32_t *emit_at, hipStream_t s) {
-    hipError_t e = scan_u32<GroupHead, OpMax, false>(GroupHead{A.kmer}, A.n_records, tile_sum, A.group_start, s);
+    hipError_t e = A.nucl ? scan_u32<GroupHead<true>, OpMax, false>(GroupHead<true>{A.kmer}, A.n_records, tile_sum, A.group_start, s)
+                          : scan_u32<GroupHead<false>, OpMax, false>(GroupHead<false>{A.kmer}, A.n_records, tile_sum, A.group_start, s);
     if (e != hipSuccess) return e;
-    return scan_u32<GroupEmit, OpSum, true>(GroupEmit{A}, A.n_records, tile_sum, emit_at, s);
+    return A.nucl ? scan_u32<GroupEmit<true>, OpSum, true>(GroupEmit<true>{A}, A.n_records, tile_sum, emit_at, s)
+                  : scan_u32<GroupEmit<false>, OpSum, true>(GroupEmit<false>{A}, A.n_records, tile_sum, emit_at, s);
 }
 
 hipError_t launch_kmm_emit(const KmmGroupArgs &A, const uint32_t *emit_at, unsigned long long *pair, uint16_t *diag, hipStream_t s) {
     if (A.n_records == 0) return hipSuccess;
-    hipLaunchKernelGGL(kmm_emit_kernel, dim3((A.n_records + 255u) / 256u), dim3(256), 0, s, A, emit_at, pair, diag);
+    hipLaunchKernelGGL(A.nucl ? kmm_emit_kernel<true> : kmm_emit_kernel<false>, dim3((A.n_records + 255u) / 256u), dim3(256), 0, s, A, emit_at, pair, diag);
     return hipGetLastError();
 }
 
 // kept_at[n_pairs + 1] (kept_at[n_pairs] = the number of kept runs)
-hipError_t launch_kmm_vote_scan(const unsigned long long *pair, uint32_t n_pairs, uint32_t *tile_sum, uint32_t *kept_at, hipStream_t s) {
-    return scan_u32<PairKept, OpSum, true>(PairKept{pair}, n_pairs, tile_sum, kept_at, s);
+hipError_t launch_kmm_vote_scan(const unsigned long long *pair, uint32_t n_pairs, bool nucl, uint32_t *tile_sum, uint32_t *kept_at, hipStream_t s) {
+    return nucl ? scan_u32<PairKept<true>, OpSum, true>(PairKept<true>{pair}, n_pairs, tile_sum, kept_at, s)
+                : scan_u32<PairKept<false>, OpSum, true>(PairKept<false>{pair}, n_pairs, tile_sum, kept_at, s);
 }
 
-hipError_t launch_kmm_vote(const unsigned long long *pair, const uint16_t *diag, uint32_t n_pairs, const uint32_t *kept_at, uint32_t n_kept, uint32_t n,
+hipError_t launch_kmm_vote(const unsigned long long *pair, const uint16_t *diag, uint32_t n_pairs, bool nucl, const uint32_t *kept_at, uint32_t n_kept, uint32_t n,
                            uint32_t *kept_rep, unsigned long long *offsets, mmgpu_pf_hit *records, hipStream_t s) {
-    if (n_pairs) hipLaunchKernelGGL(kmm_vote_kernel, dim3((n_pairs + 255u) / 256u), dim3(256), 0, s, pair, diag, n_pairs, kept_at, records, kept_rep);
+    if (n_pairs) hipLaunchKernelGGL(nucl ? kmm_vote_kernel<true> : kmm_vote_kernel<false>, dim3((n_pairs + 255u) / 256u), dim3(256), 0, s, pair, diag, n_pairs, kept_at, records, kept_rep);
     hipLaunchKernelGGL(kmm_offsets_kernel, dim3((n + 1u + 255u) / 256u), dim3(256), 0, s, kept_rep, n_kept, n, offsets, records);
     return hipGetLastError();
 }

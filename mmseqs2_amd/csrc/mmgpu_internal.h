@@ -407,14 +407,32 @@ struct KmmGroupArgs {
     uint32_t *group_start;                     // [n_records] index of the record's representative
     float cov_thr;
     int cov_mode, only_extendable;
+    int nucl;                                  // bit 63 of a k-mer is its strand (nuclmatch_api.hip)
 };
+// the extraction over a nucleotide database (nuclmatch_kernel.hip): 2-bit k-mers, the smaller of a window and its reverse complement
+struct NuclExtractArgs {
+    const uint8_t *res;                // the resident database, residues A C T G N = 0 .. 4
+    const uint32_t *off4, *len;
+    const uint32_t *order;             // [n] ids by length, longest first: workgroup b takes sequence order[b]
+    uint32_t n;
+    int k;
+    int kmers_per_seq;
+    float kmers_per_seq_scale;
+    unsigned long long seed;
+    uint4 *rule;                       // as KmmExtractArgs
+    uint32_t *count;
+    const uint32_t *rec_off;
+    unsigned long long *rec_kmer, *rec_val;
+};
+hipError_t launch_nuclmatch_extract_count(const NuclExtractArgs &A, hipStream_t s);
+hipError_t launch_nuclmatch_extract_write(const NuclExtractArgs &A, hipStream_t s);
 hipError_t launch_kmm_extract_count(const KmmExtractArgs &A, hipStream_t s);
 hipError_t launch_kmm_record_offsets(const uint32_t *count, uint32_t n, uint32_t *tile_sum, uint32_t *rec_off, hipStream_t s);
 hipError_t launch_kmm_extract_write(const KmmExtractArgs &A, hipStream_t s);
 hipError_t launch_kmm_group_scan(const KmmGroupArgs &A, uint32_t *tile_sum, uint32_t *emit_at, hipStream_t s);
 hipError_t launch_kmm_emit(const KmmGroupArgs &A, const uint32_t *emit_at, unsigned long long *pair, uint16_t *diag, hipStream_t s);
-hipError_t launch_kmm_vote_scan(const unsigned long long *pair, uint32_t n_pairs, uint32_t *tile_sum, uint32_t *kept_at, hipStream_t s);
-hipError_t launch_kmm_vote(const unsigned long long *pair, const uint16_t *diag, uint32_t n_pairs, const uint32_t *kept_at, uint32_t n_kept, uint32_t n,
+hipError_t launch_kmm_vote_scan(const unsigned long long *pair, uint32_t n_pairs, bool nucl, uint32_t *tile_sum, uint32_t *kept_at, hipStream_t s);
+hipError_t launch_kmm_vote(const unsigned long long *pair, const uint16_t *diag, uint32_t n_pairs, bool nucl, const uint32_t *kept_at, uint32_t n_kept, uint32_t n,
                            uint32_t *kept_rep, unsigned long long *offsets, mmgpu_pf_hit *records, hipStream_t s);
 hipError_t launch_kmm_handover(const unsigned long long *offsets, uint32_t n, const mmgpu_pf_hit *records, uint32_t n_entries, uint32_t *hit_query,
                                mmgpu_rescore_pair *pairs, hipStream_t s);
@@ -1265,7 +1283,9 @@ void scan_sync_for_free(mmgpu_ctx *c);      // before a batch is deleted: nothin
 
 // a k-mer matching batch (kmermatch_api.hip); rescore_api.hip reads its result for the hand-over
 struct mmgpu_kmermatch_batch_t {
-    mmgpu_kmermatch_params par{};
+    mmgpu_kmermatch_params par{};             // (a nucleotide batch: k, the selection, the hash seed and the coverage rule; no alphabet)
+    bool nucl = false;                        // a mmgpu_nuclmatch_batch_t
+    mmgpu::DevBuf d_order;                    // nucl: ids by length, longest first
     uint32_t n = 0;                           // sequences
     uint64_t bound = 0;                       // records at most (computeKmerCount)
     const uint8_t *db_res = nullptr;          // the resident database the batch was prepared against (a reload invalidates the batch)
@@ -1278,4 +1298,14 @@ struct mmgpu_kmermatch_batch_t {
             if (e) (void)hipEventDestroy(e);
     }
 };
+// the nucleotide stage's batch (nuclmatch_api.hip) is the same record under a type of its own: the hand-over to the rescoring does not take it
+struct mmgpu_nuclmatch_batch_t : mmgpu_kmermatch_batch_t {};
+namespace mmgpu {
+// kmermatch_api.hip: what the two stages' entry points share; `who` names the calling entry point in the messages
+int kmm_check_batch(const char *who, const mmgpu_ctx *c, const mmgpu_kmermatch_batch_t *b, bool must_have_run);
+int kmm_new_batch(const char *who, mmgpu_ctx *c, const mmgpu_kmermatch_params &par, bool nucl, uint64_t bound, mmgpu_kmermatch_batch_t *b);
+int kmm_run_impl(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b);
+int kmm_fetch(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, mmgpu_kmermatch_counts *counts, void *offsets, void *records, hipMemcpyKind kind);
+int kmm_kernel_ms(const char *who, mmgpu_ctx *c, mmgpu_kmermatch_batch_t *b, float *ms);
+}
 #endif

@@ -264,6 +264,22 @@ int mmgpu_kmermatch_rescore_prepare(mmgpu_ctx *, const mmgpu_rescore_params *, m
     if (batch) *batch = nullptr;
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_kmermatch_rescore_prepare: not served through mmgpu_server");
 }
+// the same stage over a nucleotide database
+int mmgpu_nuclmatch_prepare(mmgpu_ctx *, const mmgpu_nuclmatch_params *, mmgpu_nuclmatch_batch_t **batch) {
+    if (batch) *batch = nullptr;
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_nuclmatch_prepare: not served through mmgpu_server (the binary runs kmermatcher on the host)");
+}
+int mmgpu_nuclmatch_run(mmgpu_ctx *, mmgpu_nuclmatch_batch_t *) { return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_nuclmatch_run: not served through mmgpu_server"); }
+int mmgpu_nuclmatch_fetch(mmgpu_ctx *, mmgpu_nuclmatch_batch_t *, mmgpu_kmermatch_counts *, uint64_t *, mmgpu_pf_hit *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_nuclmatch_fetch: not served through mmgpu_server");
+}
+int mmgpu_nuclmatch_fetch_device(mmgpu_ctx *, mmgpu_nuclmatch_batch_t *, void *, void *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_nuclmatch_fetch_device: not served through mmgpu_server");
+}
+int mmgpu_nuclmatch_last_kernel_ms(mmgpu_ctx *, mmgpu_nuclmatch_batch_t *, float *) {
+    return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_nuclmatch_last_kernel_ms: not served through mmgpu_server");
+}
+void mmgpu_nuclmatch_free(mmgpu_ctx *, mmgpu_nuclmatch_batch_t *) {}
 int mmgpu_rescore_batch(mmgpu_ctx *, const mmgpu_rescore_params *, const mmgpu_rescore_query *, uint32_t, const uint64_t *, const mmgpu_rescore_pair *,
                         mmgpu_rescore_hit *) {
     return fail(MMGPU_ERR_UNSUPPORTED, "mmgpu_rescore_batch: not served through mmgpu_server (the binary runs rescorediagonal on the host)");
